@@ -17,6 +17,14 @@ workload (/8: xGMI-link-bound) and once for the /320 cascade (where the gather v
 All GPU collectives are the C library's own RCCL calls (pddc_comm_*, ddc_multi.cpp);
 torch.distributed is only the rendezvous (a gloo group carrying the 128-byte RCCL id).
 
+A plain run does what the headline figure needs and nothing else: set-up (with the placement
+probes below), settle and W warm-up steps, the K timed steps, --dump-outputs if asked, the line.
+Everything else the line can carry -- the measured copy ceiling, the oracle check of the
+output (`verified`), `cpu_baseline`, the gather legs at N>1, `wall_budget_s` -- runs only
+with --full (off by default); there those fields read as described below, without it they
+are null.  --dump-outputs DIR writes the last timed step's output (rank r: DIR/output_rank<r>.npy,
+float32 [rows, 2], I and Q; larger outputs as a fixed, seeded sample of whole blocks of rows).
+
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (k_fir8):
 algorithmic bytes = 7 B per input sample (6 packed in + 8/8 out) over the
 kernel's average duration measured with HIP events on the launch stream;
@@ -47,6 +55,9 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 PARITY_METRIC = "max|y-ref| / max|ref| per window (full-scale-relative), ref = CPU oracle with double accumulation"
 PARITY_TOL = 1e-6               # BASELINE.json north_star: FIR within 1e-6 of the CPU reference
+DUMP_BUDGET_BYTES = 48 << 20    # --dump-outputs: all ranks' files together (float32 I/Q rows)
+DUMP_BLOCK_ROWS = 4096          # a sampled dump keeps whole blocks of this many consecutive rows
+DUMP_SEED = 2026
 
 
 def parse(argv=None):
@@ -73,16 +84,23 @@ def parse(argv=None):
                          "form, which then holds the taps on the device as binary16 (2 bytes a tap) and whose matrix waves\n"
                          "quantise them into their operand themselves; the vector kernels keep the binary16 VALUES in fp32 registers (their\n"
                          "taps sit in SGPRs in the hot loop: no storage to halve)")
-    ap.add_argument("--gather", action="store_true", help="run the gather leg at N=1 too (1-rank RCCL group)")
-    ap.add_argument("--no-gather", action="store_true", help="skip the gather leg at N>1")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the copy ceiling, the oracle check of the last output, the cpu_baseline leg\n"
+                         "(N=1) and the gather legs (N>1); a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's output as DIR/output_rank<r>.npy (float32\n"
+                         "[rows, 2]; all ranks together at most %d MiB: a larger output as a fixed, seeded sample of blocks\n"
+                         "of %d rows)" % (DUMP_BUDGET_BYTES >> 20, DUMP_BLOCK_ROWS))
+    ap.add_argument("--gather", action="store_true", help="run the gather leg at N=1 too (1-rank RCCL group), with or without --full")
+    ap.add_argument("--no-gather", action="store_true", help="--full: skip the gather leg at N>1")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--recheck-placement", action="store_true",
                     help="diagnostics: right after the timed region, time every probed output slot again (24 launches\n"
                          "each, the chosen one first and last): the line gains `placement_recheck_ms`")
     ap.add_argument("--per-step-events", action="store_true",
                     help="diagnostics: a HIP event after every timed step; the line gains `per_step_ms` (the extra\n"
                          "records cost about a microsecond per step, so this is not the default)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle window check of the last output")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the oracle window check of the last output")
     ap.add_argument("--no-verify-all", action="store_true",
                     help="windows only: skip the every-output comparison of the last step (hosts with fewer than 16 cores skip it anyway)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -434,6 +452,56 @@ def arena_plan(free_bytes, in_bytes, out_bytes, ws_bytes, arena_gib):
             "search": out_bytes + ws_bytes >= (32 << 20)}
 
 
+def state_period(ns, wl):
+    """Steps after which the stream's state repeats: every step pushes the same ns-sample batch, so what a step outputs
+    depends only on where the stream stands in the decimation phases (ns mod the total decimation) and in the NCO phase
+    (ns * FREG mod 2^32, uint32 arithmetic as in the kernels).  The untimed launches are padded to a multiple of this,
+    so that the last timed step computes the same outputs from run to run, however many launches settling took and
+    whatever --steps and --warmup are."""
+    from math import gcd
+    if wl["stages"] is None:
+        return 1
+    p = wl["decim"] // gcd(ns, wl["decim"])
+    if wl["mix"]:
+        q = (1 << 32) // gcd((wl["freg"] * ns) % (1 << 32), 1 << 32)
+        p = p * q // gcd(p, q)
+    return p
+
+
+def dump_rows(n_rows, world):
+    """Rows of an n_rows-row output that --dump-outputs keeps: None (all of them) when they fit this rank's share of
+    DUMP_BUDGET_BYTES, else whole blocks of DUMP_BLOCK_ROWS rows -- the first, the last and a seeded choice of the
+    others, in order -- as a sorted int64 index array."""
+    import numpy as np
+    budget = DUMP_BUDGET_BYTES // max(1, world) // 8
+    if n_rows <= budget:
+        return None
+    nb = -(-n_rows // DUMP_BLOCK_ROWS)
+    k = max(2, budget // DUMP_BLOCK_ROWS)
+    inner = np.random.default_rng(DUMP_SEED).choice(np.arange(1, nb - 1), size=k - 2, replace=False)
+    blocks = np.sort(np.concatenate([[0, nb - 1], inner]).astype(np.int64))
+    rows = (blocks[:, None] * DUMP_BLOCK_ROWS + np.arange(DUMP_BLOCK_ROWS, dtype=np.int64)[None, :]).reshape(-1)
+    return rows[rows < n_rows]
+
+
+def dump_output(path, y, world):
+    """Write y (torch float32 [n, 2] on the device: the rows a caller of the timed path receives) to `path` as .npy,
+    sampled per dump_rows; returns the line's description of what was written."""
+    import numpy as np
+    import torch
+    n_rows = int(y.shape[0])
+    rows = dump_rows(n_rows, world)
+    if rows is not None:
+        y = y[torch.from_numpy(rows).to(y.device)]
+    arr = np.ascontiguousarray(y.to(torch.float32).cpu().numpy())
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.save(path, arr)
+    return {"file": os.path.basename(path), "shape": list(arr.shape), "dtype": "float32", "of_rows": n_rows,
+            "sample": None if rows is None else
+            "blocks of %d consecutive rows: the first, the last and %d more drawn with numpy default_rng(%d)"
+            % (DUMP_BLOCK_ROWS, -(-rows.size // DUMP_BLOCK_ROWS) - 2, DUMP_SEED)}
+
+
 # ----------------------------------------------------------------------------------------
 def wall_budget(world, steps, warmup, log2n, arena_rest_s=3.0, settle_ms=250.0, verify_all=True, gather=True):
     """What a run of this bench SHOULD take on the wall, by phase, in seconds -- so that the first real 8-GPU run has a
@@ -666,7 +734,11 @@ def run_rank(a):
         step()
     torch.cuda.synchronize(dev)
     ms_est = max((time.perf_counter() - t_cal) * 1e3 / 8, 1e-3)
-    for _ in range(min(int(a.settle_ms / ms_est) + 1, 100000)):
+    n_settle = min(int(a.settle_ms / ms_est) + 1, 100000)
+    per = state_period(ns, wl)
+    if per <= 4096:                                     # the same last timed step in every run (tiny NCO batches: not padded)
+        n_settle += -(calls[0] + n_settle + a.warmup + a.steps) % per
+    for _ in range(n_settle):
         step()
     for _ in range(a.warmup):
         step()
@@ -740,38 +812,44 @@ def run_rank(a):
         outbox[0] = out_view(bo)
     # measured copy ceiling: a device-to-device copy that moves as many bytes through HBM as
     # one launch of the dominant kernel does (nbytes read + nbytes written)
+    # (a run of its own: --full only)
     copy_gbps = None
-    try:
-        import ctypes
-        nb = int(wl["kernel_bytes_per_sample"] * ns / 2) // 256 * 256
-        if arena is not None and nb <= slot:
-            # under the same favourable placement as the kernel: source = the chosen input slot, destination = the
-            # fastest of the other slots (never the one that holds the output still to be verified)
-            src_ptr = arena[bi * slot:bi * slot + nb].data_ptr()
-            quick = {o: pkg.measure_copy(arena[o * slot:o * slot + nb].data_ptr(), src_ptr, nb, 6, stream)
-                     for o in range(nslot) if o not in (bi, bo)}
-            od = min(quick, key=quick.get)
-            ms = pkg.measure_copy(arena[od * slot:od * slot + nb].data_ptr(), src_ptr, nb, 40, stream)
-        else:
-            src = d_in[:nb] if nb <= d_in.numel() else torch.empty(nb, dtype=torch.uint8, device=dev)
-            # destination in another HBM extent class than the source (pddc_malloc_apart)
-            dst = ctypes.c_void_p()
-            pkg.check(pkg.ddc_lib().pddc_malloc_apart(ctypes.byref(dst), nb, src.data_ptr(), nb, 24, None, None))
-            ms = pkg.measure_copy(dst.value, src.data_ptr(), nb, 40, stream)
-            pkg.check(pkg.ddc_lib().pddc_free(dst))
-            del src
-        copy_gbps = 2.0 * nb / (ms * 1e-3) / 1e9
-    except Exception as e:                              # never lose the line over the extra figure
-        print(f"[bench] copy ceiling failed: {e}", file=sys.stderr)
+    if a.full:
+        try:
+            import ctypes
+            nb = int(wl["kernel_bytes_per_sample"] * ns / 2) // 256 * 256
+            if arena is not None and nb <= slot:
+                # under the same favourable placement as the kernel: source = the chosen input slot, destination = the
+                # fastest of the other slots (never the one that holds the output still to be verified)
+                src_ptr = arena[bi * slot:bi * slot + nb].data_ptr()
+                quick = {o: pkg.measure_copy(arena[o * slot:o * slot + nb].data_ptr(), src_ptr, nb, 6, stream)
+                         for o in range(nslot) if o not in (bi, bo)}
+                od = min(quick, key=quick.get)
+                ms = pkg.measure_copy(arena[od * slot:od * slot + nb].data_ptr(), src_ptr, nb, 40, stream)
+            else:
+                src = d_in[:nb] if nb <= d_in.numel() else torch.empty(nb, dtype=torch.uint8, device=dev)
+                # destination in another HBM extent class than the source (pddc_malloc_apart)
+                dst = ctypes.c_void_p()
+                pkg.check(pkg.ddc_lib().pddc_malloc_apart(ctypes.byref(dst), nb, src.data_ptr(), nb, 24, None, None))
+                ms = pkg.measure_copy(dst.value, src.data_ptr(), nb, 40, stream)
+                pkg.check(pkg.ddc_lib().pddc_free(dst))
+                del src
+            copy_gbps = 2.0 * nb / (ms * 1e-3) / 1e9
+        except Exception as e:                          # never lose the line over the extra figure
+            print(f"[bench] copy ceiling failed: {e}", file=sys.stderr)
 
     dt_max = grp.max_seconds(dt)
     if pipe is not None:
         pipe.check(stream)                              # a kernel-side failure flag (fused cascade) fails the run
 
     phase("settle_warmup_timed")
+    dumped = None
+    if a.dump_outputs:                                  # what the last timed step handed its caller
+        dumped = dump_output(os.path.join(a.dump_outputs, f"output_rank{rank}.npy"), out[:n_last], world)
+        phase("dump_outputs")
     # ---- parity of what was just timed (outside the timed region, every rank its own stream)
     verified = None
-    if not a.no_verify:
+    if a.full and not a.no_verify:
         if world > 1:                                   # the checker's OpenMP team: this rank's share of the node's cores
             os.environ.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or 1) // world)))
         from oracle import oracle as O
@@ -899,11 +977,13 @@ def run_rank(a):
                             "no collective): the RCCL communicator could not be made -- " + grp.comm_error)
                            if grp.comm_error else None,
             "cpu_baseline": None,
+            "dumped": dumped,
         }
         PARTIAL["res"] = res
 
-    # ---- BASELINE config 4: gather of every rank's output on rank 0's GPU (RCCL, C library)
-    if grp.comm is not None and stages is not None and not a.no_gather:
+    # ---- BASELINE config 4: gather of every rank's output on rank 0's GPU (RCCL, C library); --full (or --gather) only
+    gather = (a.full or a.gather) and not a.no_gather
+    if grp.comm is not None and stages is not None and gather:
         out2 = spare = None
         if arena is not None and in_span + ws_span + 2 * out_bytes + 256 <= slot:
             at = bo * slot + in_span + ws_span + ((out_bytes + 255) & ~255)      # right behind `out`, same slot
@@ -928,17 +1008,18 @@ def run_rank(a):
                                       "per_link_GBps": tc.get("per_link_GBps"),
                                       "expected": "kernel-bound: 6.7 MB per rank and step, the gather disappears under the next step's kernels"}
                                      if tc else None)}
-    elif res is not None and grp.comm_error and stages is not None and not a.no_gather:
+    elif res is not None and grp.comm_error and stages is not None and gather:
         res["gather"] = {"skipped": "the gather is RCCL by definition and no communicator exists: " + grp.comm_error}
-    if res is not None and world == 1 and not a.no_cpu:
+    if res is not None and world == 1 and a.full and not a.no_cpu:
         res["cpu_baseline"] = cpu_baseline(a.workload, a.cpu_seconds)
         phase("cpu_baseline")
     if res is not None:
         # rank 0's wall clock by phase beside what the phases should take (wall_budget): a first 8-GPU run that strays from
         # its budget says where
         res["phases_s"] = dict(phases, total=round(sum(phases.values()), 2))
-        res["wall_budget_s"] = wall_budget(world, a.steps, a.warmup, a.log2n, a.arena_rest_s, a.settle_ms,
-                                           not a.no_verify_all, grp.comm is not None and not a.no_gather)
+        if a.full:                                      # (what a --full run should take)
+            res["wall_budget_s"] = wall_budget(world, a.steps, a.warmup, a.log2n, a.arena_rest_s, a.settle_ms,
+                                               not a.no_verify_all, grp.comm is not None and gather)
     finish(grp, res)
 
 
@@ -1046,6 +1127,8 @@ def run_api250k(a):
     250 kS/s setting, 7.1 MHz, float32 callback buffers from the GPU (mode ddc), the synthetic LCG stream generated on the
     device, unpaced.  A "step" is one GPU batch of the stream; the client stamps the callback that completes batch W and
     the one that completes batch W + K.  This process makes no GPU call (the child owns the device)."""
+    if a.dump_outputs:
+        raise SystemExit("--dump-outputs: api250k's outputs are the C client's callback buffers, which this process never sees")
     here = os.path.dirname(os.path.abspath(__file__))
     exe = os.path.join(here, "libperseus-sdr_amd", "perseus_plumbing")
     if not os.path.exists(exe):

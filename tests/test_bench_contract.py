@@ -28,6 +28,43 @@ def test_defaults_follow_the_contract(monkeypatch):
     assert b.HBM_PEAK_GBS == 8000.0
 
 
+def test_full_and_dump_outputs_options(monkeypatch):
+    """A plain run is the headline only: --full (off by default) brings the other legs; --dump-outputs names a directory."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None
+    a = b.parse(["--full", "--dump-outputs", "some/dir", "--steps", "3"])
+    assert a.full is True and a.dump_outputs == "some/dir" and a.steps == 3
+
+
+def test_dump_rows_fixed_sample_within_budget():
+    """--dump-outputs keeps a whole output that fits its share of the budget; a larger one as whole blocks of rows, the
+    first and the last among them, the same blocks in every run, all ranks together under 64 MB of float32 I/Q rows."""
+    import numpy as np
+    b = _bench()
+    assert b.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+    assert b.dump_rows(1 << 20, 1) is None
+    for n, world in (((1 << 28) // 8, 1), (1 << 28, 1), ((1 << 28) // 8, 8), (3 * b.DUMP_BLOCK_ROWS * 1000 + 17, 2)):
+        r = b.dump_rows(n, world)
+        assert r is not None and np.array_equal(r, b.dump_rows(n, world))
+        assert r.size * 8 * world <= b.DUMP_BUDGET_BYTES and np.all(np.diff(r) > 0)
+        assert r[0] == 0 and r[-1] == n - 1 and r.size % b.DUMP_BLOCK_ROWS in (0, n % b.DUMP_BLOCK_ROWS)
+
+
+def test_state_period_of_the_periodic_stream():
+    """The untimed launches are padded to whole periods of the stream's state, so that the last timed step -- what
+    --dump-outputs writes -- is the same in every run: decimation phase (ns mod the total decimation) and NCO phase."""
+    b = _bench()
+    ns = 1 << 28
+    assert b.state_period(ns, b.workload_def("d8_127")) == 1
+    assert b.state_period(ns, b.workload_def("unpack")) == 1
+    w = b.workload_def("c320_fixture")
+    p = b.state_period(ns, w)
+    assert p == 80 and (p * ns) % 320 == 0 and (p * ns * w["freg"]) % (1 << 32) == 0
+    assert all((q * ns) % 320 or (q * ns * w["freg"]) % (1 << 32) for q in range(1, p))
+
+
 def test_cpu_baseline_leg_fields():
     b = _bench()
     r = b.cpu_baseline("d8_127", 0.2)
@@ -164,9 +201,9 @@ def test_launcher_reports_failure_when_ranks_fail():
 
 @pytest.mark.gpu
 def test_bench_line_end_to_end_on_the_gpu():
-    """The real thing, small: one JSON line, last on stdout, metric string verbatim from
+    """The real thing, small, with --full: one JSON line, last on stdout, metric string verbatim from
     BASELINE.json, roofline and cpu_baseline objects present and self-consistent."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--log2n", "24",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "8", "--warmup", "2", "--log2n", "24",
                         "--settle-ms", "20", "--cpu-seconds", "0.5"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -202,6 +239,34 @@ def test_bench_line_end_to_end_on_the_gpu():
     assert pl is None or ((pl["probe_pairs"] <= 12 or pl["grown_after"]) and pl["first_come_ms"] >= pl["chosen"]["ms"])
     assert pl is None or pl["arena_GiB"] <= 72                           # a quarter of the HBM at most, never grown by default
     assert "value_first_come" in d and (pl is None or 0 < d["value_first_come"] <= d["value"] * 1.1)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_its_dumps_repeat(tmp_path):
+    """A plain run times exactly --steps steps and carries none of the --full legs; --dump-outputs writes the last timed
+    step's output, and a second run writes the same bits, even with other --steps / --warmup (the /320 cascade with the
+    NCO: the untimed launches are padded so that the last timed step lies at the same phase of the stream's state)."""
+    import numpy as np
+    dumps = []
+    for k, (steps, warmup) in enumerate(((7, 2), (5, 3))):
+        d = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
+                            "--log2n", "24", "--settle-ms", "20", "--workload", "c320_fixture", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+        assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0 and line["dtype"]
+        assert line["unit"] == "MS/s"
+        assert abs(line["value"] - (1 << 24) / (line["ms_per_step"] * 1e-3) / 1e6) / line["value"] < 0.01
+        assert line["verified"] is None and line["cpu_baseline"] is None and "gather" not in line
+        assert line["roofline"]["copy_ceiling_GBps"] is None and "wall_budget_s" not in line
+        assert line["dumped"]["file"] == "output_rank0.npy" and sorted(os.listdir(d)) == ["output_rank0.npy"]
+        y = np.load(d / "output_rank0.npy")
+        assert y.dtype == np.float32 and y.ndim == 2 and y.shape[1] == 2 and list(y.shape) == line["dumped"]["shape"]
+        assert y.shape[0] == line["dumped"]["of_rows"] in ((1 << 24) // 320, (1 << 24) // 320 + 1) and np.isfinite(y).all()
+        assert np.abs(y).max() > 0
+        dumps.append(y)
+    assert np.array_equal(dumps[0].view(np.uint32), dumps[1].view(np.uint32))
 
 
 def test_eight_rank_dry_run_of_the_launcher():

@@ -122,7 +122,7 @@ def test_comm_init_all_grouped_calls(pkg, O, dev):
 def test_bench_gather_leg_on_one_rank():
     """bench.py --gather: the N>1 code path (RcclGroup, plan broadcast, double-buffered gather on the side
     stream) on a 1-rank communicator."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--log2n", "24",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--log2n", "24",
                         "--settle-ms", "20", "--no-cpu", "--gather"], capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, PDDC_BENCH_GATHER_C320="1"))
     assert p.returncode == 0, p.stderr[-2000:]

@@ -27,12 +27,12 @@ if [ "$MODE" = run ]; then
   # 2. the suite as the driver runs it, and smoke
   timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $F/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $F/pytest_gpu.log
   python -c "import __graft_entry__ as g; g.smoke()" > $F/smoke.log 2>&1
-  # 3. the bench line with the driver's arguments, then every workload
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $F/bench_driver_args.json 2> $F/bench_driver_args.err
+  # 3. the bench line with the driver's arguments (--full: copy ceiling, verified, cpu_baseline), then every workload
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > $F/bench_driver_args.json 2> $F/bench_driver_args.err
   for wl in d8_127 d8_255 c320 c320_fixture unpack; do
-    timeout 300 python bench.py --no-cpu --workload $wl --steps 40 --warmup 10 2>$F/bench_$wl.err | tail -1 > $F/bench_$wl.json
+    timeout 300 python bench.py --full --no-cpu --workload $wl --steps 40 --warmup 10 2>$F/bench_$wl.err | tail -1 > $F/bench_$wl.json
   done
-  timeout 300 python bench.py --no-cpu --workload d8_255 --taps-fp16 --steps 40 --warmup 10 2>$F/bench_d8_255_fp16.err | tail -1 > $F/bench_d8_255_fp16.json
+  timeout 300 python bench.py --full --no-cpu --workload d8_255 --taps-fp16 --steps 40 --warmup 10 2>$F/bench_d8_255_fp16.err | tail -1 > $F/bench_d8_255_fp16.json
   # 4. rocprofv3 kernel stats + the timed region's trace of the headline command
   bash tools/trace_gaps.sh d8_127 $F/trace_d8_127 --steps 200 --warmup 5 > $F/trace_d8_127.txt 2>&1
   cp $(find $F/trace_d8_127/prof -name "*kernel_stats.csv" | head -1) $F/kernel_stats_d8_127.csv 2>/dev/null
