@@ -164,10 +164,7 @@ struct pddc_pipeline {
     Fir8Stage3 s3;
     void *d_seam = nullptr;
     unsigned *d_flags = nullptr;
-    /* gang submission (pddc_gang_push_async): several pipelines of one GPU share one launch chain.  gang_rec != NULL
-     * turns pddc_pipeline_process into "record, do not launch": the first-stage launch and the tail behind it are
-     * written there, the gang launches them for all its members at once.                                          */
-    struct GangRec *gang_rec = nullptr;
+    /* gang submission (pddc_gang_push_async): several pipelines of one GPU share one launch chain */
     struct pddc_gang *gang = nullptr;        /* the gang whose stream the last push used (NULL: the pipeline's own)   */
     /* kernel selection (pddc_pipeline_set_option; defaults = what the measurements chose; the environment is looked at
      * once, when the pipeline is created, never on the data path) */
@@ -225,19 +222,6 @@ struct pddc_pipeline {
 static constexpr size_t kI8xSlotBytes = 64 * 1024;     /* tables (<= 48 KB) + the second stage's taps at kI8xTaps2Off */
 static constexpr size_t kI8xTaps2Off = 60 * 1024;
 
-/* what one member's process() leaves for the gang: kind 0 = nothing recorded */
-struct GangRec {
-    int kind = 0;                 /* 1: the packed /8 first stage alone (launch_fir8), 2: the fused pair; 3: k_fir_i8x
-                                     (the tuned first stage on the matrix cores, alone or as its fused pair: `fuse2`)  */
-    int ntb = 0, R = 4;
-    bool mix = false;
-    Fir8Args a;
-    FirI8xArgs ax;                /* kind 3 */
-    int hist = 0, chunk = 0, layout = -1, blocks = 0;
-    bool fuse2 = false;
-    GenTail tail;                 /* nblocks == 0: the plan ends with the first-stage kernel                       */
-};
-
 struct pddc_gang {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -251,9 +235,7 @@ struct pddc_gang {
 
 static bool stage0_fused(const pddc_pipeline *p);
 static bool stage0_packed_generic(const pddc_pipeline *p);
-static int stage0_i8_kind(const pddc_pipeline *p, size_t nsamples);
 static int setup_stage3(pddc_pipeline *p);
-static bool stages01_i8x(const pddc_pipeline *p, size_t nsamples);
 static int leave_gang(pddc_pipeline *p);
 static float *direct_out(pddc_pipeline::HostSlot &sl, void *h_out);
 
@@ -1196,16 +1178,25 @@ static void stage_outputs(unsigned long long consumed, size_t n, int D, int L, s
     *n_out = n > off ? (size_t)((n - off - 1) / (size_t)D + 1) : 0;
 }
 
-/* outputs the NEXT process() of nsamples will produce, from the stream position alone */
+/* what the NEXT process() of nsamples does per stage, from the stream position alone: n_in[i] inputs of stage i
+ * (n_in[nstages]: the outputs), its first output at input off[i], output index m0[i]                            */
+struct BatchPlan {
+    size_t n_in[PDDC_MAX_STAGES + 1], off[PDDC_MAX_STAGES];
+    unsigned long long m0[PDDC_MAX_STAGES];
+};
+
+static void plan_batch(const pddc_pipeline *p, size_t nsamples, BatchPlan &b)
+{
+    b.n_in[0] = nsamples;
+    for (int i = 0; i < p->nstages; ++i)
+        stage_outputs(p->st[i].consumed, b.n_in[i], p->st[i].decim, p->st[i].interp, &b.off[i], &b.m0[i], &b.n_in[i + 1]);
+}
+
 static size_t predict_outputs(const pddc_pipeline *p, size_t nsamples)
 {
-    size_t n = nsamples, off, nout;
-    unsigned long long m0;
-    for (int i = 0; i < p->nstages; ++i) {
-        stage_outputs(p->st[i].consumed, n, p->st[i].decim, p->st[i].interp, &off, &m0, &nout);
-        n = nout;
-    }
-    return n;
+    BatchPlan b;
+    plan_batch(p, nsamples, b);
+    return b.n_in[p->nstages];
 }
 
 size_t pddc_pipeline_next_output(const pddc_pipeline *p, size_t nsamples_in)
@@ -1238,6 +1229,10 @@ static size_t words_in_window(const pddc_pipeline *p)
         ++first;
     return p->segs.size() - first;
 }
+
+/* ---- the route: which kernels run a batch ---------------------------------------------------------------------------
+ * choose_route() is the one place that decides it; process_batch(), the gang, pddc_pipeline_time_stage0, _schedule,
+ * _place_buffers and the queries below all ask it.  The predicates in front of it are its parts and nothing else's.  */
 
 /* Which kernel runs the decimate-by-8 first stage of this batch: 0 the vector kernel (k_fir8), 2 k_fir_i8x (the wire bytes
  * on the int8 matrix cores; tuned: the NCO folded into the taps -- every first stage of 1..256 taps whose history window
@@ -1275,54 +1270,8 @@ static bool i8x_pair_ok(const pddc_pipeline *p, size_t nsamples)
     return nsamples > 0 && nsamples % 8192 == 0 && s0.consumed % 8 == 0 && s1.consumed % 8 == 0;
 }
 
-static bool stages01_fusable(const pddc_pipeline *p, size_t nsamples);
-/* ... with one more rule for cascades: where this batch cannot take k_fir_i8x's fused pair (not whole 8192-sample tiles, or
- * larger than the pair is good for) but CAN take k_fir8's (tiles of 4096), the vector pair wins over matrix-core stage 0 +
- * a second-stage kernel of its own */
-static int stage0_i8_kind(const pddc_pipeline *p, size_t nsamples)
-{
-    const int k = stage0_i8_kind_raw(p, nsamples);
-    if (k == 2 && p->nstages >= 2 && !i8x_pair_ok(p, nsamples) && stages01_fusable(p, nsamples))
-        return 0;
-    /* (Measured and not added: in overlap mode a two-stage plan's tail -- the /5 of 2 MS/s, the /10 of 1 MS/s -- could ride
-     * in k_fir8's launch, which k_fir_i8x, one block of twelve waves per CU, cannot offer.  2^28 samples, same process,
-     * each twice: 8 * 5 vector + carried tail 0.405 / 0.457 ms, k_fir_i8x + tail in line 0.425 / 0.408; 8 * 10 0.452 / 0.407
-     * against 0.4255 / 0.4259: no winner, and the matrix-core path is the steadier one.  tools/plan_rates.py --overlap) */
-    return k;
-}
-
-/* the tuned decimate-by-10 first stage (the 1.6 MS/s plan's) on k_fir_i8x's paired-rows form: up to 57 taps (the taps are
- * delayed by up to 7 samples to put a batch's first window on a multiple of 8), one tuning word in the history window */
-static bool stage0_packed_generic(const pddc_pipeline *p);
-static bool i8x_d10_ok(const pddc_pipeline *p)
-{
-    const Stage &s0 = p->st[0];
-    return stage0_packed_generic(p) && (p->flags & PDDC_F_MIX) && p->opt.i8x && !p->opt.no_i8 && s0.decim == 10 && s0.interp == 1 &&
-           s0.ntaps + 7 <= kFirI8xD10Hist && s0.hist >= 8 && s0.hist % 8 == 0 && s0.hist <= kFirI8xD10Hist && s0.i8x_ok &&
-           words_in_window(p) == 1;
-}
-
-int pddc_pipeline_stage0_on_i8(const pddc_pipeline *p, size_t nsamples)
-{
-    return !p ? 0 : i8x_d10_ok(p) && nsamples >= 8 ? 2 : stage0_i8_kind(p, nsamples);
-}
-
-/* a first stage that is a plain decimator but not the fused decimate-by-8 (e.g. the /10 of the
- * 1.6 MS/s plan): the generic kernel reads the packed samples itself (unpack and mix while it
- * stages), so no float2 intermediate is written.  Its history is then kept packed too.        */
-static bool stage0_packed_generic(const pddc_pipeline *p)
-{
-    return p->st[0].interp == 1 && !stage0_fused(p) && !(p->flags & PDDC_F_NO_FAST);
-}
-
-int pddc_pipeline_stage0_reads_packed(const pddc_pipeline *p)
-{
-    return p && (stage0_fused(p) || stage0_packed_generic(p)) ? 1 : 0;
-}
-
-/* stages 0+1 run as one kernel when: stage 0 is the fused decimate-by-8, stage 1
- * is a plain decimate-by-8 with <= 64 taps, the batch is whole tiles, and both
- * stages sit on an 8-sample phase boundary */
+/* stages 0+1 run as one kernel (k_fir8's fused pair) when: stage 0 is the fused decimate-by-8, stage 1 is a plain
+ * decimate-by-8 with <= 64 taps, the batch is whole tiles, and both stages sit on an 8-sample phase boundary */
 static bool stages01_fusable(const pddc_pipeline *p, size_t nsamples)
 {
     if (p->nstages < 2 || !stage0_fused(p) || p->opt.no_fuse2)
@@ -1336,11 +1285,120 @@ static bool stages01_fusable(const pddc_pipeline *p, size_t nsamples)
            s1.consumed % 8 == 0;
 }
 
-/* the cascade's first two stages as k_fir_i8x's fused pair: stage 0 on the matrix cores, stage 1 -- a plain decimate-by-8
- * of <= 64 taps -- on its values while they are still in LDS; whole tiles of 8192 samples */
-static bool stages01_i8x(const pddc_pipeline *p, size_t nsamples)
+/* stage0_i8_kind_raw with one more rule for cascades: where this batch cannot take k_fir_i8x's fused pair (not whole
+ * 8192-sample tiles, or larger than the pair is good for) but CAN take k_fir8's (tiles of 4096), the vector pair wins over
+ * matrix-core stage 0 + a second-stage kernel of its own */
+static int stage0_i8_kind(const pddc_pipeline *p, size_t nsamples)
 {
-    return stage0_i8_kind(p, nsamples) == 2 && i8x_pair_ok(p, nsamples);
+    const int k = stage0_i8_kind_raw(p, nsamples);
+    if (k == 2 && p->nstages >= 2 && !i8x_pair_ok(p, nsamples) && stages01_fusable(p, nsamples))
+        return 0;
+    /* (Measured and not added: in overlap mode a two-stage plan's tail -- the /5 of 2 MS/s, the /10 of 1 MS/s -- could ride
+     * in k_fir8's launch, which k_fir_i8x, one block of twelve waves per CU, cannot offer.  2^28 samples, same process,
+     * each twice: 8 * 5 vector + carried tail 0.405 / 0.457 ms, k_fir_i8x + tail in line 0.425 / 0.408; 8 * 10 0.452 / 0.407
+     * against 0.4255 / 0.4259: no winner, and the matrix-core path is the steadier one.  tools/plan_rates.py --overlap) */
+    return k;
+}
+
+/* Opt-in (PDDC_FUSE3=1, the whole cascade in one kernel: setup_stage3): measured on MI355X the one-kernel cascade is
+ * SLOWER than the fused pair followed by the tail kernel -- x320 at 2^28 samples 0.323 against 0.287 + 0.027 ms, no gain
+ * at 2^20..2^22 either (profiles/r03/c_fused_cascade_*.txt) -- because k_fir8 is bound by each block's own dependency
+ * chain, and work added to the same waves lengthens it one for one; the tail costs less on OTHER waves
+ * (pddc_pipeline_set_overlap).                                                                                        */
+static bool stages012_fusable(const pddc_pipeline *p, size_t nsamples)
+{
+    return p->s3_ok && p->nstages >= 3 && p->opt.fuse3 == 1 && stages01_fusable(p, nsamples);
+}
+
+/* a first stage that is a plain decimator but not the fused decimate-by-8 (e.g. the /10 of the
+ * 1.6 MS/s plan): the generic kernel reads the packed samples itself (unpack and mix while it
+ * stages), so no float2 intermediate is written.  Its history is then kept packed too.        */
+static bool stage0_packed_generic(const pddc_pipeline *p)
+{
+    return p->st[0].interp == 1 && !stage0_fused(p) && !(p->flags & PDDC_F_NO_FAST);
+}
+
+/* the tuned decimate-by-10 first stage (the 1.6 MS/s plan's) on k_fir_i8x's paired-rows form: up to 57 taps (the taps are
+ * delayed by up to 7 samples to put a batch's first window on a multiple of 8), one tuning word in the history window */
+static bool i8x_d10_ok(const pddc_pipeline *p)
+{
+    const Stage &s0 = p->st[0];
+    return stage0_packed_generic(p) && (p->flags & PDDC_F_MIX) && p->opt.i8x && !p->opt.no_i8 && s0.decim == 10 && s0.interp == 1 &&
+           s0.ntaps + 7 <= kFirI8xD10Hist && s0.hist >= 8 && s0.hist % 8 == 0 && s0.hist <= kFirI8xD10Hist && s0.i8x_ok &&
+           words_in_window(p) == 1;
+}
+
+/* The first launch of a batch.  The first six launch one kernel from a FirstLaunch record (build_first, launch_first);
+ * the last three run stage 0 in line (run_stage).                                                                   */
+enum class Route {
+    I8xPair,        /* k_fir_i8x's fused pair: stage 0 on the matrix cores, stage 1 on its outputs in LDS           */
+    Fused3,         /* k_fir8 FUSE3, the fused cascade: stages 0, 1 and 2 (opt-in, stages012_fusable)               */
+    Fir8Pair,       /* k_fir8's fused pair                                                                          */
+    I8x,            /* k_fir_i8x alone: the fused decimate-by-8 first stage on the matrix cores                     */
+    Fir8,           /* k_fir8 alone                                                                                 */
+    I8xD10,         /* the tuned decimate-by-10 first stage on k_fir_i8x (i8x_d10_ok)                               */
+    PackedGeneric,  /* k_firp or k_fir_generic on the packed samples (stage0_packed_generic)                        */
+    MixedHist,      /* stage 0's history window holds several tuning words: unpack stretch by stretch, k_fir_generic */
+    Unpack,         /* unpack(+mix) to float2, then the per-stage kernels                                           */
+};
+
+static bool route_has_record(Route r) { return r <= Route::I8xD10; }
+
+struct RouteChoice {
+    Route route;
+    int nfirst;                   /* stages the first launch covers: 1, 2 or 3 */
+};
+
+/* The route of a batch of nsamples from the present stream position.  mixed_hist: mixed_history() said so (queries pass
+ * false: what the batch takes when its history window holds one word).                                           */
+static RouteChoice choose_route(const pddc_pipeline *p, size_t nsamples, bool mixed_hist)
+{
+    if (mixed_hist)
+        return { Route::MixedHist, 1 };
+    if (stages012_fusable(p, nsamples))
+        return { Route::Fused3, 3 };
+    const bool i8 = stage0_i8_kind(p, nsamples) == 2;
+    if (i8 && i8x_pair_ok(p, nsamples))
+        return { Route::I8xPair, 2 };
+    if (stages01_fusable(p, nsamples))
+        return { Route::Fir8Pair, 2 };
+    if (stage0_fused(p))
+        return { i8 ? Route::I8x : Route::Fir8, 1 };
+    if (stage0_packed_generic(p)) {
+        size_t off, n1;
+        unsigned long long m0;
+        stage_outputs(p->st[0].consumed, nsamples, p->st[0].decim, 1, &off, &m0, &n1);
+        return { n1 > 0 && i8x_d10_ok(p) ? Route::I8xD10 : Route::PackedGeneric, 1 };
+    }
+    return { Route::Unpack, 1 };
+}
+
+int pddc_pipeline_stage0_on_i8(const pddc_pipeline *p, size_t nsamples)
+{
+    if (!p)
+        return 0;
+    const Route r = choose_route(p, nsamples, false).route;
+    return r == Route::I8x || r == Route::I8xPair || r == Route::I8xD10 ? 2 : 0;
+}
+
+/* (every route but the unpack one reads the packed batch; which one that is depends on the plan, not on the batch) */
+int pddc_pipeline_stage0_reads_packed(const pddc_pipeline *p)
+{
+    return p && choose_route(p, 0, false).route != Route::Unpack ? 1 : 0;
+}
+
+/* 2: k_fir_i8x's fused pair, 1: k_fir8's (alone, or inside the fused cascade) */
+int pddc_pipeline_uses_fused_pair(const pddc_pipeline *p, size_t nsamples)
+{
+    if (!p)
+        return 0;
+    const RouteChoice rc = choose_route(p, nsamples, false);
+    return rc.route == Route::I8xPair ? 2 : rc.nfirst >= 2 ? 1 : 0;
+}
+
+int pddc_pipeline_uses_fused_cascade(const pddc_pipeline *p, size_t nsamples)
+{
+    return p && choose_route(p, nsamples, false).route == Route::Fused3 ? 1 : 0;
 }
 
 /* k_fir_i8x's operands for the word in force (rebuilt and uploaded in stream order when word, taps, form or stream changed)
@@ -1461,11 +1519,6 @@ static int i8x_d10_prepare(pddc_pipeline *p, int delay, hipStream_t s, FirI8xArg
     return PDDC_OK;
 }
 
-extern "C" int pddc_pipeline_uses_fused_pair(const pddc_pipeline *p, size_t nsamples)
-{
-    return !p ? 0 : stages01_i8x(p, nsamples) ? 2 : stages01_fusable(p, nsamples) ? 1 : 0;
-}
-
 /* The whole cascade in one kernel: behind the fused pair, stage 2 -- a plain decimator at 1/64 of the input rate --
  * runs on the pair's outputs while they are still in LDS (k_fir8<.., FUSE3>): the 1/8 B per input sample that the
  * pair wrote and the tail kernel read back, the tail's launch and the two launch gaps all go (x320: one streaming
@@ -1504,20 +1557,6 @@ static int setup_stage3(pddc_pipeline *p)
     p->s3 = q;
     p->s3_ok = true;
     return PDDC_OK;
-}
-
-/* Opt-in (PDDC_FUSE3=1): measured on MI355X the one-kernel cascade is SLOWER than the fused pair followed by the tail
- * kernel -- x320 at 2^28 samples 0.323 against 0.287 + 0.027 ms, no gain at 2^20..2^22 either (profiles/r03/
- * c_fused_cascade_*.txt) -- because k_fir8 is bound by each block's own dependency chain, and work added to the same
- * waves lengthens it one for one; the tail costs less on OTHER waves (pddc_pipeline_set_overlap).                  */
-static bool stages012_fusable(const pddc_pipeline *p, size_t nsamples)
-{
-    return p->s3_ok && p->nstages >= 3 && p->opt.fuse3 == 1 && stages01_fusable(p, nsamples);
-}
-
-extern "C" int pddc_pipeline_uses_fused_cascade(const pddc_pipeline *p, size_t nsamples)
-{
-    return p && stages012_fusable(p, nsamples) ? 1 : 0;
 }
 
 /* Waits for everything queued on `stream` and reports a kernel-side failure (the fused cascade's bounded wait for a
@@ -1639,9 +1678,8 @@ int pddc_pipeline_place_buffers(pddc_pipeline *p, const void *d_packed, size_t m
         if (s.buf_in_ws)
             return fail(PDDC_ESTATE, "the inter-stage buffers come from the caller's workspace (pddc_pipeline_set_workspace)");
         const size_t cap = ws_stage_samples(p, i, max_nsamples);
-        /* with the fused pair stage 1's buffer is never written: the pair writes stage 2's, reading the packed batch */
-        const bool skipped = i == 1 && p->nstages >= 2 && stages01_fusable(p, max_nsamples - max_nsamples % (size_t)fir8_tile_inputs(p->R));
-        if (skipped)
+        /* with a fused pair stage 1's buffer is never written: the pair writes stage 2's, reading the packed batch */
+        if (i == 1 && choose_route(p, max_nsamples - max_nsamples % (size_t)fir8_tile_inputs(p->R), false).nfirst >= 2)
             continue;
         if (cap * 8 >= ((size_t)32 << 20) && src_bytes >= ((size_t)64 << 20)) {
             void *ptr = nullptr;
@@ -1667,7 +1705,7 @@ int pddc_pipeline_place_buffers(pddc_pipeline *p, const void *d_packed, size_t m
 /* Overlap mode.  A cascade behind the fused pair is kernels in a row, each waiting for the one before: the pair (0.29 ms
  * at 2^28 samples), a launch gap, the tail (23 us at a fifth of the HBM rate: it has 1/64 of the samples and a tenth
  * of the arithmetic), another gap -- 11 % of the x320 step (profiles/r02/k_trace_c320.txt).  What was tried first
- * (profiles/r03/): the tail INSIDE the pair's kernel (stages012_fusable above: slower, that kernel is bound by every
+ * (profiles/r03/): the tail INSIDE the pair's kernel (Route::Fused3 above: slower, that kernel is bound by every
  * block's own dependency chain); the tail on a side stream behind an event (every cross-stream event put 18 us between
  * two pairs on the main stream, and the two grids, ready at the same instant, were dealt out interleaved: the pair took
  * 0.338 instead of 0.287 ms).  What works needs neither stream nor event: the tail of batch k becomes part of the
@@ -1749,8 +1787,400 @@ static void fill_stage3_args(const pddc_pipeline *p, Fir8Args &a, float *dst, si
     a.s3.off = (int)off;
 }
 
-int pddc_pipeline_process(pddc_pipeline *p, const void *d_packed, size_t nsamples, void *d_out,
-                          size_t out_capacity, size_t *n_out_ret, void *stream_v)
+/* destination of stage i: the next stage's input buffer (grown when the batch is larger than any before), or the caller's */
+static int stage_dst(pddc_pipeline *p, int i, const BatchPlan &b, void *d_out, hipStream_t s, float **dst)
+{
+    if (i + 1 < p->nstages) {
+        Stage &nx = p->st[i + 1];
+        const size_t need = b.n_in[i + 1] + 8;
+        /* growing the buffer frees it: a tail that overlap mode still holds back may read it (its input half or its
+         * output side) -- it goes out first */
+        if (p->carry_pending && !nx.buf_in_ws && !(nx.d_buf && nx.buf_cap >= need)) {
+            int rf = pddc_pipeline_fence(p, s);
+            if (rf)
+                return rf;
+        }
+        int r = ensure_buf(nx, need);
+        if (r)
+            return r;
+        *dst = nx.d_buf;
+    } else if (p->flags & PDDC_F_OUT_PACKED24) {
+        const size_t n_final = b.n_in[p->nstages];
+        if (p->d_fout_cap < n_final + 8) {
+            HIP_TRY(hipDeviceSynchronize());
+            if (p->d_fout)
+                HIP_TRY(hipFree(p->d_fout));
+            p->d_fout = nullptr;
+            p->d_fout_cap = 0;
+            HIP_TRY(hipMalloc(&p->d_fout, (n_final + n_final / 4 + 64) * 8));
+            p->d_fout_cap = n_final + n_final / 4 + 64;
+        }
+        *dst = p->d_fout;
+    } else {
+        *dst = static_cast<float *>(d_out);
+    }
+    return PDDC_OK;
+}
+
+/* Overlap mode: the plan's LAST stage `ti` (a plain decimator behind one first-stage kernel: the fused pair, or the
+ * unfused fused-/8 stage 0) is held back and rides along with the next batch's first-stage launch; gang mode launches it
+ * right behind its members' first-stage launch.  Prepares its record: shape, the half of the double-buffered input the
+ * first stage writes this time (use_alt: *dst_first becomes it), history, output.  1: no shape, nothing touched.     */
+static int carry_setup(pddc_pipeline *p, int ti, const BatchPlan &b, void *d_out, hipStream_t s, float **dst_first,
+                       GenTail *mine, bool use_alt, size_t lds_cap)
+{
+    Stage &sl = p->st[ti];
+    mine->H = sl.hist;
+    mine->D = sl.decim;
+    mine->ntaps = sl.ntaps;
+    mine->n_out = (long long)b.n_in[ti + 1];
+    if (!gen_tail_shape(mine, lds_cap, sl.d_taps_firp != nullptr))
+        return 1;                                    /* does not fit: in line */
+    if (use_alt) {
+        if (sl.buf_in_ws) {
+            if (sl.d_buf_alt == nullptr || sl.buf_alt_cap < b.n_in[ti] + 8)
+                return fail(PDDC_ECAPACITY, "overlap mode: the workspace was set before pddc_pipeline_set_overlap, "
+                                            "or for smaller batches (it needs two halves for the last stage)");
+        } else if (sl.buf_alt_cap < b.n_in[ti] + 8) {
+            if (p->carry_pending) {                 /* (the held-back tail may read the half that is about to be freed) */
+                int rf = pddc_pipeline_fence(p, s);
+                if (rf)
+                    return rf;
+            }
+            HIP_TRY(hipDeviceSynchronize());
+            if (sl.d_buf_alt)
+                HIP_TRY(hipFree(sl.d_buf_alt));
+            sl.d_buf_alt = nullptr;
+            sl.buf_alt_cap = 0;
+            HIP_TRY(hipMalloc(&sl.d_buf_alt, sizeof(float) * 2 * sl.buf_cap));
+            sl.buf_alt_cap = sl.buf_cap;
+        }
+        *dst_first = sl.d_buf_alt;
+    }
+    float *dst_last;
+    int r = stage_dst(p, ti, b, d_out, s, &dst_last);
+    if (r)
+        return r;
+    mine->in = *dst_first;
+    mine->hist = static_cast<const float *>(sl.d_hist[sl.cur]);
+    mine->hist_out = static_cast<float *>(sl.d_hist[sl.cur ^ 1]);
+    mine->out = dst_last;
+    mine->taps = sl.d_taps_dup;
+    mine->taps2 = sl.d_taps_firp;
+    mine->first = (long long)b.off[ti];
+    mine->n_batch = (long long)b.n_in[ti];
+    return PDDC_OK;
+}
+
+/* the test hook of pddc_pipeline_inject_failure: the batch fails when it reaches stage i, before anything of it is queued */
+static int injected_failure(pddc_pipeline *p, int i)
+{
+    if (p->fail_at_stage < 0 || p->fail_at_stage > i)
+        return PDDC_OK;
+    p->fail_at_stage = -1;
+    return fail(PDDC_EHIP, "injected failure at stage %d (pddc_pipeline_inject_failure)", i);
+}
+
+/* may overlap mode hold stage ti back (carry_setup)? */
+static bool carry_wanted(const pddc_pipeline *p, int ti, const BatchPlan &b)
+{
+    return p->overlap && p->nstages == ti + 1 && p->R == 4 && stage0_fused(p) && p->st[ti].interp == 1 &&
+           !(p->flags & (PDDC_F_OUT_PACKED24 | PDDC_F_NO_FAST)) && b.n_in[ti + 1] > 0;
+}
+
+/* Which tuning words does stage 0's history window [n0 - H, n0) hold?  Drops the segments that ended before it.  One word,
+ * or the old word all through with the new one starting exactly now: the packed-history kernels handle it (freg_hist).
+ * Anything else (true): the mixed-history route.                                                                      */
+static bool mixed_history(pddc_pipeline *p)
+{
+    if (!(p->flags & PDDC_F_MIX) || !(stage0_fused(p) || stage0_packed_generic(p)))
+        return false;
+    const long long w0 = (long long)p->n0 - (long long)p->st[0].hist;
+    while (p->segs.size() >= 2 && p->segs[1].n_begin <= w0)
+        p->segs.erase(p->segs.begin());
+    const size_t k = p->segs.size();
+    const bool ok = k == 1 || (k == 2 && p->segs[1].n_begin == (long long)p->n0);
+    const uint32_t hist_word = p->segs[0].freg;
+    if (ok && hist_word != p->freg_applied) {      /* cannot happen while set_freg keeps both in step */
+        p->freg_applied = hist_word;
+        compute_lo_steps(p);
+    }
+    return !ok;
+}
+
+/* What a route with a record (route_has_record) launches first: the kernel's arguments, and the plain decimator behind it
+ * that gang or overlap mode takes along.  process_batch() builds one per batch and launches it, or hands it to the gang,
+ * which groups its members' records into *_many launches; pddc_pipeline_time_stage0 builds the same with the histories
+ * left alone and launches it again and again.                                                                       */
+struct FirstLaunch {
+    Route route = Route::Fir8;
+    bool mix = false;
+    int ntb = 0, R = 4, NT = 256;                   /* k_fir8's shape                                                   */
+    int hist = 0, blocks = 0, chunk = 0, layout = -1;   /* k_fir_i8x's history and options                          */
+    Fir8Args a;                                     /* Fir8, Fir8Pair, Fused3                                           */
+    FirI8xArgs ax;                                  /* I8x, I8xPair, I8xD10                                             */
+    GenTail tail;                                   /* the stage behind (nblocks == 0: none)                            */
+    bool hold_tail = false;                         /* overlap mode: `tail` waits for the next batch's launch           */
+    int stages = 0;                                 /* stages of the batch this takes care of: the route's and the tail's */
+};
+
+/* The record of `route` for this batch, writing to dst.  advance = false: no history is written (hist_out, hist2_out and
+ * the fused cascade's third-stage history stay NULL).  k_fir_i8x's operands are brought up to date on `s`.            */
+static int build_first(pddc_pipeline *p, Route route, const BatchPlan &b, const void *d_packed, float *dst, bool advance,
+                       hipStream_t s, FirstLaunch &r)
+{
+    const Stage &s0 = p->st[0], &s1 = p->st[1];
+    const size_t nsamples = b.n_in[0];
+    const bool pair = route == Route::I8xPair || route == Route::Fir8Pair || route == Route::Fused3;
+    void *const hist_out = advance && nsamples >= (size_t)s0.hist ? s0.d_hist[s0.cur ^ 1] : nullptr;
+    void *const hist2_out = advance ? s1.d_hist[s1.cur ^ 1] : nullptr;
+    r.route = route;
+    r.mix = (p->flags & PDDC_F_MIX) != 0;
+    r.ntb = s0.ntb;
+    r.R = p->R;
+    r.NT = p->NT;
+    r.hist = s0.hist;
+    r.blocks = p->opt.i8x_blocks;
+    r.chunk = p->opt.i8x_chunk;
+    r.layout = p->opt.i8x_layout;
+    if (route == Route::I8x || route == Route::I8xPair || route == Route::I8xD10) {
+        FirI8xArgs &q = r.ax;
+        int rc;
+        if (route == Route::I8xD10) {
+            /* the decimation phase of this batch (its first output's newest sample, 0 .. 9) goes into the taps as a delay,
+             * so that the windows end on a multiple of 8 samples */
+            const int first = (int)b.off[0], delay = (8 - (first & 7)) & 7;
+            if ((rc = i8x_d10_prepare(p, delay, s, q)))
+                return rc;
+            q.n_out = (long long)b.n_in[1];
+            q.in_off = first + delay;
+            q.hist_len = s0.hist;
+        } else if ((rc = i8x_prepare(p, r.mix, pair, s, q))) {
+            return rc;
+        }
+        q.in = d_packed;
+        q.hist = s0.d_hist[s0.cur];
+        q.hist_out = hist_out;
+        q.out = dst;
+        q.n_in = (long long)nsamples;
+        if (route == Route::I8xD10)
+            q.n0 = p->n0 + (unsigned long long)q.in_off;
+        if (pair) {
+            q.hist2 = s1.d_hist[s1.cur];
+            q.hist2_out = hist2_out;
+        }
+        return PDDC_OK;
+    }
+    Fir8Args &a = r.a;
+    a.in = d_packed;
+    a.hist = s0.d_hist[s0.cur];
+    a.hist_out = hist_out;
+    a.out = route == Route::Fused3 ? nullptr : dst;
+    a.taps_blk = s0.d_taps_blk;
+    if (pair) {
+        a.taps2_blk = s1.d_taps_blk;
+        a.hist2 = s1.d_hist[s1.cur];
+        a.hist2_out = hist2_out;
+    }
+    a.n_in = (long long)nsamples;
+    fill_fir8_args(p, a);
+    if (route == Route::Fused3)
+        fill_stage3_args(p, a, dst, b.off[2], b.n_in[3], advance);
+    return PDDC_OK;
+}
+
+static hipError_t launch_first(const FirstLaunch &r, hipStream_t s)
+{
+    switch (r.route) {
+    case Route::I8xPair:
+    case Route::I8x:
+        return launch_fir_i8x(r.ax, r.hist, r.mix, r.route == Route::I8xPair, s, r.blocks, r.chunk, r.layout);
+    case Route::I8xD10:
+        return launch_fir_i8x_d10(r.ax, s, r.blocks, r.chunk, r.layout);
+    case Route::Fused3:
+        return launch_fir8_fused3(r.ntb, r.R, r.mix, r.a, s);
+    case Route::Fir8Pair:
+        return launch_fir8_fused2(r.ntb, r.R, r.mix, r.a, s);
+    case Route::Fir8:
+        return launch_fir8(r.ntb, r.R, IN_PACKED24, r.mix, r.a, s, r.NT);
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
+/* The batch's first launch: its destination, the stage behind it where gang mode (`gang`) or overlap mode takes that
+ * along, the record.  A tail that overlap mode holds back goes out first (pddc_pipeline_fence) unless this launch
+ * carries it.  1: gang mode, and the stage behind has no shape -- nothing queued, no stream state moved.            */
+static int prepare_first(pddc_pipeline *p, RouteChoice rt, const BatchPlan &b, const void *d_packed, void *d_out, bool gang,
+                         hipStream_t s, FirstLaunch &r)
+{
+    const int ti = rt.nfirst;                       /* the stage behind the launch */
+    /* overlap mode: the one stage behind k_fir8 (alone or as its pair) rides along with the NEXT batch's launch (k_fir_i8x
+     * carries no tail: in line).  Where that may happen, the fence waits until it is known whether it does.          */
+    const bool may_carry = rt.route == Route::Fir8Pair ||
+                           ((rt.route == Route::Fir8 || rt.route == Route::I8x) && carry_wanted(p, ti, b));
+    bool ov = !gang && may_carry && (rt.route == Route::Fir8Pair || (rt.route == Route::Fir8 && p->NT == 256)) &&
+              carry_wanted(p, ti, b);
+    int rc;
+    if (!may_carry && (rc = pddc_pipeline_fence(p, s)))
+        return rc;
+    if (ti == 1 && (rc = injected_failure(p, 0)))   /* stage 0 alone: before its launch (a pair's: at the stage behind) */
+        return rc;
+    float *dst;
+    if ((rc = stage_dst(p, ti - 1, b, d_out, s, &dst)))
+        return rc;
+    if (ov) {
+        rc = carry_setup(p, ti, b, d_out, s, &dst, &r.tail, p->ov_parity == 1, kCarryLdsCap);
+        if (rc < 0)
+            return rc;
+        ov = rc == PDDC_OK;
+    }
+    const bool gtail = gang && p->nstages == ti + 1;
+    if (gtail && (rc = carry_setup(p, ti, b, d_out, s, &dst, &r.tail, false, 160u * 1024u)))
+        return rc;                                      /* (1: no shape for this tail -- nothing touched yet) */
+    if (!ov && (rc = pddc_pipeline_fence(p, s)))        /* in line: what is held back goes first */
+        return rc;
+    if ((rc = build_first(p, rt.route, b, d_packed, dst, true, s, r)))
+        return rc;
+    if (ov && p->carry_pending)
+        r.a.tail = p->carry_tail;
+    r.hold_tail = ov;
+    r.stages = ti + (ov || gtail ? 1 : 0);
+    return PDDC_OK;
+}
+
+/* Gang mode takes a batch whose plan is the first-stage kernel (k_fir8 or k_fir_i8x, alone or as its fused pair) and at
+ * most one plain decimator behind it, from a pipeline that holds nothing back and measures nothing.                  */
+static bool gang_ok(const pddc_pipeline *p, RouteChoice rt, const BatchPlan &b)
+{
+    const bool x = rt.route == Route::I8x || rt.route == Route::I8xPair;
+    if (!x && rt.route != Route::Fir8 && rt.route != Route::Fir8Pair)
+        return false;
+    const int last = p->nstages - 1;
+    const bool tail_ok = p->nstages == rt.nfirst ||
+                         (p->nstages == rt.nfirst + 1 && p->st[last].interp == 1 && b.n_in[p->nstages] > 0);
+    return tail_ok && p->NT == 256 && !p->overlap && !p->carry_pending && !p->time_stage0 && p->fail_at_stage < 0 &&
+           !(p->flags & (PDDC_F_OUT_PACKED24 | PDDC_F_NO_FAST)) && b.n_in[1] > 0 && b.n_in[0] >= (size_t)p->st[0].hist &&
+           (x || fir8_many_supported(rt.nfirst, p->st[0].ntb, p->R));
+}
+
+/* Stage i of the batch in line: stage 0 where the route has no record (mixed history, packed generic, unpack), and every
+ * stage behind the first launch; then the history update where the kernel did not write the new history itself.     */
+static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, const void *d_packed, void *d_out, hipStream_t s)
+{
+    Stage &st = p->st[i];
+    int rc;
+    if ((rc = injected_failure(p, i)))
+        return rc;
+    const bool mix = (p->flags & PDDC_F_MIX) != 0;
+    const size_t nsamples = b.n_in[0];
+    const size_t *n_in = b.n_in, *off = b.off;
+    float *dst;
+    if ((rc = stage_dst(p, i, b, d_out, s, &dst)))
+        return rc;
+    void *h_in = st.d_hist[st.cur], *h_out = st.d_hist[st.cur ^ 1];
+    const void *x = d_packed;                       /* this stage's input batch */
+    bool hist_done = false;
+    if (i == 0 && route == Route::MixedHist) {
+        /* rare: batches shorter than the history with retunes between them.  The packed history
+         * is unpacked and mixed stretch by stretch, each with the word and offset that applied to
+         * it, the batch likewise with the current word, and the generic decimator runs on floats;
+         * the packed history for the next call is carried as usual.                            */
+        const int H = st.hist;
+        if ((rc = ensure_buf(st, nsamples + 8)))
+            return rc;
+        if (!p->d_hist_f32)
+            HIP_TRY(hipMalloc(&p->d_hist_f32, (size_t)PDDC_MAX_TAPS * 8 + 256));
+        const long long w0 = (long long)p->n0 - H;
+        for (size_t k = 0; k < p->segs.size(); ++k) {
+            const long long a0 = std::max(w0, k == 0 ? w0 : p->segs[k].n_begin);
+            const long long a1 = std::min((long long)p->n0, k + 1 < p->segs.size() ? p->segs[k + 1].n_begin
+                                                                                   : (long long)p->n0);
+            if (a1 <= a0)
+                continue;
+            float lc[8], ls[8];
+            lo_steps(p->segs[k].freg, lc, ls);
+            HIP_TRY(launch_unpack24(static_cast<const uint8_t *>(h_in) + (a0 - w0) * PDDC_PACKED_BYTES, a1 - a0,
+                                    p->d_hist_f32 + 2 * (a0 - w0), false, true, (unsigned long long)a0,
+                                    p->segs[k].freg, p->segs[k].off, lc, ls, s));
+        }
+        HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, true, p->n0, p->freg, p->phase_off,
+                                p->lo_c, p->lo_s, s));
+        if (n_in[1] > 0)
+            HIP_TRY(launch_fir_generic(st.d_buf, p->d_hist_f32, H, (long long)off[0], (long long)n_in[1], st.decim,
+                                       st.d_taps_dup, st.ntaps, dst, nullptr, (long long)nsamples, s));
+        /* hist_done stays false: the packed history moves on below (x == d_packed) */
+    } else if (i == 0 && route == Route::PackedGeneric) {
+        if (n_in[1] > 0) {
+            if (st.d_taps_firp)           /* register-blocked kernel for /4 /5 /8 /10 */
+                HIP_TRY(launch_firp_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1], st.decim,
+                                           st.d_taps_firp, st.ntaps, dst, h_out, (long long)nsamples, mix, p->n0,
+                                           p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s, p->lo_c_applied,
+                                           p->lo_s_applied, s));
+            else
+                HIP_TRY(launch_fir_generic_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1],
+                                                  st.decim, st.d_taps_dup, st.ntaps, dst, h_out, (long long)nsamples,
+                                                  mix, p->n0, p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s,
+                                                  p->lo_c_applied, p->lo_s_applied, s));
+            hist_done = true;             /* block 0 of the kernel wrote the new (packed) history */
+        }
+    } else {
+        if (i == 0) {
+            /* generic first stage: unpack(+mix) to float2, then the generic FIR */
+            if ((rc = ensure_buf(st, nsamples + 8)))
+                return rc;
+            HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, mix, p->n0, p->freg,
+                                    p->phase_off, p->lo_c, p->lo_s, s));
+        }
+        x = st.d_buf;
+        const bool fast = i > 0 && st.ntb != 0 && !(p->flags & PDDC_F_NO_FAST) &&
+                          fir8_supported(st.ntb, p->R) && (n_in[i] % 8 == 0) && off[i] == 0 &&
+                          (st.consumed % 8 == 0) && n_in[i] > 0;
+        if (fast) {
+            Fir8Args a;
+            a.in = x;
+            a.hist = h_in;
+            a.hist_out = n_in[i] >= (size_t)st.hist ? h_out : nullptr;
+            a.out = dst;
+            a.taps_blk = st.d_taps_blk;
+            a.n_in = (long long)n_in[i];
+            fill_fir8_args(p, a);
+            HIP_TRY(launch_fir8(st.ntb, p->R, IN_F32C, false, a, s));
+            hist_done = a.hist_out != nullptr;
+        } else if (st.interp > 1) {
+            if (n_in[i + 1] > 0 && st.d_taps_poly && !(p->flags & PDDC_F_NO_FAST)) {
+                HIP_TRY(launch_resample_lds(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
+                                            st.consumed, b.m0[i], (long long)n_in[i + 1], st.interp, st.decim,
+                                            st.d_taps_poly, st.poly_k, st.poly_kp, dst, static_cast<float *>(h_out),
+                                            (long long)n_in[i], s));
+                hist_done = true;
+            } else if (n_in[i + 1] > 0) {
+                HIP_TRY(launch_resample(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
+                                        st.consumed, b.m0[i], (long long)n_in[i + 1], st.interp, st.decim,
+                                        st.d_taps, st.ntaps, dst, s));
+            }
+        } else if (n_in[i + 1] > 0) {
+            if (st.d_taps_firp)
+                HIP_TRY(launch_firp(IN_F32C, false, x, h_in, st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
+                                    st.d_taps_firp, st.ntaps, dst, h_out, (long long)n_in[i], nullptr, s));
+            else
+                HIP_TRY(launch_fir_generic(static_cast<const float *>(x), static_cast<const float *>(h_in),
+                                           st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
+                                           st.d_taps_dup, st.ntaps, dst, static_cast<float *>(h_out),
+                                           (long long)n_in[i], s));
+            hist_done = true;             /* block 0 of the kernel wrote the new history */
+        }
+    }
+    if (n_in[i] > 0 && !hist_done)
+        HIP_TRY(launch_hist_update(h_out, h_in, st.hist, x, (long long)n_in[i], st.hist_elem, s));
+    return PDDC_OK;
+}
+
+/* pddc_pipeline_process, and for the gang (`gang` != NULL): the first launch is recorded there, not launched.  A batch the
+ * gang cannot take (other plan shapes, the rare routes, gang_ok) answers 1 before anything has been queued or any stream
+ * state has moved, and the gang runs it as a chain of its own.                                                      */
+static int process_batch(pddc_pipeline *p, const void *d_packed, size_t nsamples, void *d_out, size_t out_capacity,
+                         size_t *n_out_ret, hipStream_t s, FirstLaunch *gang)
 {
     if (!p)
         return fail(PDDC_EINVAL, "null pipeline");
@@ -1764,505 +2194,60 @@ int pddc_pipeline_process(pddc_pipeline *p, const void *d_packed, size_t nsample
         return fail(PDDC_EINVAL, "nsamples (%zu) must be a multiple of %d", nsamples, PDDC_INPUT_GRANULE);
     if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
         return fail(PDDC_EINVAL, "device pointers must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream_v;
     HIP_TRY(hipSetDevice(p->device));
 
-    /* plan: outputs per stage */
-    size_t n_in[PDDC_MAX_STAGES + 1], off[PDDC_MAX_STAGES];
-    unsigned long long m0[PDDC_MAX_STAGES];
-    n_in[0] = nsamples;
-    for (int i = 0; i < p->nstages; ++i)
-        stage_outputs(p->st[i].consumed, n_in[i], p->st[i].decim, p->st[i].interp, &off[i], &m0[i], &n_in[i + 1]);
-    const size_t n_final = n_in[p->nstages];
+    BatchPlan b;
+    plan_batch(p, nsamples, b);
+    const size_t n_final = b.n_in[p->nstages];
     if (n_final > out_capacity)
         return fail(PDDC_ECAPACITY, "output capacity %zu < %zu", out_capacity, n_final);
 
-    const bool mix = (p->flags & PDDC_F_MIX) != 0;
-    int rc;
-    /* destination of stage i: the next stage's input buffer, or the caller's */
-    /* (reads_packed: the kernel writing it streams the packed batch -- stage 0, or the fused pair for stage 1) */
-    auto stage_dst = [&](int i, float **dst, bool reads_packed) -> int {
-        if (i + 1 < p->nstages) {
-            (void)reads_packed;
-            /* growing the buffer frees it: a tail that overlap mode still holds back may read it (its input half or its
-             * output side) -- it goes out first */
-            if (p->carry_pending && !p->st[i + 1].buf_in_ws && !(p->st[i + 1].d_buf && p->st[i + 1].buf_cap >= n_in[i + 1] + 8)) {
-                int rf = pddc_pipeline_fence(p, s);
-                if (rf)
-                    return rf;
-            }
-            int r = ensure_buf(p->st[i + 1], n_in[i + 1] + 8);
-            if (r)
-                return r;
-            *dst = p->st[i + 1].d_buf;
-        } else if (p->flags & PDDC_F_OUT_PACKED24) {
-            if (p->d_fout_cap < n_final + 8) {
-                HIP_TRY(hipDeviceSynchronize());
-                if (p->d_fout)
-                    HIP_TRY(hipFree(p->d_fout));
-                p->d_fout = nullptr;
-                p->d_fout_cap = 0;
-                HIP_TRY(hipMalloc(&p->d_fout, (n_final + n_final / 4 + 64) * 8));
-                p->d_fout_cap = n_final + n_final / 4 + 64;
-            }
-            *dst = p->d_fout;
-        } else {
-            *dst = static_cast<float *>(d_out);
-        }
-        return PDDC_OK;
-    };
-
-    /* Overlap mode: the plan's LAST stage `ti` (a plain decimator behind one first-stage kernel: the fused pair, or the
-     * unfused fused-/8 stage 0) is held back and rides along with the next batch's first-stage launch.  Prepares its
-     * record: shape, the half of the double-buffered input the first stage writes this time, history, output.   */
-    auto carry_setup = [&](int ti, float **dst_first, GenTail *mine, bool use_alt, size_t lds_cap) -> int {
-        Stage &sl = p->st[ti];
-        mine->H = sl.hist;
-        mine->D = sl.decim;
-        mine->ntaps = sl.ntaps;
-        mine->n_out = (long long)n_in[ti + 1];
-        if (!gen_tail_shape(mine, lds_cap, sl.d_taps_firp != nullptr))
-            return 1;                                    /* does not fit: in line */
-        if (use_alt) {
-            if (sl.buf_in_ws) {
-                if (sl.d_buf_alt == nullptr || sl.buf_alt_cap < n_in[ti] + 8)
-                    return fail(PDDC_ECAPACITY, "overlap mode: the workspace was set before pddc_pipeline_set_overlap, "
-                                                "or for smaller batches (it needs two halves for the last stage)");
-            } else if (sl.buf_alt_cap < n_in[ti] + 8) {
-                if (p->carry_pending) {                 /* (the held-back tail may read the half that is about to be freed) */
-                    int rf = pddc_pipeline_fence(p, s);
-                    if (rf)
-                        return rf;
-                }
-                HIP_TRY(hipDeviceSynchronize());
-                if (sl.d_buf_alt)
-                    HIP_TRY(hipFree(sl.d_buf_alt));
-                sl.d_buf_alt = nullptr;
-                sl.buf_alt_cap = 0;
-                HIP_TRY(hipMalloc(&sl.d_buf_alt, sizeof(float) * 2 * sl.buf_cap));
-                sl.buf_alt_cap = sl.buf_cap;
-            }
-            *dst_first = sl.d_buf_alt;
-        }
-        float *dst_last;
-        int r = stage_dst(ti, &dst_last, false);
-        if (r)
-            return r;
-        mine->in = *dst_first;
-        mine->hist = static_cast<const float *>(sl.d_hist[sl.cur]);
-        mine->hist_out = static_cast<float *>(sl.d_hist[sl.cur ^ 1]);
-        mine->out = dst_last;
-        mine->taps = sl.d_taps_dup;
-        mine->taps2 = sl.d_taps_firp;
-        mine->first = (long long)off[ti];
-        mine->n_batch = (long long)n_in[ti];
-        return PDDC_OK;
-    };
-    auto carry_wanted = [&](int ti) {
-        return p->overlap && p->nstages == ti + 1 && p->R == 4 && stage0_fused(p) && p->st[ti].interp == 1 &&
-               !(p->flags & (PDDC_F_OUT_PACKED24 | PDDC_F_NO_FAST)) && n_in[ti + 1] > 0;
-    };
+    const RouteChoice rt = choose_route(p, nsamples, mixed_history(p));
+    if (gang && !gang_ok(p, rt, b))
+        return 1;
 
     /* Stream state (which history buffer is current, inputs consumed per stage, the sample
      * counter) is committed only after every launch of the batch has been accepted: a failure
      * half way leaves the pipeline exactly where it was, and the batch can be retried.       */
-    bool flip[PDDC_MAX_STAGES] = { false, false, false, false };
-    int first = 0;
-    int skip_from = PDDC_MAX_STAGES;        /* overlap mode: stages from here on are held back, not launched here   */
-    /* which tuning words does stage 0's history window [n0 - H, n0) hold?  Drop the segments that
-     * ended before it.  One word, or the old word all through with the new one starting exactly now:
-     * the packed-history kernels handle it (freg_hist).  Anything else: the mixed-history route.  */
-    bool mixed_hist = false;
-    if (mix && (stage0_fused(p) || stage0_packed_generic(p))) {
-        const long long w0 = (long long)p->n0 - (long long)p->st[0].hist;
-        while (p->segs.size() >= 2 && p->segs[1].n_begin <= w0)
-            p->segs.erase(p->segs.begin());
-        const size_t k = p->segs.size();
-        const bool ok = k == 1 || (k == 2 && p->segs[1].n_begin == (long long)p->n0);
-        mixed_hist = !ok;
-        const uint32_t hist_word = p->segs[0].freg;
-        if (ok && hist_word != p->freg_applied) {      /* cannot happen while set_freg keeps both in step */
-            p->freg_applied = hist_word;
-            compute_lo_steps(p);
-        }
-    }
-    /* Gang mode: this call only RECORDS the first-stage launch and the one plain decimator that may follow it; the gang
-     * launches them for all its members together.  Anything else (other plan shapes, the rare routes, an empty tail)
-     * answers 1 before anything has been touched, and the gang runs this member's batch as a chain of its own.   */
-    GangRec *const g = p->gang_rec;
-    if (g) {
-        g->kind = 0;
-        g->tail = GenTail{};
-        const int i8k = mixed_hist ? 0 : stage0_i8_kind(p, nsamples);
-        const int nfirst = (i8k == 2 ? stages01_i8x(p, nsamples) : stages01_fusable(p, nsamples)) ? 2 : 1;
-        const int last = p->nstages - 1;
-        const bool tail_ok = p->nstages == nfirst ||
-                             (p->nstages == nfirst + 1 && p->st[last].interp == 1 && n_in[p->nstages] > 0);
-        if (mixed_hist || !stage0_fused(p) || p->NT != 256 || p->overlap || p->carry_pending ||
-            p->time_stage0 || p->fail_at_stage >= 0 || (p->flags & (PDDC_F_OUT_PACKED24 | PDDC_F_NO_FAST)) ||
-            stages012_fusable(p, nsamples) || !tail_ok || n_in[1] == 0 || nsamples < (size_t)p->st[0].hist ||
-            (i8k != 2 && !fir8_many_supported(nfirst, p->st[0].ntb, p->R)))
-            return 1;
-    }
-    const int i8kind = mixed_hist ? 0 : stage0_i8_kind(p, nsamples);
-    if (i8kind == 2 && stages01_i8x(p, nsamples) && !stages012_fusable(p, nsamples)) {
-        /* stages 0 and 1 as k_fir_i8x's fused pair: stage 0 on the int8 matrix cores with the NCO in its taps, stage 1 on
-         * its values while they are in LDS.  The stage behind the pair runs in line (no carried tail on this kernel). */
-        Stage &s0 = p->st[0], &s1 = p->st[1];
-        float *dst;
-        if ((rc = pddc_pipeline_fence(p, s)))
+    int rc, next = 0;
+    FirstLaunch r;
+    if (route_has_record(rt.route)) {
+        if ((rc = prepare_first(p, rt, b, d_packed, d_out, gang != nullptr, s, r)))
             return rc;
-        if ((rc = stage_dst(1, &dst, true)))
-            return rc;
-        GenTail mine;
-        const bool gtail = g && p->nstages == 3;
-        if (gtail && (rc = carry_setup(2, &dst, &mine, false, 160u * 1024u)))
-            return rc;                                      /* (1: no shape for this tail -- nothing touched yet) */
-        FirI8xArgs q;
-        if ((rc = i8x_prepare(p, mix, true, s, q)))
-            return rc;
-        q.in = d_packed;
-        q.hist = s0.d_hist[s0.cur];
-        q.hist_out = s0.d_hist[s0.cur ^ 1];
-        q.out = dst;
-        q.n_in = (long long)nsamples;
-        q.hist2 = s1.d_hist[s1.cur];
-        q.hist2_out = s1.d_hist[s1.cur ^ 1];
-        if ((rc = stage0_event(p, s, true)))
-            return rc;
-        if (g) {
-            g->kind = 3;
-            g->mix = mix;
-            g->ax = q;
-            g->hist = s0.hist;
-            g->fuse2 = true;
-            g->chunk = p->opt.i8x_chunk;
-            g->layout = p->opt.i8x_layout;
-            g->blocks = p->opt.i8x_blocks;
-            if (gtail) {
-                g->tail = mine;
-                flip[2] = true;
-            }
+        if (gang) {
+            *gang = r;
         } else {
-            HIP_TRY(launch_fir_i8x(q, s0.hist, mix, true, s, p->opt.i8x_blocks, p->opt.i8x_chunk, p->opt.i8x_layout));
-        }
-        if ((rc = stage0_event(p, s, false)))
-            return rc;
-        flip[0] = flip[1] = true;
-        first = gtail ? 3 : 2;
-    } else if (!mixed_hist && stages012_fusable(p, nsamples)) {
-        /* stages 0, 1 and 2 in ONE kernel: neither intermediate touches HBM */
-        Stage &s0 = p->st[0], &s1 = p->st[1];
-        float *dst;
-        if ((rc = pddc_pipeline_fence(p, s)))
-            return rc;
-        if ((rc = stage_dst(2, &dst, true)))
-            return rc;
-        Fir8Args a;
-        a.in = d_packed;
-        a.hist = s0.d_hist[s0.cur];
-        a.hist_out = s0.d_hist[s0.cur ^ 1];
-        a.out = nullptr;
-        a.taps_blk = s0.d_taps_blk;
-        a.taps2_blk = s1.d_taps_blk;
-        a.hist2 = s1.d_hist[s1.cur];
-        a.hist2_out = s1.d_hist[s1.cur ^ 1];
-        a.n_in = (long long)nsamples;
-        fill_fir8_args(p, a);
-        fill_stage3_args(p, a, dst, off[2], n_in[3], true);
-        if ((rc = stage0_event(p, s, true)))
-            return rc;
-        HIP_TRY(launch_fir8_fused3(s0.ntb, p->R, mix, a, s));
-        if ((rc = stage0_event(p, s, false)))
-            return rc;
-        flip[0] = flip[1] = flip[2] = true;
-        first = 3;
-    } else if (!mixed_hist && stages01_fusable(p, nsamples)) {
-        /* stages 0 and 1 in ONE kernel: the 8 B/sample-at-1/8-rate intermediate
-         * (1 B written + 1 B read per input sample) never touches HBM */
-        Stage &s0 = p->st[0], &s1 = p->st[1];
-        float *dst;
-        if ((rc = stage_dst(1, &dst, true)))
-            return rc;
-        /* overlap mode: the one stage behind the pair is held back and rides along with the NEXT batch's pair */
-        GenTail mine;
-        bool ov = !g && carry_wanted(2);
-        if (ov) {
-            rc = carry_setup(2, &dst, &mine, p->ov_parity == 1, kCarryLdsCap);
-            if (rc < 0)
-                return rc;
-            ov = rc == PDDC_OK;
-        }
-        const bool gtail = g && p->nstages == 3;
-        if (gtail && (rc = carry_setup(2, &dst, &mine, false, 160u * 1024u)))
-            return rc;                                      /* (1: no shape for this tail -- nothing touched yet) */
-        if (!ov && (rc = pddc_pipeline_fence(p, s)))        /* in line: what is held back goes first */
-            return rc;
-        Fir8Args a;
-        a.in = d_packed;
-        a.hist = s0.d_hist[s0.cur];
-        a.hist_out = s0.d_hist[s0.cur ^ 1];
-        a.out = dst;
-        a.taps_blk = s0.d_taps_blk;
-        a.taps2_blk = s1.d_taps_blk;
-        a.hist2 = s1.d_hist[s1.cur];
-        a.hist2_out = s1.d_hist[s1.cur ^ 1];
-        a.n_in = (long long)nsamples;
-        fill_fir8_args(p, a);
-        if (ov && p->carry_pending)
-            a.tail = p->carry_tail;
-        if ((rc = stage0_event(p, s, true)))
-            return rc;
-        if (g) {
-            g->kind = 2;
-            g->ntb = s0.ntb;
-            g->R = p->R;
-            g->mix = mix;
-            g->a = a;
-            if (gtail) {
-                g->tail = mine;
-                flip[2] = true;
-            }
-        } else {
-            HIP_TRY(launch_fir8_fused2(s0.ntb, p->R, mix, a, s));
-        }
-        if (ov)
-            p->carry_pending = false;       /* (failure atomicity: only once the launch was accepted) */
-        if ((rc = stage0_event(p, s, false)))
-            return rc;
-        flip[0] = flip[1] = true;
-        first = gtail ? 3 : 2;
-        if (ov) {                           /* the previous tail went out with this launch; this batch's is held back */
-            p->carry_tail = mine;
-            p->carry_pending = true;
-            p->ov_parity ^= 1;
-            flip[2] = true;
-            first = 3;
-        }
-    } else if (!(!mixed_hist && carry_wanted(1)) && (rc = pddc_pipeline_fence(p, s))) {
-        return rc;                                          /* any other route runs the later stages in line */
-    }
-    for (int i = first; i < p->nstages && i < skip_from; ++i) {
-        Stage &st = p->st[i];
-        if (p->fail_at_stage >= 0 && p->fail_at_stage <= i) {
-            p->fail_at_stage = -1;
-            return fail(PDDC_EHIP, "injected failure at stage %d (pddc_pipeline_inject_failure)", i);
-        }
-        float *dst;
-        if ((rc = stage_dst(i, &dst, i == 0)))
-            return rc;
-        void *h_in = st.d_hist[st.cur], *h_out = st.d_hist[st.cur ^ 1];
-        const void *x = d_packed;                       /* this stage's input batch */
-        bool hist_done = false;
-        if (i == 0 && mixed_hist) {
-            /* rare: batches shorter than the history with retunes between them.  The packed history
-             * is unpacked and mixed stretch by stretch, each with the word and offset that applied to
-             * it, the batch likewise with the current word, and the generic decimator runs on floats;
-             * the packed history for the next call is carried as usual.                            */
-            const int H = st.hist;
-            if ((rc = ensure_buf(st, nsamples + 8)))
-                return rc;
-            if (!p->d_hist_f32)
-                HIP_TRY(hipMalloc(&p->d_hist_f32, (size_t)PDDC_MAX_TAPS * 8 + 256));
-            const long long w0 = (long long)p->n0 - H;
-            for (size_t k = 0; k < p->segs.size(); ++k) {
-                const long long a0 = std::max(w0, k == 0 ? w0 : p->segs[k].n_begin);
-                const long long a1 = std::min((long long)p->n0, k + 1 < p->segs.size() ? p->segs[k + 1].n_begin
-                                                                                       : (long long)p->n0);
-                if (a1 <= a0)
-                    continue;
-                float lc[8], ls[8];
-                lo_steps(p->segs[k].freg, lc, ls);
-                HIP_TRY(launch_unpack24(static_cast<const uint8_t *>(h_in) + (a0 - w0) * PDDC_PACKED_BYTES, a1 - a0,
-                                        p->d_hist_f32 + 2 * (a0 - w0), false, true, (unsigned long long)a0,
-                                        p->segs[k].freg, p->segs[k].off, lc, ls, s));
-            }
-            HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, true, p->n0, p->freg, p->phase_off,
-                                    p->lo_c, p->lo_s, s));
-            if (n_in[1] > 0)
-                HIP_TRY(launch_fir_generic(st.d_buf, p->d_hist_f32, H, (long long)off[0], (long long)n_in[1], st.decim,
-                                           st.d_taps_dup, st.ntaps, dst, nullptr, (long long)nsamples, s));
-            /* hist_done stays false: the packed history moves on below (x == d_packed) */
-        } else if (i == 0 && stage0_fused(p)) {
-            /* overlap mode, two-stage plan: stage 1 is held back and rides along with the next batch's stage 0 */
-            GenTail mine;
-            bool ov = !g && carry_wanted(1) && p->NT == 256 && i8kind != 2;   /* (k_fir_i8x carries no tail: in line) */
-            if (ov) {
-                rc = carry_setup(1, &dst, &mine, p->ov_parity == 1, kCarryLdsCap);
-                if (rc < 0)
-                    return rc;
-                ov = rc == PDDC_OK;
-            }
-            const bool gtail = g && p->nstages == 2;
-            if (gtail && (rc = carry_setup(1, &dst, &mine, false, 160u * 1024u)))
-                return rc;
-            if (!ov && (rc = pddc_pipeline_fence(p, s)))
-                return rc;
-            Fir8Args a;
-            a.in = d_packed;
-            a.hist = h_in;
-            a.hist_out = nsamples >= (size_t)st.hist ? h_out : nullptr;
-            a.out = dst;
-            a.taps_blk = st.d_taps_blk;
-            a.n_in = (long long)nsamples;
-            fill_fir8_args(p, a);
-            if (ov && p->carry_pending)
-                a.tail = p->carry_tail;
             if ((rc = stage0_event(p, s, true)))
                 return rc;
-            if (g && i8kind == 2) {
-                FirI8xArgs q;
-                if ((rc = i8x_prepare(p, mix, false, s, q)))
-                    return rc;
-                q.in = d_packed;
-                q.hist = h_in;
-                q.hist_out = a.hist_out;
-                q.out = dst;
-                q.n_in = (long long)nsamples;
-                g->kind = 3;
-                g->mix = mix;
-                g->ax = q;
-                g->hist = st.hist;
-                g->fuse2 = false;
-                g->chunk = p->opt.i8x_chunk;
-                g->layout = p->opt.i8x_layout;
-                g->blocks = p->opt.i8x_blocks;
-                if (gtail) {
-                    g->tail = mine;
-                    flip[1] = true;
-                    skip_from = 1;
-                }
-            } else if (g) {
-                g->kind = 1;
-                g->ntb = st.ntb;
-                g->R = p->R;
-                g->mix = mix;
-                g->a = a;
-                if (gtail) {
-                    g->tail = mine;
-                    flip[1] = true;
-                    skip_from = 1;
-                }
-            } else if (i8kind == 2 && !ov) {
-                /* the NCO in the taps, the wire bytes on the int8 matrix cores (k_fir_i8x; same history as k_fir8) */
-                FirI8xArgs q;
-                if ((rc = i8x_prepare(p, mix, false, s, q)))
-                    return rc;
-                q.in = d_packed;
-                q.hist = h_in;
-                q.hist_out = a.hist_out;
-                q.out = dst;
-                q.n_in = (long long)nsamples;
-                HIP_TRY(launch_fir_i8x(q, st.hist, mix, false, s, p->opt.i8x_blocks, p->opt.i8x_chunk, p->opt.i8x_layout));
-            } else {
-                HIP_TRY(launch_fir8(st.ntb, p->R, IN_PACKED24, mix, a, s, p->NT));
-            }
+            HIP_TRY(launch_first(r, s));
+            if (r.hold_tail)
+                p->carry_pending = false;   /* the previous tail went out with this launch (only once it was accepted) */
             if ((rc = stage0_event(p, s, false)))
                 return rc;
-            hist_done = a.hist_out != nullptr;
-            if (ov) {
-                p->carry_tail = mine;
-                p->carry_pending = true;
-                p->ov_parity ^= 1;
-                flip[1] = true;
-                skip_from = 1;
-            }
-        } else if (i == 0 && stage0_packed_generic(p)) {
-            if (n_in[1] > 0 && i8x_d10_ok(p)) {
-                /* the matrix cores: the decimation phase of this batch (its first output's newest sample, 0 .. 9) goes into
-                 * the taps as a delay, so that the windows end on a multiple of 8 samples */
-                const int first = (int)off[0], delay = (8 - (first & 7)) & 7;
-                FirI8xArgs q;
-                if ((rc = i8x_d10_prepare(p, delay, s, q)))
-                    return rc;
-                q.in = d_packed;
-                q.hist = h_in;
-                q.hist_out = nsamples >= (size_t)st.hist ? h_out : nullptr;
-                q.out = static_cast<float *>(dst);
-                q.n_in = (long long)nsamples;
-                q.n_out = (long long)n_in[1];
-                q.in_off = first + delay;
-                q.hist_len = st.hist;
-                q.n0 = p->n0 + (unsigned long long)q.in_off;
-                if ((rc = stage0_event(p, s, true)))
-                    return rc;
-                HIP_TRY(launch_fir_i8x_d10(q, s, p->opt.i8x_blocks, p->opt.i8x_chunk, p->opt.i8x_layout));
-                if ((rc = stage0_event(p, s, false)))
-                    return rc;
-                x = d_packed;                 /* (a batch shorter than the history: the packed history moves on below) */
-                hist_done = q.hist_out != nullptr;
-            } else if (n_in[1] > 0) {
-                if (st.d_taps_firp)           /* register-blocked kernel for /4 /5 /8 /10 */
-                    HIP_TRY(launch_firp_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1], st.decim,
-                                               st.d_taps_firp, st.ntaps, dst, h_out, (long long)nsamples, mix, p->n0,
-                                               p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s, p->lo_c_applied,
-                                               p->lo_s_applied, s));
-                else
-                    HIP_TRY(launch_fir_generic_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1],
-                                                      st.decim, st.d_taps_dup, st.ntaps, dst, h_out, (long long)nsamples,
-                                                      mix, p->n0, p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s,
-                                                      p->lo_c_applied, p->lo_s_applied, s));
-                hist_done = true;             /* block 0 of the kernel wrote the new (packed) history */
-            }
-        } else {
-            if (i == 0) {
-                /* generic first stage: unpack(+mix) to float2, then the generic FIR */
-                if ((rc = ensure_buf(st, nsamples + 8)))
-                    return rc;
-                HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, mix, p->n0, p->freg,
-                                        p->phase_off, p->lo_c, p->lo_s, s));
-            }
-            x = st.d_buf;
-            const bool fast = i > 0 && st.ntb != 0 && !(p->flags & PDDC_F_NO_FAST) &&
-                              fir8_supported(st.ntb, p->R) && (n_in[i] % 8 == 0) && off[i] == 0 &&
-                              (st.consumed % 8 == 0) && n_in[i] > 0;
-            if (fast) {
-                Fir8Args a;
-                a.in = x;
-                a.hist = h_in;
-                a.hist_out = n_in[i] >= (size_t)st.hist ? h_out : nullptr;
-                a.out = dst;
-                a.taps_blk = st.d_taps_blk;
-                a.n_in = (long long)n_in[i];
-                fill_fir8_args(p, a);
-                HIP_TRY(launch_fir8(st.ntb, p->R, IN_F32C, false, a, s));
-                hist_done = a.hist_out != nullptr;
-            } else if (st.interp > 1) {
-                if (n_in[i + 1] > 0 && st.d_taps_poly && !(p->flags & PDDC_F_NO_FAST)) {
-                    HIP_TRY(launch_resample_lds(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
-                                                st.consumed, m0[i], (long long)n_in[i + 1], st.interp, st.decim,
-                                                st.d_taps_poly, st.poly_k, st.poly_kp, dst, static_cast<float *>(h_out),
-                                                (long long)n_in[i], s));
-                    hist_done = true;
-                } else if (n_in[i + 1] > 0) {
-                    HIP_TRY(launch_resample(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
-                                            st.consumed, m0[i], (long long)n_in[i + 1], st.interp, st.decim,
-                                            st.d_taps, st.ntaps, dst, s));
-                }
-            } else if (n_in[i + 1] > 0) {
-                if (st.d_taps_firp)
-                    HIP_TRY(launch_firp(IN_F32C, false, x, h_in, st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
-                                        st.d_taps_firp, st.ntaps, dst, h_out, (long long)n_in[i], nullptr, s));
-                else
-                    HIP_TRY(launch_fir_generic(static_cast<const float *>(x), static_cast<const float *>(h_in),
-                                               st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
-                                               st.d_taps_dup, st.ntaps, dst, static_cast<float *>(h_out),
-                                               (long long)n_in[i], s));
-                hist_done = true;             /* block 0 of the kernel wrote the new history */
-            }
         }
-        if (n_in[i] > 0) {
-            if (!hist_done)
-                HIP_TRY(launch_hist_update(h_out, h_in, st.hist, x, (long long)n_in[i], st.hist_elem, s));
-            flip[i] = true;
-        }
+        Stage &s0 = p->st[0];
+        if (nsamples < (size_t)s0.hist)     /* the kernel wrote no history (build_first): it moves on here */
+            HIP_TRY(launch_hist_update(s0.d_hist[s0.cur ^ 1], s0.d_hist[s0.cur], s0.hist, d_packed, (long long)nsamples,
+                                       s0.hist_elem, s));
+        next = r.stages;
+    } else if ((rc = pddc_pipeline_fence(p, s))) {
+        return rc;                          /* the stages run in line: what is held back goes first */
     }
+    for (int i = next; i < p->nstages; ++i)
+        if ((rc = run_stage(p, i, rt.route, b, d_packed, d_out, s)))
+            return rc;
     if (p->flags & PDDC_F_OUT_PACKED24)
         HIP_TRY(launch_pack24(p->d_fout, (long long)n_final, d_out, s));
-    for (int i = 0; i < p->nstages; ++i) {          /* commit */
-        if (flip[i])
+
+    if (r.hold_tail) {                      /* this batch's last stage is held back for the next launch */
+        p->carry_tail = r.tail;
+        p->carry_pending = true;
+        p->ov_parity ^= 1;
+    }
+    for (int i = 0; i < p->nstages; ++i) {  /* commit: every stage that had input has its new history */
+        if (b.n_in[i] > 0)
             p->st[i].cur ^= 1;
-        p->st[i].consumed += n_in[i];
+        p->st[i].consumed += b.n_in[i];
     }
     p->n0 += nsamples;
     if (p->freg_applied != p->freg) {
@@ -2273,6 +2258,12 @@ int pddc_pipeline_process(pddc_pipeline *p, const void *d_packed, size_t nsample
     if (n_out_ret)
         *n_out_ret = n_final;
     return PDDC_OK;
+}
+
+int pddc_pipeline_process(pddc_pipeline *p, const void *d_packed, size_t nsamples, void *d_out,
+                          size_t out_capacity, size_t *n_out_ret, void *stream_v)
+{
+    return process_batch(p, d_packed, nsamples, d_out, out_capacity, n_out_ret, (hipStream_t)stream_v, nullptr);
 }
 
 int pddc_host_alloc(void **h_ptr, size_t nbytes)
@@ -2675,21 +2666,20 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
     }
     /* every member plans its batch: the ones whose plan is "first-stage kernel [+ one plain decimator]" leave a record,
      * the others run their own launches on the gang's stream right here */
-    GangRec rec[PDDC_GANG_MAX];
+    FirstLaunch rec[PDDC_GANG_MAX];
     bool open[PDDC_GANG_MAX];
     float *direct[PDDC_GANG_MAX];
+    const bool try_gang = n > 1 && !tunables().gang_solo.load();
     for (int i = 0; i < n; ++i) {
         pddc_pipeline *p = items[i].pipe;
         pddc_pipeline::HostSlot &sl = p->slot[si[i]];
         direct[i] = (p->flags & PDDC_F_OUT_PACKED24) ? nullptr : direct_out(sl, items[i].h_out);
         void *dst = direct[i] ? direct[i] : sl.d_out;
         const size_t cap = direct[i] ? items[i].out_capacity : sl.out_cap;
-        p->gang_rec = n > 1 && !tunables().gang_solo.load() ? &rec[i] : nullptr;
-        int rc = p->gang_rec ? pddc_pipeline_process(p, sl.d_in, nsamples, dst, cap, &items[i].n_out, s) : 1;
-        p->gang_rec = nullptr;
-        open[i] = rc == PDDC_OK && rec[i].kind != 0;
+        int rc = try_gang ? process_batch(p, sl.d_in, nsamples, dst, cap, &items[i].n_out, s, &rec[i]) : 1;
+        open[i] = rc == PDDC_OK;
         if (rc == 1) {
-            rc = pddc_pipeline_process(p, sl.d_in, nsamples, dst, cap, &items[i].n_out, s);
+            rc = process_batch(p, sl.d_in, nsamples, dst, cap, &items[i].n_out, s, nullptr);
             if (rc == PDDC_OK)
                 rc = pddc_pipeline_fence(p, s);
         }
@@ -2705,13 +2695,13 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
         GenTailMany tm;
         int k = 0;
         bool any_tail = false;
-        const bool x = rec[i].kind == 3;
+        const bool x = rec[i].route == Route::I8x || rec[i].route == Route::I8xPair;
         for (int j = i; j < n; ++j) {
-            if (!open[j] || rec[j].kind != rec[i].kind || rec[j].mix != rec[i].mix ||
+            if (!open[j] || rec[j].route != rec[i].route || rec[j].mix != rec[i].mix ||
                 (rec[j].tail.nblocks > 0) != (rec[i].tail.nblocks > 0) || rec[j].tail.kind != rec[i].tail.kind ||
                 rec[j].tail.D != rec[i].tail.D || rec[j].tail.ntaps != rec[i].tail.ntaps)
                 continue;
-            if (x ? (rec[j].hist != rec[i].hist || rec[j].fuse2 != rec[i].fuse2 || rec[j].ax.n_in != rec[i].ax.n_in)
+            if (x ? (rec[j].hist != rec[i].hist || rec[j].ax.n_in != rec[i].ax.n_in)
                   : (rec[j].ntb != rec[i].ntb || rec[j].R != rec[i].R || rec[j].a.n_in != rec[i].a.n_in))
                 continue;
             if (x)
@@ -2724,9 +2714,10 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
             ++k;
         }
         if (x)
-            HIP_TRY(launch_fir_i8x_many(xm, k, rec[i].hist, rec[i].mix, rec[i].fuse2, s, rec[i].blocks, rec[i].chunk, rec[i].layout));
+            HIP_TRY(launch_fir_i8x_many(xm, k, rec[i].hist, rec[i].mix, rec[i].route == Route::I8xPair, s, rec[i].blocks,
+                                        rec[i].chunk, rec[i].layout));
         else
-            HIP_TRY(launch_fir8_many(rec[i].kind, rec[i].ntb, rec[i].R, rec[i].mix, fm, k, s));
+            HIP_TRY(launch_fir8_many(rec[i].route == Route::Fir8Pair ? 2 : 1, rec[i].ntb, rec[i].R, rec[i].mix, fm, k, s));
         if (any_tail)
             HIP_TRY(launch_gen_tail_many(tm, k, s));
         if (n_ganged)
@@ -2937,11 +2928,13 @@ int pddc_pipeline_schedule(const pddc_pipeline *p, size_t nsamples, int out[5])
         return fail(PDDC_EINVAL, "null argument");
     if (!stage0_fused(p))
         return fail(PDDC_ESTATE, "stage 0 does not run the fused kernel");
-    const bool fuse2 = stages01_fusable(p, nsamples);
+    /* k_fir8's form for the stages the first launch covers (where k_fir_i8x takes them: the form k_fir8 would take) */
+    const RouteChoice rt = choose_route(p, nsamples, false);
+    const bool fuse2 = rt.nfirst >= 2 && fir8_fused2_supported(p->st[0].ntb, p->st[1].ntb, p->R);
     const int nt = fuse2 ? 256 : p->NT;
     out[0] = fir8_tile_inputs(p->R, nt);
     fir8_schedule_query((long long)nsamples, p->R, fuse2, nt, &out[1], &out[2], &out[3], &out[4],
-                        stages012_fusable(p, nsamples) ? p->s3.g : 0);
+                        rt.route == Route::Fused3 ? p->s3.g : 0);
     return PDDC_OK;
 }
 
@@ -2984,64 +2977,25 @@ int pddc_pipeline_time_stage0(pddc_pipeline *p, const void *d_packed, size_t nsa
         return fail(PDDC_EINVAL, "bad size/alignment");
     hipStream_t s = (hipStream_t)stream_v;
     HIP_TRY(hipSetDevice(p->device));
-    Fir8Args a;
-    a.in = d_packed;
-    a.hist = p->st[0].d_hist[p->st[0].cur];
-    a.hist_out = nullptr;                  /* state is not advanced */
-    a.out = static_cast<float *>(d_out);
-    const bool fuse2 = stages01_fusable(p, nsamples);
-    const bool fuse3 = stages012_fusable(p, nsamples);
+    float *dst = static_cast<float *>(d_out);
     if (p->nstages > 1) {                  /* stage 0 (or the fused pair) of a cascade writes an internal buffer */
         int rc = ensure_buf(p->st[1], nsamples / (size_t)p->st[0].decim + 8);
         if (rc)
             return rc;
-        a.out = p->st[1].d_buf;
+        dst = p->st[1].d_buf;              /* (the fused cascade's third-stage outputs too) */
     }
-    if (fuse3) {                           /* the fused cascade: third-stage outputs into that buffer, state untouched */
-        size_t off3, n3;
-        unsigned long long m3;
-        stage_outputs(p->st[2].consumed, nsamples / 64, p->st[2].decim, 1, &off3, &m3, &n3);
-        fill_stage3_args(p, a, a.out, off3, n3, false);
-    }
-    if (fuse2) {
-        a.taps2_blk = p->st[1].d_taps_blk;
-        a.hist2 = p->st[1].d_hist[p->st[1].cur];
-        a.hist2_out = nullptr;
-    }
-    a.taps_blk = p->st[0].d_taps_blk;
-    a.n_in = (long long)nsamples;
-    fill_fir8_args(p, a);
-    const bool mix = (p->flags & PDDC_F_MIX) != 0;
-    const int i8kind = stage0_i8_kind(p, nsamples);                    /* what process() would launch for this batch */
-    const bool x2 = !fuse3 && i8kind == 2 && stages01_i8x(p, nsamples);
-    const bool x1 = !fuse3 && !x2 && !fuse2 && i8kind == 2;
-    FirI8xArgs qx;
-    if (x1 || x2) {
-        int rc = i8x_prepare(p, mix, x2, s, qx);
-        if (rc)
-            return rc;
-        qx.in = d_packed;
-        qx.hist = a.hist;
-        qx.hist_out = nullptr;
-        qx.out = a.out;
-        qx.n_in = (long long)nsamples;
-        qx.hist2 = p->st[1].d_hist[p->st[1].cur];
-        qx.hist2_out = nullptr;
-    }
+    BatchPlan b;                           /* what process() would launch for this batch, state untouched */
+    plan_batch(p, nsamples, b);
+    FirstLaunch r;
+    int rc = build_first(p, choose_route(p, nsamples, false).route, b, d_packed, dst, false, s, r);
+    if (rc)
+        return rc;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     HIP_TRY(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) {
-        if (fuse3)
-            HIP_TRY(launch_fir8_fused3(p->st[0].ntb, p->R, mix, a, s));
-        else if (x1 || x2)
-            HIP_TRY(launch_fir_i8x(qx, p->st[0].hist, mix, x2, s, p->opt.i8x_blocks, p->opt.i8x_chunk, p->opt.i8x_layout));
-        else if (fuse2)
-            HIP_TRY(launch_fir8_fused2(p->st[0].ntb, p->R, mix, a, s));
-        else
-            HIP_TRY(launch_fir8(p->st[0].ntb, p->R, IN_PACKED24, mix, a, s, p->NT));
-    }
+    for (int i = 0; i < iters; ++i)
+        HIP_TRY(launch_first(r, s));
     HIP_TRY(hipEventRecord(e1, s));
     HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.0f;

@@ -953,6 +953,37 @@ def test_a_failed_batch_leaves_the_stream_where_it_was(pkg, dev, O):
     flaky.close()
 
 
+@pytest.mark.parametrize("form", ["k_fir_i8x", "k_fir8", "d10"])
+def test_a_failure_injected_at_a_lone_first_stage_fires_before_its_launch(pkg, dev, O, form):
+    """A plan that is one first-stage kernel (k_fir_i8x or k_fir8 alone, the decimate-by-10 matrix-core form): a failure
+    injected at stage 0 fails the batch before that kernel is launched, disarms the hook, and the retried batch
+    continues the stream bit-identically to one that never failed."""
+    stages = [(10, load_taps("c320_s3_d5_161")[:51])] if form == "d10" else [(8, load_taps("d8_127"))]
+    ns = 8 * 4096
+    batches = [to_dev(O.lcg_bytes(6 * ns, 300 + k), dev) for k in range(3)]
+    pipes = []
+    for _ in range(2):
+        pipe = pkg.Pipeline(stages, mix=True)
+        pipe.set_freg(123456789)
+        if form == "k_fir8":
+            pipe.set_option("no_i8", 1)
+        pipes.append(pipe)
+    good, flaky = pipes
+    assert good.on_i8(ns) == (0 if form == "k_fir8" else 2)
+    want = [good.process(b).cpu().numpy() for b in batches]
+    L = pkg.ddc_lib()
+    got = [flaky.process(batches[0]).cpu().numpy()]
+    assert L.pddc_pipeline_inject_failure(flaky._h, 0) == 0
+    with pytest.raises(pkg.PddcError) as e:
+        flaky.process(batches[1])
+    assert e.value.code == pkg.PDDC_EHIP and b"injected failure at stage 0" in L.pddc_last_error()
+    got += [flaky.process(b).cpu().numpy() for b in batches[1:]]   # the retry, and the hook is gone
+    for k in range(len(batches)):
+        assert np.array_equal(got[k], want[k]), k
+    good.close()
+    flaky.close()
+
+
 def test_too_small_output_buffer_is_refused_before_anything_runs(pkg, dev, O):
     import ctypes as C
     h = load_taps("d8_127")
