@@ -357,6 +357,47 @@ int pddc_gang_create(pddc_gang **out, int device);
 int pddc_gang_destroy(pddc_gang *g);      /* after (or before) its pipelines: waits for what is in flight */
 int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsamples, int *n_ganged);
 
+/* ---- bank: several tuned receivers from ONE read of the same batch -------------------------
+ * A gang round shares launches, but every receiver still reads its own copy of the batch.  A
+ * bank is a fixed set of up to PDDC_BANK_MAX pipelines of one GPU that are fed the SAME batch
+ * every round; members whose first stage is the tuned decimate-by-8 on the matrix cores (<= 64
+ * taps: history 32 or 64) share its launch -- one read of the batch for up to four of them
+ * (k_fir_i8x_bank) -- grouped by history length into launches of 4, 2 and 1 members (8 = 4 + 4,
+ * 6 = 4 + 2, 3 = 2 + 1).  Everything behind the first stage runs per member as in
+ * pddc_pipeline_process, and a banked member's outputs, histories, counters and save_state blob
+ * are bit for bit what pddc_pipeline_process gives that pipeline alone with option no_fuse2 = 1.
+ * Each member keeps its own plan, word, taps, options and buffers.
+ * A member is banked in a round when its batch would take k_fir_i8x alone with one tuning word
+ * in its history window (no retune inside it), no overlap mode, no packed output, no stage-0 timing
+ * and default k_fir_i8x options -- and it is ALIGNED: its stage-0 history is the bank's (the last
+ * samples of the previous round's batch, or zeros while every member is fresh).  A member is
+ * aligned after create if it was fresh (created, reset or seek, nothing processed), and after
+ * every round whose batch held at least its history length; anything done to it outside the
+ * bank (process, push, reset, seek, restore_state, set_taps) makes it unaligned for one round.
+ * Members that are not banked run pddc_pipeline_process on the same stream in the same round:
+ * every member's output is correct in every round, only the sharing changes.
+ * A pipeline belongs to at most one bank; destroy the bank before its members.  A member
+ * destroyed first is detached: the bank refuses further rounds (PDDC_ESTATE) and can still be
+ * destroyed.  Everything that can refuse a round (null pointers or capacities, a detached member,
+ * a held-back overlap tail, nsamples not a multiple of 8) is checked before anything is queued:
+ * such a call leaves every stream where it was.  A failure AFTER that (a HIP error while queueing,
+ * or an error an unbanked member's own processing reports, e.g. an overlap-mode member whose
+ * workspace cannot take its tail) leaves the members before it advanced and the rest where they
+ * were: reset or destroy them.  One thread at a time per bank. */
+#define PDDC_BANK_MAX 8
+typedef struct pddc_bank pddc_bank;
+/* members[0 .. n): distinct pipelines on `device`, none in another bank (PDDC_ENODEV without a GPU) */
+int pddc_bank_create(pddc_bank **out, int device, pddc_pipeline *const *members, int n);
+int pddc_bank_destroy(pddc_bank *b);
+/* one batch of nsamples at d_packed through every member; member i writes d_out[i] (capacity out_capacity[i]),
+ * n_out[i] = its outputs; *n_banked = members whose first stage shared a bank launch.  Stream-ordered like
+ * pddc_pipeline_process. */
+int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void *const *d_out,
+                      const size_t *out_capacity, size_t *n_out, int *n_banked, void *stream);
+/* what the next round of nsamples would do: bit i set = member i shares a bank launch; *launches = bank launches
+ * (a group of one is a launch of the solo kernel and counts) */
+int pddc_bank_schedule(const pddc_bank *b, size_t nsamples, unsigned *banked_mask, int *launches);
+
 /* pinned host memory for the two calls above */
 int pddc_host_alloc(void **h_ptr, size_t nbytes);
 int pddc_host_free(void *h_ptr);

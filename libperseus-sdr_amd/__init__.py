@@ -172,6 +172,14 @@ def ddc_lib() -> C.CDLL:
     L.pddc_gang_destroy.restype = C.c_int
     L.pddc_gang_push_async.argtypes = [vp, C.POINTER(GangItem), C.c_int, sz, C.POINTER(C.c_int)]
     L.pddc_gang_push_async.restype = C.c_int
+    L.pddc_bank_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int]
+    L.pddc_bank_create.restype = C.c_int
+    L.pddc_bank_destroy.argtypes = [vp]
+    L.pddc_bank_destroy.restype = C.c_int
+    L.pddc_bank_process.argtypes = [vp, vp, sz, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_int), vp]
+    L.pddc_bank_process.restype = C.c_int
+    L.pddc_bank_schedule.argtypes = [vp, sz, C.POINTER(C.c_uint), C.POINTER(C.c_int)]
+    L.pddc_bank_schedule.restype = C.c_int
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
     L.pddc_pipeline_time_stage0_inline.restype = C.c_int
@@ -601,6 +609,42 @@ class Gang:
     def close(self):
         if getattr(self, "_h", None):
             ddc_lib().pddc_gang_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Bank:
+    """pddc_bank: up to PDDC_BANK_MAX pipelines of one GPU fed the same batch every round; the tuned first stages of up to
+    four of them come from one read of it (include/perseus_ddc.h).  Destroy it before its pipelines."""
+
+    def __init__(self, pipes, device: int = 0):
+        self.pipes = list(pipes)                  # (keeps the members alive as long as the bank)
+        arr = (C.c_void_p * len(self.pipes))(*[p._h.value if isinstance(p._h, C.c_void_p) else p._h for p in self.pipes])
+        h = C.c_void_p()
+        check(ddc_lib().pddc_bank_create(C.byref(h), device, arr, len(self.pipes)))
+        self._h = h
+
+    def process_ptr(self, d_in: int, nsamples: int, d_outs, caps, stream: int = 0):
+        """One round: nsamples packed samples at device address d_in through every member; member i writes d_outs[i]
+        (capacity caps[i] outputs).  -> (list of n_out, number of members whose first stage shared a bank launch)."""
+        k = len(self.pipes)
+        outs = (C.c_void_p * k)(*[int(d) for d in d_outs])
+        cap = (C.c_size_t * k)(*[int(c) for c in caps])
+        n = (C.c_size_t * k)()
+        nb = C.c_int()
+        check(ddc_lib().pddc_bank_process(self._h, d_in, nsamples, outs, cap, n, C.byref(nb), stream))
+        return [int(v) for v in n], nb.value
+
+    def schedule(self, nsamples: int):
+        """-> (mask: bit i = member i shares a bank launch in the next round of nsamples, bank launches)"""
+        mask, launches = C.c_uint(), C.c_int()
+        check(ddc_lib().pddc_bank_schedule(self._h, nsamples, C.byref(mask), C.byref(launches)))
+        return mask.value, launches.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            ddc_lib().pddc_bank_destroy(self._h)
             self._h = None
 
     __del__ = close

@@ -11,12 +11,14 @@ The source avoids both (no 2-vector arithmetic in the finishing code, -fno-slp-v
 asm statement).  A compiler update, a build line without the flag or a new 2-vector expression would bring them back
 silently; this script looks at the machine code instead:
   * every k_fir_i8x / k_fir_i8x_many instantiation with LAYOUT 1 (loaders finish tiles) or LAYOUT 2 (two finishing waves
-    whose SIMDs hold no matrix wave only as long as waves w, w + 4, w + 8 share a SIMD -- measured, not guaranteed): no
-    v_pk_*_f32 at all;
-  * LAYOUT 1 and 2: every nontemporal result store (`global_store_dword[x2] ... nt`) is followed by `s_nop`, no global
+    whose SIMDs hold no matrix wave only as long as waves w, w + 4, w + 8 share a SIMD -- measured, not guaranteed), and
+    every k_fir_i8x_bank instantiation (the channel bank: its matrix waves store results while the other channels' matrix
+    waves run; the same rules, DESIGN.md 4): no v_pk_*_f32 at all;
+  * LAYOUT 1 and 2 and the bank: every nontemporal result store (`global_store_dword[x2] ... nt`) is followed by `s_nop`, no global
     store at all is followed directly by a vector instruction, and there IS at least one such store (a kernel without
     any would pass the check by having lost what it checks).
-usage: check_hazard_pads.py ddc_fir_i8.o [--arch gfx950] [--llvm-bin DIR]"""
+The bank's instantiations for 2 and 4 channels must be there, or the check fails.
+usage: check_hazard_pads.py ddc_fir_i8.o [--arch gfx950] [--llvm-bin DIR] [--list]"""
 import os
 import re
 import subprocess
@@ -24,6 +26,7 @@ import sys
 import tempfile
 
 NAME = re.compile(r"k_fir_i8x(?:_many)?ILi(\d+)ELi(\d)ELb([01])ELi(\d)E")
+BANK = re.compile(r"k_fir_i8x_bankILi(\d+)ELi(\d)E")
 
 
 class ToolError(Exception):
@@ -58,6 +61,7 @@ def main(argv):
                     help="no check, a count: packed fp32 instructions whose SECOND source takes its low half from the high register\n"
                          "(op_sel[1] = 1) -- the operand selection that delivered a zero low half beside a matrix wave (NOTEBOOK R6.4);\n"
                          "for objects whose kernels never share a SIMD with a matrix wave inside one launch chain (ddc_kernels.o)")
+    ap.add_argument("--list", action="store_true", help="print every checked kernel as `checked: <form> <symbol>`")
     a = ap.parse_args(argv)
     if a.report_src1_swap:
         try:
@@ -84,15 +88,22 @@ def main(argv):
             ins = line.strip().split("//")[0].strip()
             if ins:
                 cur.append(ins)
-    problems, checked = [], 0
+    problems, checked, bank_nch = [], 0, set()
     for name, code in kernels.items():
-        m = NAME.search(name)
-        if not m:
+        m, mb = NAME.search(name), BANK.search(name)
+        if mb:
+            form = f"bank hist {mb.group(1)} nch {mb.group(2)}"
+            bank_nch.add(int(mb.group(2)))
+        elif m:
+            layout = int(m.group(4))
+            if layout == 0:
+                continue                   # the matrix waves finish their own tiles: no other matrix wave on their SIMD
+            form = f"layout {layout}"
+        else:
             continue
-        layout = int(m.group(4))
-        if layout == 0:
-            continue                       # the matrix waves finish their own tiles: no other matrix wave on their SIMD
         checked += 1
+        if a.list:
+            print(f"checked: {form} {name}")
         pk = [i for i in code if re.match(r"v_pk_(mul|fma|add)_f32", i)]
         if pk:
             problems.append(f"{name}: {len(pk)} packed fp32 instructions in a kernel whose finishing waves may sit beside matrix "
@@ -112,10 +123,14 @@ def main(argv):
             problems.append(f"{name}: no nontemporal result store found at all: has store_f2_padded changed its instruction?")
     if not checked:
         problems.append("no k_fir_i8x instantiation with LAYOUT 1 or 2 found: has the kernel been renamed?")
+    for nch in (2, 4):
+        if nch not in bank_nch:
+            problems.append(f"no k_fir_i8x_bank instantiation for {nch} channels found: has the kernel been renamed?")
     for p in problems:
         print("check_hazard_pads:", p, file=sys.stderr)
     if not problems:
-        print(f"check_hazard_pads: {checked} k_fir_i8x kernels with finishing waves (layouts 1, 2): no packed fp32, every result store padded")
+        print(f"check_hazard_pads: {checked} k_fir_i8x kernels with finishing waves (layouts 1, 2, the bank): no packed fp32, every result "
+              f"store padded")
     return 1 if problems else 0
 
 

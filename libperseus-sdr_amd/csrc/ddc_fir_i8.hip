@@ -271,13 +271,20 @@ struct Roles {
 };
 
 /* the block's work; `nblk` blocks walk this stream's tiles, this is block `blk` of them (k_fir_i8x: the grid; k_fir_i8x_many:
- * the grid's x dimension, one stream per y) */
-template <int HIST, int MODE, bool FUSE2, int LAYOUT, int D = 8>
+ * the grid's x dimension, one stream per y).
+ * NCH > 1 (k_fir_i8x_bank; tuned paired rows, layout 0 only): NCH channels over ONE plane set per tile.  Matrix wave w works
+ * for channel w / (4 / NCH) -- `a` is that channel's record, the loaders get channel 0's -- and takes 2 NCH of the tile's 8
+ * column blocks; each channel has ONE value array pair (no double buffer: 4 x 10 KB beside the planes' 109 KB), and the wave
+ * finishes exactly the outputs it computed, so only its own LDS writes are read back and no other wave waits for them. */
+template <int HIST, int MODE, bool FUSE2, int LAYOUT, int D = 8, int NCH = 1>
 __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long ntiles, int C, long long nblk, long long blk)
 {
     using namespace i8x;
     using G = Geo<HIST, MODE, FUSE2, D>;
     using R = Roles<LAYOUT, D>;
+    static_assert(NCH == 1 || (MODE == 2 && !FUSE2 && LAYOUT == 0 && D == 8 && (NCH == 2 || NCH == 4)),
+                  "the bank: tuned paired rows, decimate by 8, matrix waves finish, 2 or 4 channels");
+    static_assert(12 * (size_t)G::PLANE + (size_t)NCH * G::NARR * G::AS * sizeof(float) <= 160 * 1024, "bank LDS");
     constexpr int TILE_S = G::TILE_S, NGRP = R::NGRP;
     constexpr bool PART = NGRP % R::NLT != 0;                  /* the last round of main groups is a partial one */
     constexpr int PLANE = G::PLANE, KSTEPS = G::KSTEPS, AS = G::AS, NARR = G::NARR, PORCH = G::PORCH, EXTRA = G::EXTRA,
@@ -304,19 +311,22 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
         v = y;
     };
     auto put_f2 = [&](float2 *p, float x, float y) __attribute__((always_inline)) {
-        if (LAYOUT == 0) {
+        if (LAYOUT == 0 && NCH == 1) {
             const f32x2 v = { x, y };
             __builtin_nontemporal_store(v, reinterpret_cast<f32x2 *>(p));
         } else
             store_f2_padded(p, x, y);
     };
-    auto post_store = [&](long long t, const float *arr, int pt, auto guard_c) __attribute__((always_inline)) {
+    /* outputs pt + STRIDE o4 (o4 = 0 .. COUNT) of tile t from their values in `arr`: combine, rotate, store (NPT finishing
+     * threads: STRIDE = NPT, COUNT = 1024 / NPT; the bank's matrix waves: their own outputs, STRIDE = 64) */
+    auto post_store = [&](long long t, const float *arr, int pt, auto guard_c, auto stride_c, auto count_c) __attribute__((always_inline)) {
         constexpr bool GUARD = decltype(guard_c)::value;
+        constexpr int STRIDE = decltype(stride_c)::value, COUNT = decltype(count_c)::value;
         float2 *dst = reinterpret_cast<float2 *>(a.out) + t * 1024;
         const long long left = n_out - t * 1024;
 #pragma unroll
-        for (int o4 = 0; o4 < 1024 / NPT; ++o4) {
-            const int o = pt + NPT * o4;
+        for (int o4 = 0; o4 < COUNT; ++o4) {
+            const int o = pt + STRIDE * o4;
             const int q = 20 * (o >> 4) + (o & 15);
             float uI, uQ;
             if (MODE == 1) {
@@ -513,7 +523,7 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
     auto post = [&](long long t, float *arr, float *other, bool next_first, int pt, auto guard_c) __attribute__((always_inline)) {
         const int pw = __builtin_amdgcn_readfirstlane(pt >> 6);
         if (!FUSE2) {
-            post_store(t, arr, pt, guard_c);
+            post_store(t, arr, pt, guard_c, std::integral_constant<int, NPT>{}, std::integral_constant<int, 1024 / NPT>{});
         } else if (LAYOUT == 0) {
             if (pw < 2)
                 post_stage2(t, arr, pt);
@@ -868,17 +878,21 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
         }
     };
     __syncthreads();
+    /* the bank: this wave's channel and its share of the columns (NCH = 1: the wave's share of the tile) */
+    const int mw = NCH > 1 ? wave % (4 / NCH) : wave;
+    float *const arr_ch = arr_base + (NCH > 1 ? wave / (4 / NCH) : 0) * NARR * AS;
     int buf = 0;
     long long t = wk.tile(cur);
     while (t >= 0) {
         const bool first = cur.k == 0;
         cur = wk.next(cur);
         const uint8_t *pb = lds_i8x + buf * 6 * PLANE;
-        float *arr = arr_base + buf * NARR * AS, *arr_o = arr_base + (buf ^ 1) * NARR * AS;
+        float *arr = NCH > 1 ? arr_ch : arr_base + buf * NARR * AS, *arr_o = arr_base + (buf ^ 1) * NARR * AS;
         if (MODE == 2) {
             /* columns of 8 outputs, 8 D = 64 (80) samples apart: 128 of them in a tile, 16 per pass; every matrix wave makes both rails.
              * Output o = 8 col + 4 (kq & 1) + v lies at array position o + PORCH. */
             constexpr int NMW = LAYOUT == 2 ? 2 : 4;
+            constexpr int CPW = 8 / NMW * NCH;              /* column blocks per wave */
             if (FUSE2 && first && t > 0 && wave == NMW - 1) {
                 /* a chunk's first tile computes its own porch: columns -8 .. -1 in lanes 8..15; the other lanes repeat column
                  * -8 (same operand bytes, same results, same address: the whole wave runs the matrix instructions) */
@@ -886,8 +900,8 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
                 band(pb, EXTRA + 8 * D * colx + 16 * kq, arr + 20 * (pp >> 4) + (pp & 15));
             }
 #pragma unroll
-            for (int cb = 0; cb < 8 / NMW; ++cb) {
-                const int col = 16 * ((8 / NMW) * wave + cb) + n, pp = PORCH + 8 * col + 4 * (kq & 1);
+            for (int cb = 0; cb < CPW; ++cb) {
+                const int col = 16 * (CPW * mw + cb) + n, pp = PORCH + 8 * col + 4 * (kq & 1);
                 band(pb, EXTRA + 8 * D * col + 16 * kq, arr + 20 * (pp >> 4) + (pp & 15));
             }
         } else {
@@ -904,8 +918,19 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
         }
         }
         __syncthreads();                 /* ONE barrier per tile: the next tile's planes are written, this tile's values are in LDS */
-        if (LAYOUT == 0)                 /* ... and these waves finish it themselves */
+        if (NCH > 1) {                   /* the bank: this wave's own 256 NCH outputs of its channel, 64 consecutive per store */
+            /* (in rounds of 256 outputs, not unrolled: sixteen outputs' addresses and phases at once do not fit beside the
+             * tables) */
+#pragma unroll 1
+            for (int h = 0; h < NCH; ++h)
+                post_store(t, arr, 256 * (NCH * mw + h) + lane, std::true_type{}, std::integral_constant<int, 64>{},
+                           std::integral_constant<int, 4>{});
+            /* (the next tile's values go to the same array: the LDS unit keeps one wave's accesses in order, this keeps the
+             * compiler from moving them) */
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        } else if (LAYOUT == 0) {        /* ... and these waves finish it themselves */
             post(t, arr, arr_o, cur.k == 0, tid, std::true_type{});
+        }
         t = wk.tile(cur);
         buf ^= 1;
     }
@@ -944,6 +969,46 @@ __global__ __launch_bounds__(768, 1) void k_fir_i8x_many(FirI8xMany m, long long
     a.taps16 = r.taps16;
     a.two_e = r.two_e;
     fir_i8x_block<HIST, MODE, FUSE2, LAYOUT>(a, ntiles, C, (long long)gridDim.x, (long long)blockIdx.x);
+}
+
+/* The channel bank (ddc_kernels.h FirI8xBank): NCH tuned first stages from one read of the input.  The loaders are
+ * k_fir_i8x's, one plane set per tile for every channel; matrix wave w is channel w / (4 / NCH) over 2 NCH column blocks,
+ * with that channel's tables resident (64 registers, as in the solo form) and finishes its own outputs (fir_i8x_block).
+ * Which LDS option: the four channels' double-buffered value arrays (80 KB) do not fit beside the planes (109 KB); single
+ * buffers do (40 KB), because each matrix wave reads back only what it wrote itself -- no wave waits for another's values,
+ * and the tile keeps its ONE barrier.  Finishing straight from the accumulators would save the LDS round trip but needs
+ * rows 0..7 (uI) and 8..15 (uQ) of a column brought together across lane halves, and a combine / rotation in another
+ * order than the solo form's -- the outputs must be the solo form's bits, so the bank shares its finishing code instead. */
+template <int HIST, int NCH>
+__global__ __launch_bounds__(768, 1) void k_fir_i8x_bank(FirI8xBank b, long long ntiles, int C)
+{
+    /* the record through the scalar cache, the channel by a wave-uniform index (see k_fir_i8x_many) */
+    const FirI8xBank PDDC_CONSTANT &r = *(const FirI8xBank PDDC_CONSTANT *)__builtin_amdgcn_kernarg_segment_ptr();
+    (void)b;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ch = wave < 4 ? wave / (4 / NCH) : 0;
+    FirI8xArgs a;
+    a.in = r.a.in;
+    a.hist = r.a.hist;
+    a.n_in = r.a.n_in;
+    a.atab = r.ch[ch].atab;
+    a.out = r.ch[ch].out;
+    a.hist_out = r.ch[ch].hist_out;
+    a.scale = r.ch[ch].scale;
+    a.ct[0] = r.ch[ch].ct[0];
+    a.ct[1] = r.ch[ch].ct[1];
+    a.n0 = r.ch[ch].n0;
+    a.freg = r.ch[ch].freg;
+    a.phase_off = r.ch[ch].phase_off;
+    if (blockIdx.x == 0 && wave >= 4) {
+        /* the loaders write channel 0's next history (fir_i8x_block); the other channels get the same bytes here */
+        const int lt = threadIdx.x - 256;
+        const uint4 *src = reinterpret_cast<const uint4 *>(static_cast<const uint8_t *>(a.in) + (a.n_in - HIST) * 6);
+        for (int c = 1; c < NCH; ++c)
+            if (r.ch[c].hist_out && lt < HIST * 6 / 16)
+                static_cast<uint4 *>(r.ch[c].hist_out)[lt] = src[lt];
+    }
+    fir_i8x_block<HIST, 2, false, 0, 8, NCH>(a, ntiles, C, (long long)gridDim.x, (long long)blockIdx.x);
 }
 
 /* ---- host side: the tap operands ------------------------------------------------------------------------------------ */
@@ -1102,43 +1167,56 @@ void fir_i8x_taps2(const float *taps2, int ntaps2, bool mix, uint32_t freg, floa
     }
 }
 
+/* what every k_fir_i8x launcher does first: the device's CU count, looked up once per kernel (`cus` is that kernel's own
+ * cache, per device), and the LDS attribute of its kernels set on the same occasion */
+static hipError_t i8x_cus(int (&cus)[64], const void *k0, const void *k1, size_t lds, long long &ncu)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (cus[dev & 63] == 0) {
+        int v = 0;
+        hipError_t e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess)
+            return e;
+        for (const void *k : { k0, k1 })
+            if (k && (e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess)
+                return e;
+        cus[dev & 63] = v > 0 ? v : 256;
+    }
+    ncu = cus[dev & 63];
+    return hipSuccess;
+}
+
+/* the walk: chunks of C tiles (c_default unless asked) round at most nblk blocks, never more than a block's fair share,
+ * so that every CU has work -> the grid and C */
+static void i8x_walk(long long nblk, long long ntiles, int max_blocks, int chunk, long long c_default, long long &grid, long long &C)
+{
+    if (max_blocks > 0 && nblk > max_blocks)
+        nblk = max_blocks;
+    C = chunk > 0 ? chunk : c_default;
+    if (C > (ntiles + nblk - 1) / nblk)
+        C = (ntiles + nblk - 1) / nblk;
+    const long long nchunks = (ntiles + C - 1) / C;
+    grid = nchunks < nblk ? nchunks : nblk;
+}
+
 template <int HIST, int MODE, bool FUSE2, int LAYOUT, int D = 8>
 static hipError_t launch_fir_i8x_l(const FirI8xArgs &a, int max_blocks, int chunk, hipStream_t s, const FirI8xMany *many = nullptr,
                                    int nmany = 0)
 {
     using G = i8x::Geo<HIST, MODE, FUSE2, D>;
     const long long ntiles = D == 8 ? (a.n_in + i8x::TILE - 1) / i8x::TILE : (a.n_out + 1023) / 1024;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
     static int cus[64] = { 0 };
-    if (cus[dev & 63] == 0) {
-        int v = 0;
-        hipError_t e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e != hipSuccess)
-            return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fir_i8x<HIST, MODE, FUSE2, LAYOUT, D>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-        if (e != hipSuccess)
-            return e;
-        if (D == 8)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fir_i8x_many<HIST, MODE, FUSE2, LAYOUT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS_BYTES);
-        if (e != hipSuccess)
-            return e;
-        cus[dev & 63] = v > 0 ? v : 256;
-    }
-    /* chunks of C tiles go round the blocks: C = 1 (tile-interleaved) unless asked otherwise; never more than a block's
-     * fair share, so that every CU has work */
-    long long nblk = cus[dev & 63];
+    long long nblk = 0, grid = 0, C = 0;
+    const hipError_t e = i8x_cus(cus, reinterpret_cast<const void *>(&k_fir_i8x<HIST, MODE, FUSE2, LAYOUT, D>),
+                                 D == 8 ? reinterpret_cast<const void *>(&k_fir_i8x_many<HIST, MODE, FUSE2, LAYOUT>) : nullptr,
+                                 G::LDS_BYTES, nblk);
+    if (e != hipSuccess)
+        return e;
+    /* chunks of C tiles go round the blocks: C = 1 (tile-interleaved) unless asked otherwise */
     if (many && nmany > 1)
         nblk = (nblk + nmany - 1) / nmany;        /* the streams of a round share the CUs */
-    if (max_blocks > 0 && nblk > max_blocks)
-        nblk = max_blocks;
-    long long C = chunk > 0 ? chunk : FUSE2 ? (LAYOUT == 2 ? 8 : 4) : 1;
-    if (C > (ntiles + nblk - 1) / nblk)
-        C = (ntiles + nblk - 1) / nblk;
-    const long long nchunks = (ntiles + C - 1) / C;
-    const long long grid = nchunks < nblk ? nchunks : nblk;
+    i8x_walk(nblk, ntiles, max_blocks, chunk, FUSE2 ? (LAYOUT == 2 ? 8 : 4) : 1, grid, C);
     if (many && D == 8)
         hipLaunchKernelGGL((k_fir_i8x_many<HIST, MODE, FUSE2, LAYOUT>), dim3((unsigned)grid, (unsigned)nmany), dim3(768), G::LDS_BYTES, s,
                            *many, ntiles, (int)C);
@@ -1223,6 +1301,53 @@ hipError_t launch_fir_i8x_d10(const FirI8xArgs &a, hipStream_t s, int max_blocks
     return layout == 1   ? launch_fir_i8x_l<kFirI8xD10Hist, 2, false, 1, 10>(a, max_blocks, chunk, s)
            : layout == 2 ? launch_fir_i8x_l<kFirI8xD10Hist, 2, false, 2, 10>(a, max_blocks, chunk, s)
                          : launch_fir_i8x_l<kFirI8xD10Hist, 2, false, 0, 10>(a, max_blocks, chunk, s);
+}
+
+template <int HIST, int NCH>
+static hipError_t launch_fir_i8x_bank_l(const FirI8xBank &b, int max_blocks, int chunk, hipStream_t s)
+{
+    using G = i8x::Geo<HIST, 2, false>;
+    constexpr size_t lds = 12 * (size_t)G::PLANE + (size_t)NCH * G::NARR * G::AS * sizeof(float);
+    const long long ntiles = (b.a.n_in + i8x::TILE - 1) / i8x::TILE;
+    static int cus[64] = { 0 };
+    long long nblk = 0, grid = 0, C = 0;
+    const hipError_t e = i8x_cus(cus, reinterpret_cast<const void *>(&k_fir_i8x_bank<HIST, NCH>), nullptr, lds, nblk);
+    if (e != hipSuccess)
+        return e;
+    i8x_walk(nblk, ntiles, max_blocks, chunk, 1, grid, C);      /* launch_fir_i8x_l's walk: one block per CU, C = 1 */
+    hipLaunchKernelGGL((k_fir_i8x_bank<HIST, NCH>), dim3((unsigned)grid), dim3(768), lds, s, b, ntiles, (int)C);
+    return hipGetLastError();
+}
+
+hipError_t launch_fir_i8x_bank(const FirI8xBank &b, int nch, int hist, hipStream_t s, int max_blocks, int chunk)
+{
+    const FirI8xArgs &a = b.a;
+    if (a.n_in <= 0)
+        return hipSuccess;
+    if ((nch != 1 && nch != 2 && nch != 4) || (hist != 32 && hist != 64) || (a.n_in & 7) || !a.in || !a.hist)
+        return hipErrorInvalidValue;
+    for (int c = 0; c < nch; ++c)
+        if (!b.ch[c].atab || !b.ch[c].out || (b.ch[c].hist_out && a.n_in < hist))
+            return hipErrorInvalidValue;
+    if (nch == 1) {                                      /* one channel: the solo kernel itself */
+        FirI8xArgs q;
+        q.in = a.in;
+        q.hist = a.hist;
+        q.n_in = a.n_in;
+        q.atab = b.ch[0].atab;
+        q.out = b.ch[0].out;
+        q.hist_out = b.ch[0].hist_out;
+        q.scale = b.ch[0].scale;
+        q.ct[0] = b.ch[0].ct[0];
+        q.ct[1] = b.ch[0].ct[1];
+        q.n0 = b.ch[0].n0;
+        q.freg = b.ch[0].freg;
+        q.phase_off = b.ch[0].phase_off;
+        return launch_fir_i8x(q, hist, true, false, s, max_blocks, chunk, 0);
+    }
+    if (hist == 32)
+        return nch == 2 ? launch_fir_i8x_bank_l<32, 2>(b, max_blocks, chunk, s) : launch_fir_i8x_bank_l<32, 4>(b, max_blocks, chunk, s);
+    return nch == 2 ? launch_fir_i8x_bank_l<64, 2>(b, max_blocks, chunk, s) : launch_fir_i8x_bank_l<64, 4>(b, max_blocks, chunk, s);
 }
 
 hipError_t launch_fir_i8x_many(const FirI8xMany &m, int n, int hist, bool mix, bool fuse2, hipStream_t s, int max_blocks, int chunk,

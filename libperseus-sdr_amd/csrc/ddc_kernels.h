@@ -217,6 +217,29 @@ hipError_t launch_fir_i8x_many(const FirI8xMany &m, int n, int hist, bool mix, b
 hipError_t launch_fir_i8x(const FirI8xArgs &a, int hist, bool mix, bool fuse2, hipStream_t s, int max_blocks = 0, int chunk = 0,
                           int layout = -1 /* by form */);
 
+/* ---- the channel bank: up to kFirI8xBankMax tuned first stages (paired rows, hist 32 or 64, decimate by 8) from ONE read of
+ * the input -- one plane set per tile, every channel's matrix passes over it (k_fir_i8x_bank, ddc_fir_i8.hip).  The input,
+ * its history (the same bytes for every channel) and n_in are shared (FirI8xBank::a: in, hist, n_in; its other fields are
+ * not read); each channel has its own table, outputs, history out, constants and phase.  Each channel's outputs are the
+ * bits launch_fir_i8x gives for that channel alone. */
+constexpr int kFirI8xBankMax = 4;
+struct FirI8xBankCh {
+    const void *atab;        /* fir_i8x_build_tables, mix, hist 32 or 64: the paired [c ; s], [-s ; c] tables */
+    float      *out;         /* n_in / 8 float2                                                               */
+    void       *hist_out;    /* the batch's last hist samples (or NULL)                                       */
+    float       scale;
+    float       ct[2];
+    unsigned long long n0;
+    uint32_t    freg, phase_off;
+};
+struct FirI8xBank {
+    FirI8xArgs   a;
+    FirI8xBankCh ch[kFirI8xBankMax];
+};
+static_assert(sizeof(FirI8xBank) <= 4000, "FirI8xBank must fit the kernel-argument segment");
+/* nch = 1, 2 or 4 channels (1: launch_fir_i8x itself) */
+hipError_t launch_fir_i8x_bank(const FirI8xBank &b, int nch, int hist, hipStream_t s, int max_blocks = 0, int chunk = 0);
+
 /* k_fir8 with packed input does not scale the unpacked integers (value * 256): the taps of
  * that stage must be uploaded multiplied by this, RN(1/8388607) / 256 -- the factor that
  * k_unpack24 applies per sample (bit-exact with the reference there; here the FIR tolerance

@@ -166,6 +166,10 @@ struct pddc_pipeline {
     unsigned *d_flags = nullptr;
     /* gang submission (pddc_gang_push_async): several pipelines of one GPU share one launch chain */
     struct pddc_gang *gang = nullptr;        /* the gang whose stream the last push used (NULL: the pipeline's own)   */
+    /* bank (pddc_bank_*): the bank this pipeline belongs to, and a counter of everything that moved its stage-0 history
+     * (every batch, reset / seek, restore_state, set_taps on stage 0): the bank compares it with what it saw last    */
+    struct pddc_bank *bank = nullptr;
+    unsigned long long hist_ver = 0;
     /* kernel selection (pddc_pipeline_set_option; defaults = what the measurements chose; the environment is looked at
      * once, when the pipeline is created, never on the data path) */
     struct Opts {
@@ -237,6 +241,7 @@ static bool stage0_fused(const pddc_pipeline *p);
 static bool stage0_packed_generic(const pddc_pipeline *p);
 static int setup_stage3(pddc_pipeline *p);
 static int leave_gang(pddc_pipeline *p);
+static void leave_bank(pddc_pipeline *p);
 static float *direct_out(pddc_pipeline::HostSlot &sl, void *h_out);
 
 static float round_to_half(float v)
@@ -874,6 +879,7 @@ int pddc_pipeline_destroy(pddc_pipeline *p)
     hipSetDevice(p->device);
     hipDeviceSynchronize();
     (void)leave_gang(p);
+    leave_bank(p);
     for (int i = 0; i < PDDC_MAX_STAGES; ++i) {
         if (p->st[i].d_taps_base)
             hipFree(p->st[i].d_taps_base);
@@ -961,6 +967,7 @@ int pddc_pipeline_reset(pddc_pipeline *p)
     p->freg_applied = p->freg;
     compute_lo_steps(p);
     p->fresh = true;
+    ++p->hist_ver;
     p->carry_pending = false;                         /* a reset stream has no tail to finish */
     p->ov_parity = 0;
     p->segs.assign(1, pddc_pipeline::WordSeg{ 0, p->freg, 0u });      /* samples before the start are zeros */
@@ -1118,6 +1125,8 @@ int pddc_pipeline_set_taps(pddc_pipeline *p, int stage, const float *taps, int n
     if (p->carry_pending)
         return fail(PDDC_ESTATE, "overlap mode holds a tail back: pddc_pipeline_fence(p, stream) first");
     Stage &s = p->st[stage];
+    if (stage == 0)
+        ++p->hist_ver;                                /* (a bank takes the member alone for one round) */
     /* the history length is fixed at create time; a new tap set must fit it */
     const int need_hist = s.interp > 1 ? (ntaps + s.interp - 1) / s.interp : ntaps - 1;
     if (ntaps < 1 || need_hist > s.hist || (s.ntb && ntaps > 8 * s.ntb))
@@ -2176,6 +2185,23 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
     return PDDC_OK;
 }
 
+/* commit: every stage that had input has its new history; the stream moves on by the batch */
+static void commit_batch(pddc_pipeline *p, const BatchPlan &b)
+{
+    for (int i = 0; i < p->nstages; ++i) {
+        if (b.n_in[i] > 0)
+            p->st[i].cur ^= 1;
+        p->st[i].consumed += b.n_in[i];
+    }
+    p->n0 += b.n_in[0];
+    if (p->freg_applied != p->freg) {
+        p->freg_applied = p->freg;
+        compute_lo_steps(p);
+    }
+    p->fresh = false;
+    ++p->hist_ver;
+}
+
 /* pddc_pipeline_process, and for the gang (`gang` != NULL): the first launch is recorded there, not launched.  A batch the
  * gang cannot take (other plan shapes, the rare routes, gang_ok) answers 1 before anything has been queued or any stream
  * state has moved, and the gang runs it as a chain of its own.                                                      */
@@ -2244,17 +2270,7 @@ static int process_batch(pddc_pipeline *p, const void *d_packed, size_t nsamples
         p->carry_pending = true;
         p->ov_parity ^= 1;
     }
-    for (int i = 0; i < p->nstages; ++i) {  /* commit: every stage that had input has its new history */
-        if (b.n_in[i] > 0)
-            p->st[i].cur ^= 1;
-        p->st[i].consumed += b.n_in[i];
-    }
-    p->n0 += nsamples;
-    if (p->freg_applied != p->freg) {
-        p->freg_applied = p->freg;
-        compute_lo_steps(p);
-    }
-    p->fresh = false;
+    commit_batch(p, b);
     if (n_out_ret)
         *n_out_ret = n_final;
     return PDDC_OK;
@@ -2745,6 +2761,224 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
     return PDDC_OK;
 }
 
+/* ---- bank: several tuned receivers from one read of the same batch (include/perseus_ddc.h) --------------------------
+ * The members' first stages go through k_fir_i8x_bank in groups of 4 / 2 / 1 of one history length; every record is the
+ * one process_batch builds for the I8x route (build_first: the member's own tables, buffers, word and phase), the
+ * stages behind run through run_stage and the batch commits as in process_batch.  So a banked member is, bit for bit,
+ * the pipeline processed alone with no_fuse2 = 1 -- only its first launch is shared.                                 */
+struct pddc_bank {
+    int device = 0;
+    int n = 0;
+    pddc_pipeline *m[PDDC_BANK_MAX] = {};
+    bool detached = false;                          /* a member was destroyed before the bank */
+    /* per member: its hist_ver when the bank last saw it, and whether its stage-0 history was the bank's then */
+    unsigned long long ver[PDDC_BANK_MAX] = {};
+    bool al[PDDC_BANK_MAX] = {};
+};
+static_assert(kFirI8xBankMax == 4, "groups of 4 / 2 / 1");
+
+static void leave_bank(pddc_pipeline *p)
+{
+    pddc_bank *b = p->bank;
+    if (!b)
+        return;
+    for (int i = 0; i < b->n; ++i)
+        if (b->m[i] == p) {
+            b->m[i] = nullptr;
+            b->detached = true;
+        }
+    p->bank = nullptr;
+}
+
+/* can this member's batch take the bank kernel at all?  Its route would be k_fir_i8x alone (no_fuse2) on the tuned
+ * paired-rows form of hist 32 / 64, one word in its history window, nothing held back or measured, default options */
+static bool bank_eligible(const pddc_pipeline *p, size_t nsamples)
+{
+    const Stage &s0 = p->st[0];
+    if (!(p->flags & PDDC_F_MIX) || (p->flags & (PDDC_F_OUT_PACKED24 | PDDC_F_NO_FAST)))
+        return false;
+    if (s0.decim != 8 || s0.interp != 1 || (s0.hist != 32 && s0.hist != 64))
+        return false;
+    if (p->overlap || p->carry_pending || p->time_stage0 || p->fail_at_stage >= 0)
+        return false;
+    if (p->opt.i8x_blocks != 0 || p->opt.i8x_chunk != 0 || (p->opt.i8x_layout != -1 && p->opt.i8x_layout != 0))
+        return false;
+    return stage0_i8_kind_raw(p, nsamples) == 2;    /* (the matrix-core form, nsamples >= hist, one word in the window) */
+}
+
+/* the round's launches: groups[g] = member indices, banked in order; returns the number of groups */
+static int bank_plan(const pddc_bank *b, size_t nsamples, int groups[PDDC_BANK_MAX][kFirI8xBankMax], int gsize[PDDC_BANK_MAX],
+                     unsigned *mask)
+{
+    int ng = 0;
+    *mask = 0;
+    for (int hist : { 32, 64 }) {
+        int idx[PDDC_BANK_MAX], k = 0;
+        for (int i = 0; i < b->n; ++i) {
+            const pddc_pipeline *p = b->m[i];
+            if (p && p->st[0].hist == hist && b->al[i] && p->hist_ver == b->ver[i] && bank_eligible(p, nsamples))
+                idx[k++] = i;
+        }
+        for (int at = 0; at < k;) {
+            const int left = k - at, size = left >= 4 ? 4 : left >= 2 ? 2 : 1;
+            for (int c = 0; c < size; ++c) {
+                groups[ng][c] = idx[at + c];
+                *mask |= 1u << idx[at + c];
+            }
+            gsize[ng++] = size;
+            at += size;
+        }
+    }
+    return ng;
+}
+
+int pddc_bank_create(pddc_bank **out, int device, pddc_pipeline *const *members, int n)
+{
+    if (!out)
+        return fail(PDDC_EINVAL, "null argument");
+    *out = nullptr;
+    if (!members || n < 1 || n > PDDC_BANK_MAX)
+        return fail(PDDC_EINVAL, "bank: 1..%d members", PDDC_BANK_MAX);
+    for (int i = 0; i < n; ++i) {
+        if (!members[i])
+            return fail(PDDC_EINVAL, "bank member %d: null pipeline", i);
+        for (int j = 0; j < i; ++j)
+            if (members[j] == members[i])
+                return fail(PDDC_EINVAL, "bank members %d and %d: the same pipeline", j, i);
+    }
+    int rc = require_device();
+    if (rc)
+        return rc;
+    for (int i = 0; i < n; ++i) {
+        if (members[i]->device != device)
+            return fail(PDDC_EINVAL, "bank member %d: pipeline on GPU %d, bank on GPU %d", i, members[i]->device, device);
+        if (members[i]->bank)
+            return fail(PDDC_ESTATE, "bank member %d: already in a bank", i);
+    }
+    pddc_bank *b = new (std::nothrow) pddc_bank;
+    if (!b)
+        return fail(PDDC_ENOMEM, "out of memory");
+    b->device = device;
+    b->n = n;
+    for (int i = 0; i < n; ++i) {
+        pddc_pipeline *p = members[i];
+        b->m[i] = p;
+        b->ver[i] = p->hist_ver;
+        b->al[i] = p->fresh;                        /* fresh: zero history, the bank's before its first round */
+        p->bank = b;
+    }
+    *out = b;
+    return PDDC_OK;
+}
+
+int pddc_bank_destroy(pddc_bank *b)
+{
+    if (!b)
+        return PDDC_OK;
+    for (int i = 0; i < b->n; ++i)
+        if (b->m[i])
+            b->m[i]->bank = nullptr;
+    delete b;
+    return PDDC_OK;
+}
+
+int pddc_bank_schedule(const pddc_bank *b, size_t nsamples, unsigned *banked_mask, int *launches)
+{
+    if (!b || !banked_mask || !launches)
+        return fail(PDDC_EINVAL, "null argument");
+    int groups[PDDC_BANK_MAX][kFirI8xBankMax], gsize[PDDC_BANK_MAX];
+    *launches = b->detached || nsamples % PDDC_INPUT_GRANULE ? 0 : bank_plan(b, nsamples, groups, gsize, banked_mask);
+    if (*launches == 0)
+        *banked_mask = 0;
+    return PDDC_OK;
+}
+
+int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void *const *d_out, const size_t *out_capacity,
+                      size_t *n_out, int *n_banked, void *stream_v)
+{
+    if (n_banked)
+        *n_banked = 0;
+    if (!b || !d_out || !out_capacity || !n_out)
+        return fail(PDDC_EINVAL, "null argument");
+    if (b->detached)
+        return fail(PDDC_ESTATE, "bank: a member pipeline was destroyed before the bank");
+    if (nsamples % PDDC_INPUT_GRANULE)
+        return fail(PDDC_EINVAL, "nsamples (%zu) must be a multiple of %d", nsamples, PDDC_INPUT_GRANULE);
+    /* everything that can refuse the round is checked before anything is queued or any stream position moves */
+    if (nsamples && (!d_packed || ((uintptr_t)d_packed & 15)))
+        return fail(PDDC_EINVAL, "bank: null or unaligned input");
+    for (int i = 0; i < b->n; ++i) {
+        const pddc_pipeline *p = b->m[i];
+        n_out[i] = 0;
+        if (nsamples == 0)
+            continue;
+        if (!d_out[i] || ((uintptr_t)d_out[i] & 15))
+            return fail(PDDC_EINVAL, "bank member %d: null or unaligned output buffer", i);
+        if (p->carry_pending)
+            return fail(PDDC_ESTATE, "bank member %d: overlap mode holds a tail back (pddc_pipeline_fence first)", i);
+        const size_t need = predict_outputs(p, nsamples);
+        if (need > out_capacity[i])
+            return fail(PDDC_ECAPACITY, "bank member %d: output capacity %zu < %zu", i, out_capacity[i], need);
+    }
+    if (nsamples == 0)
+        return PDDC_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = (hipStream_t)stream_v;
+    int groups[PDDC_BANK_MAX][kFirI8xBankMax], gsize[PDDC_BANK_MAX];
+    unsigned mask = 0;
+    const int ng = bank_plan(b, nsamples, groups, gsize, &mask);
+    /* the banked members' first-stage records (the I8x route's, with their tables brought up to date on s) */
+    BatchPlan bp[PDDC_BANK_MAX];
+    FirstLaunch rec[PDDC_BANK_MAX];
+    int rc;
+    for (int i = 0; i < b->n; ++i) {
+        if (!(mask >> i & 1))
+            continue;
+        pddc_pipeline *p = b->m[i];
+        /* (what process_batch does first: drop the tuning-word segments that ended before the history window -- banked
+         * means one word in it, so the route stays I8x, but the segments kept are part of the stream state save_state
+         * writes) */
+        (void)mixed_history(p);
+        plan_batch(p, nsamples, bp[i]);
+        float *dst;
+        if ((rc = stage_dst(p, 0, bp[i], d_out[i], s, &dst)) || (rc = build_first(p, Route::I8x, bp[i], d_packed, dst, true, s, rec[i])))
+            return rc;
+    }
+    /* one launch per group: the input and its history once, every member its own channel */
+    for (int g = 0; g < ng; ++g) {
+        FirI8xBank fb;
+        fb.a = rec[groups[g][0]].ax;
+        for (int c = 0; c < gsize[g]; ++c) {
+            const FirI8xArgs &q = rec[groups[g][c]].ax;
+            fb.ch[c] = FirI8xBankCh{ q.atab, q.out, q.hist_out, q.scale, { q.ct[0], q.ct[1] }, q.n0, q.freg, q.phase_off };
+        }
+        HIP_TRY(launch_fir_i8x_bank(fb, gsize[g], rec[groups[g][0]].hist, s));
+    }
+    /* behind it, per member: the stages after the first, the commit -- process_batch's.  (A failure from here on -- a HIP
+     * error, or one an unbanked member's own process_batch reports, such as its overlap workspace -- leaves the members
+     * before it advanced: the header says so) */
+    for (int i = 0; i < b->n; ++i) {
+        pddc_pipeline *p = b->m[i];
+        if (mask >> i & 1) {
+            for (int k = 1; k < p->nstages; ++k)
+                if ((rc = run_stage(p, k, Route::I8x, bp[i], d_packed, d_out[i], s)))
+                    return rc;                      /* (members before this one have moved on: the stream is broken) */
+            commit_batch(p, bp[i]);
+            n_out[i] = bp[i].n_in[p->nstages];
+        } else if ((rc = process_batch(p, d_packed, nsamples, d_out[i], out_capacity[i], &n_out[i], s, nullptr))) {
+            return rc;
+        }
+    }
+    /* every member's stage-0 history is now the batch's last samples -- the bank's next history -- if the batch held that many */
+    for (int i = 0; i < b->n; ++i) {
+        b->ver[i] = b->m[i]->hist_ver;
+        b->al[i] = nsamples >= (size_t)b->m[i]->st[0].hist;
+    }
+    if (n_banked)
+        *n_banked = __builtin_popcount(mask);
+    return PDDC_OK;
+}
+
 int pddc_pipeline_push_host(pddc_pipeline *p, const void *h_packed, size_t nsamples, void *h_out,
                             size_t out_capacity, size_t *n_out_ret)
 {
@@ -2882,6 +3116,7 @@ int pddc_pipeline_restore_state(pddc_pipeline *p, const void *h_buf, size_t nbyt
     p->phase_off = h.phase_off;
     p->freg_applied = h.freg_applied;
     p->fresh = h.fresh != 0;
+    ++p->hist_ver;
     compute_lo_steps(p);
     return PDDC_OK;
 }
