@@ -363,17 +363,24 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
  * every round; members whose first stage is the tuned decimate-by-8 on the matrix cores (<= 64
  * taps: history 32 or 64) share its launch -- one read of the batch for up to four of them
  * (k_fir_i8x_bank) -- grouped by history length into launches of 4, 2 and 1 members (8 = 4 + 4,
- * 6 = 4 + 2, 3 = 2 + 1).  Everything behind the first stage runs per member as in
- * pddc_pipeline_process, and a banked member's outputs, histories, counters and save_state blob
- * are bit for bit what pddc_pipeline_process gives that pipeline alone with option no_fuse2 = 1.
- * Each member keeps its own plan, word, taps, options and buffers.
- * A member is banked in a round when its batch would take k_fir_i8x alone with one tuning word
- * in its history window (no retune inside it), no overlap mode, no packed output, no stage-0 timing
- * and default k_fir_i8x options -- and it is ALIGNED: its stage-0 history is the bank's (the last
- * samples of the previous round's batch, or zeros while every member is fresh).  A member is
- * aligned after create if it was fresh (created, reset or seek, nothing processed), and after
- * every round whose batch held at least its history length; anything done to it outside the
- * bank (process, push, reset, seek, restore_state, set_taps) makes it unaligned for one round.
+ * 6 = 4 + 2, 3 = 2 + 1).  Members whose first stage is the tuned decimate-by-10 on the matrix
+ * cores (the 1, 1.6 and 2 MS/s plans: history 48 or 56) share it in PAIRS: two members whose batch
+ * puts its first stage-0 output on the same decimation phase (0 .. 9) take one launch, the longer
+ * history first, whatever their histories; a member of a phase without a partner runs alone.
+ * Everything behind the first stage runs per member as in pddc_pipeline_process, and a banked
+ * member's outputs, histories, counters and save_state blob are bit for bit what
+ * pddc_pipeline_process gives that pipeline alone -- with option no_fuse2 = 1 for the
+ * decimate-by-8 members.  Each member keeps its own plan, word, taps, options and buffers.
+ * A member is banked in a round when its batch would take k_fir_i8x alone (decimate by 8), or the
+ * tuned decimate-by-10 form with at least one stage-0 output, with one tuning word in its history
+ * window (no retune inside it), no overlap mode, no packed output, no stage-0 timing or failure
+ * injection and default k_fir_i8x options -- and it is ALIGNED: its stage-0 history is the bank's
+ * (the last samples of the previous round's batch, or zeros while every member is fresh).  A member
+ * is aligned after create if it was fresh (created, reset or seek, nothing processed), and after
+ * every round whose batch held at least its history length (a decimate-by-10 member that was
+ * aligned stays so through a shorter one); anything done to it outside the bank (process, push,
+ * reset, seek, restore_state, set_taps) makes it unaligned for one round -- and a decimate-by-10
+ * member that processed a batch of its own may sit on another phase than its partner from then on.
  * Members that are not banked run pddc_pipeline_process on the same stream in the same round:
  * every member's output is correct in every round, only the sharing changes.
  * A pipeline belongs to at most one bank; destroy the bank before its members.  A member
@@ -395,7 +402,7 @@ int pddc_bank_destroy(pddc_bank *b);
 int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void *const *d_out,
                       const size_t *out_capacity, size_t *n_out, int *n_banked, void *stream);
 /* what the next round of nsamples would do: bit i set = member i shares a bank launch; *launches = bank launches
- * (a group of one is a launch of the solo kernel and counts) */
+ * (a decimate-by-8 group of one is a launch of the solo kernel and counts; a decimate-by-10 pair is one launch) */
 int pddc_bank_schedule(const pddc_bank *b, size_t nsamples, unsigned *banked_mask, int *launches);
 
 /* pinned host memory for the two calls above */

@@ -616,7 +616,9 @@ class Gang:
 
 class Bank:
     """pddc_bank: up to PDDC_BANK_MAX pipelines of one GPU fed the same batch every round; the tuned first stages of up to
-    four of them come from one read of it (include/perseus_ddc.h).  Destroy it before its pipelines."""
+    four of them come from one read of it (include/perseus_ddc.h).  Decimate-by-8 members (<= 64 taps) are grouped by
+    history length; decimate-by-10 members (the 1 / 1.6 / 2 MS/s plans) go in pairs of the same decimation phase, and one
+    without a partner runs alone.  Destroy it before its pipelines."""
 
     def __init__(self, pipes, device: int = 0):
         self.pipes = list(pipes)                  # (keeps the members alive as long as the bank)

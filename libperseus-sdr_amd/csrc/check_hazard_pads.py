@@ -17,7 +17,8 @@ silently; this script looks at the machine code instead:
   * LAYOUT 1 and 2 and the bank: every nontemporal result store (`global_store_dword[x2] ... nt`) is followed by `s_nop`, no global
     store at all is followed directly by a vector instruction, and there IS at least one such store (a kernel without
     any would pass the check by having lost what it checks).
-The bank's instantiations for 2 and 4 channels must be there, or the check fails.
+The bank's instantiations for 2 and 4 channels must be there, or the check fails.  `--list` names each bank kernel's
+history, channels and decimation (`checked: bank hist 64 nch 2 d 10 <symbol>`).
 usage: check_hazard_pads.py ddc_fir_i8.o [--arch gfx950] [--llvm-bin DIR] [--list]"""
 import os
 import re
@@ -26,7 +27,7 @@ import sys
 import tempfile
 
 NAME = re.compile(r"k_fir_i8x(?:_many)?ILi(\d+)ELi(\d)ELb([01])ELi(\d)E")
-BANK = re.compile(r"k_fir_i8x_bankILi(\d+)ELi(\d)E")
+BANK = re.compile(r"k_fir_i8x_bankILi(\d+)ELi(\d)E(?:Li(\d+)E)?")   # (no decimation argument: by 8)
 
 
 class ToolError(Exception):
@@ -92,7 +93,7 @@ def main(argv):
     for name, code in kernels.items():
         m, mb = NAME.search(name), BANK.search(name)
         if mb:
-            form = f"bank hist {mb.group(1)} nch {mb.group(2)}"
+            form = f"bank hist {mb.group(1)} nch {mb.group(2)} d {mb.group(3) or 8}"
             bank_nch.add(int(mb.group(2)))
         elif m:
             layout = int(m.group(4))

@@ -275,15 +275,17 @@ struct Roles {
  * NCH > 1 (k_fir_i8x_bank; tuned paired rows, layout 0 only): NCH channels over ONE plane set per tile.  Matrix wave w works
  * for channel w / (4 / NCH) -- `a` is that channel's record, the loaders get channel 0's -- and takes 2 NCH of the tile's 8
  * column blocks; each channel has ONE value array pair (no double buffer: 4 x 10 KB beside the planes' 109 KB), and the wave
- * finishes exactly the outputs it computed, so only its own LDS writes are read back and no other wave waits for them. */
+ * finishes exactly the outputs it computed, so only its own LDS writes are read back and no other wave waits for them.
+ * Decimate by 10 (D = 10): 2 channels only -- the planes of a 10240-sample tile take 136 KB, two value array pairs (20 KB)
+ * fit beside them in the CU's 160 KB, four (40 KB) do not. */
 template <int HIST, int MODE, bool FUSE2, int LAYOUT, int D = 8, int NCH = 1>
 __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long ntiles, int C, long long nblk, long long blk)
 {
     using namespace i8x;
     using G = Geo<HIST, MODE, FUSE2, D>;
     using R = Roles<LAYOUT, D>;
-    static_assert(NCH == 1 || (MODE == 2 && !FUSE2 && LAYOUT == 0 && D == 8 && (NCH == 2 || NCH == 4)),
-                  "the bank: tuned paired rows, decimate by 8, matrix waves finish, 2 or 4 channels");
+    static_assert(NCH == 1 || (MODE == 2 && !FUSE2 && LAYOUT == 0 && ((D == 8 && (NCH == 2 || NCH == 4)) || (D == 10 && NCH == 2))),
+                  "the bank: tuned paired rows, matrix waves finish; decimate by 8 with 2 or 4 channels, by 10 with 2");
     static_assert(12 * (size_t)G::PLANE + (size_t)NCH * G::NARR * G::AS * sizeof(float) <= 160 * 1024, "bank LDS");
     constexpr int TILE_S = G::TILE_S, NGRP = R::NGRP;
     constexpr bool PART = NGRP % R::NLT != 0;                  /* the last round of main groups is a partial one */
@@ -978,8 +980,10 @@ __global__ __launch_bounds__(768, 1) void k_fir_i8x_many(FirI8xMany m, long long
  * buffers do (40 KB), because each matrix wave reads back only what it wrote itself -- no wave waits for another's values,
  * and the tile keeps its ONE barrier.  Finishing straight from the accumulators would save the LDS round trip but needs
  * rows 0..7 (uI) and 8..15 (uQ) of a column brought together across lane halves, and a combine / rotation in another
- * order than the solo form's -- the outputs must be the solo form's bits, so the bank shares its finishing code instead. */
-template <int HIST, int NCH>
+ * order than the solo form's -- the outputs must be the solo form's bits, so the bank shares its finishing code instead.
+ * D = 10 (the tuned decimate-by-10 form, hist 64, NCH = 2): the same scheme on k_fir_i8x's 10240-sample tiles; the two
+ * channels share one decimation phase (in_off, n_out) and may differ in the history they keep (hist_len). */
+template <int HIST, int NCH, int D = 8>
 __global__ __launch_bounds__(768, 1) void k_fir_i8x_bank(FirI8xBank b, long long ntiles, int C)
 {
     /* the record through the scalar cache, the channel by a wave-uniform index (see k_fir_i8x_many) */
@@ -1000,15 +1004,24 @@ __global__ __launch_bounds__(768, 1) void k_fir_i8x_bank(FirI8xBank b, long long
     a.n0 = r.ch[ch].n0;
     a.freg = r.ch[ch].freg;
     a.phase_off = r.ch[ch].phase_off;
+    if (D == 10) {
+        /* decimate by 10: the group's one phase (every channel's windows end on in_off + 10 m, n_out of them), and the
+         * loaders read channel 0's history -- the longest; the other channels' taps are zero where it reaches further */
+        a.n_out = r.a.n_out;
+        a.in_off = r.a.in_off;
+        a.hist_len = r.ch[ch].hist_len;
+    }
     if (blockIdx.x == 0 && wave >= 4) {
-        /* the loaders write channel 0's next history (fir_i8x_block); the other channels get the same bytes here */
+        /* the loaders write channel 0's next history (fir_i8x_block); the other channels get their own last samples here
+         * (decimate by 8: the same HIST bytes; by 10: each its own hist_len) */
         const int lt = threadIdx.x - 256;
-        const uint4 *src = reinterpret_cast<const uint4 *>(static_cast<const uint8_t *>(a.in) + (a.n_in - HIST) * 6);
+        const int hl = D == 8 ? HIST : r.ch[1].hist_len;              /* (decimate by 10: channel 1 is the only other) */
+        const uint4 *src = reinterpret_cast<const uint4 *>(static_cast<const uint8_t *>(a.in) + (a.n_in - hl) * 6);
         for (int c = 1; c < NCH; ++c)
-            if (r.ch[c].hist_out && lt < HIST * 6 / 16)
+            if (r.ch[c].hist_out && lt < hl * 6 / 16)
                 static_cast<uint4 *>(r.ch[c].hist_out)[lt] = src[lt];
     }
-    fir_i8x_block<HIST, 2, false, 0, 8, NCH>(a, ntiles, C, (long long)gridDim.x, (long long)blockIdx.x);
+    fir_i8x_block<HIST, 2, false, 0, D, NCH>(a, ntiles, C, (long long)gridDim.x, (long long)blockIdx.x);
 }
 
 /* ---- host side: the tap operands ------------------------------------------------------------------------------------ */
@@ -1303,19 +1316,19 @@ hipError_t launch_fir_i8x_d10(const FirI8xArgs &a, hipStream_t s, int max_blocks
                          : launch_fir_i8x_l<kFirI8xD10Hist, 2, false, 0, 10>(a, max_blocks, chunk, s);
 }
 
-template <int HIST, int NCH>
+template <int HIST, int NCH, int D = 8>
 static hipError_t launch_fir_i8x_bank_l(const FirI8xBank &b, int max_blocks, int chunk, hipStream_t s)
 {
-    using G = i8x::Geo<HIST, 2, false>;
+    using G = i8x::Geo<HIST, 2, false, D>;
     constexpr size_t lds = 12 * (size_t)G::PLANE + (size_t)NCH * G::NARR * G::AS * sizeof(float);
-    const long long ntiles = (b.a.n_in + i8x::TILE - 1) / i8x::TILE;
+    const long long ntiles = D == 8 ? (b.a.n_in + i8x::TILE - 1) / i8x::TILE : (b.a.n_out + 1023) / 1024;
     static int cus[64] = { 0 };
     long long nblk = 0, grid = 0, C = 0;
-    const hipError_t e = i8x_cus(cus, reinterpret_cast<const void *>(&k_fir_i8x_bank<HIST, NCH>), nullptr, lds, nblk);
+    const hipError_t e = i8x_cus(cus, reinterpret_cast<const void *>(&k_fir_i8x_bank<HIST, NCH, D>), nullptr, lds, nblk);
     if (e != hipSuccess)
         return e;
     i8x_walk(nblk, ntiles, max_blocks, chunk, 1, grid, C);      /* launch_fir_i8x_l's walk: one block per CU, C = 1 */
-    hipLaunchKernelGGL((k_fir_i8x_bank<HIST, NCH>), dim3((unsigned)grid), dim3(768), lds, s, b, ntiles, (int)C);
+    hipLaunchKernelGGL((k_fir_i8x_bank<HIST, NCH, D>), dim3((unsigned)grid), dim3(768), lds, s, b, ntiles, (int)C);
     return hipGetLastError();
 }
 
@@ -1348,6 +1361,43 @@ hipError_t launch_fir_i8x_bank(const FirI8xBank &b, int nch, int hist, hipStream
     if (hist == 32)
         return nch == 2 ? launch_fir_i8x_bank_l<32, 2>(b, max_blocks, chunk, s) : launch_fir_i8x_bank_l<32, 4>(b, max_blocks, chunk, s);
     return nch == 2 ? launch_fir_i8x_bank_l<64, 2>(b, max_blocks, chunk, s) : launch_fir_i8x_bank_l<64, 4>(b, max_blocks, chunk, s);
+}
+
+hipError_t launch_fir_i8x_bank_d10(const FirI8xBank &b, int nch, hipStream_t s, int max_blocks, int chunk)
+{
+    const FirI8xArgs &a = b.a;
+    if (a.n_out <= 0)
+        return hipSuccess;
+    /* launch_fir_i8x_d10's checks on the shared part and on every channel; channel 0's history is the one the loaders read */
+    if ((nch != 1 && nch != 2) || (a.n_in & 7) || (a.in_off & 7) || a.in_off < 0 || !a.in || !a.hist ||
+        (long long)a.in_off - 7 + 10 * (a.n_out - 1) >= a.n_in)
+        return hipErrorInvalidValue;
+    for (int c = 0; c < nch; ++c) {
+        const FirI8xBankCh &h = b.ch[c];
+        if (!h.atab || !h.out || (h.hist_out && a.n_in < h.hist_len) || h.hist_len < 8 || (h.hist_len & 7) ||
+            h.hist_len > b.ch[0].hist_len || h.hist_len > kFirI8xD10Hist)
+            return hipErrorInvalidValue;
+    }
+    if (nch == 1) {                                      /* one channel: the solo kernel itself */
+        FirI8xArgs q;
+        q.in = a.in;
+        q.hist = a.hist;
+        q.n_in = a.n_in;
+        q.n_out = a.n_out;
+        q.in_off = a.in_off;
+        q.hist_len = b.ch[0].hist_len;
+        q.atab = b.ch[0].atab;
+        q.out = b.ch[0].out;
+        q.hist_out = b.ch[0].hist_out;
+        q.scale = b.ch[0].scale;
+        q.ct[0] = b.ch[0].ct[0];
+        q.ct[1] = b.ch[0].ct[1];
+        q.n0 = b.ch[0].n0;
+        q.freg = b.ch[0].freg;
+        q.phase_off = b.ch[0].phase_off;
+        return launch_fir_i8x_d10(q, s, max_blocks, chunk, 0);
+    }
+    return launch_fir_i8x_bank_l<kFirI8xD10Hist, 2, 10>(b, max_blocks, chunk, s);
 }
 
 hipError_t launch_fir_i8x_many(const FirI8xMany &m, int n, int hist, bool mix, bool fuse2, hipStream_t s, int max_blocks, int chunk,

@@ -221,14 +221,19 @@ hipError_t launch_fir_i8x(const FirI8xArgs &a, int hist, bool mix, bool fuse2, h
  * the input -- one plane set per tile, every channel's matrix passes over it (k_fir_i8x_bank, ddc_fir_i8.hip).  The input,
  * its history (the same bytes for every channel) and n_in are shared (FirI8xBank::a: in, hist, n_in; its other fields are
  * not read); each channel has its own table, outputs, history out, constants and phase.  Each channel's outputs are the
- * bits launch_fir_i8x gives for that channel alone. */
+ * bits launch_fir_i8x gives for that channel alone.
+ * The tuned decimate-by-10 form (launch_fir_i8x_bank_d10, 2 channels): the channels share one decimation phase -- a.in_off
+ * and a.n_out are read too -- and each keeps hist_len samples of history; a.hist holds channel 0's, which must be the
+ * longest (the others' taps are zero where it reaches further).  Each channel's outputs are launch_fir_i8x_d10's bits. */
 constexpr int kFirI8xBankMax = 4;
 struct FirI8xBankCh {
-    const void *atab;        /* fir_i8x_build_tables, mix, hist 32 or 64: the paired [c ; s], [-s ; c] tables */
-    float      *out;         /* n_in / 8 float2                                                               */
-    void       *hist_out;    /* the batch's last hist samples (or NULL)                                       */
+    const void *atab;        /* fir_i8x_build_tables, mix, hist 32 or 64: the paired [c ; s], [-s ; c] tables
+                              * (decimate by 10: fir_i8x_d10_build_tables)                                   */
+    float      *out;         /* n_in / 8 float2 (decimate by 10: a.n_out)                                     */
+    void       *hist_out;    /* the batch's last hist samples (decimate by 10: hist_len) (or NULL)            */
     float       scale;
     float       ct[2];
+    int         hist_len;    /* decimate by 10: samples of history this channel keeps (unread by 8)           */
     unsigned long long n0;
     uint32_t    freg, phase_off;
 };
@@ -237,8 +242,11 @@ struct FirI8xBank {
     FirI8xBankCh ch[kFirI8xBankMax];
 };
 static_assert(sizeof(FirI8xBank) <= 4000, "FirI8xBank must fit the kernel-argument segment");
+static_assert(offsetof(FirI8xBankCh, n0) == 40 && sizeof(FirI8xBankCh) == 56, "hist_len sits in what was padding");
 /* nch = 1, 2 or 4 channels (1: launch_fir_i8x itself) */
 hipError_t launch_fir_i8x_bank(const FirI8xBank &b, int nch, int hist, hipStream_t s, int max_blocks = 0, int chunk = 0);
+/* the tuned decimate-by-10 first stage: nch = 1 or 2 channels (1: launch_fir_i8x_d10 itself) */
+hipError_t launch_fir_i8x_bank_d10(const FirI8xBank &b, int nch, hipStream_t s, int max_blocks = 0, int chunk = 0);
 
 /* k_fir8 with packed input does not scale the unpacked integers (value * 256): the taps of
  * that stage must be uploaded multiplied by this, RN(1/8388607) / 256 -- the factor that

@@ -2762,10 +2762,11 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
 }
 
 /* ---- bank: several tuned receivers from one read of the same batch (include/perseus_ddc.h) --------------------------
- * The members' first stages go through k_fir_i8x_bank in groups of 4 / 2 / 1 of one history length; every record is the
- * one process_batch builds for the I8x route (build_first: the member's own tables, buffers, word and phase), the
- * stages behind run through run_stage and the batch commits as in process_batch.  So a banked member is, bit for bit,
- * the pipeline processed alone with no_fuse2 = 1 -- only its first launch is shared.                                 */
+ * The members' first stages go through k_fir_i8x_bank in groups of 4 / 2 / 1 of one history length (decimate by 8), or in
+ * pairs of one decimation phase (decimate by 10); every record is the one process_batch builds for the I8x or I8xD10 route
+ * (build_first: the member's own tables, buffers, word and phase), the stages behind run through run_stage and the batch
+ * commits as in process_batch.  So a banked member is, bit for bit, the pipeline processed alone (with no_fuse2 = 1 for
+ * decimate by 8: the I8xD10 route has no fused pair) -- only its first launch is shared.                              */
 struct pddc_bank {
     int device = 0;
     int n = 0;
@@ -2806,7 +2807,33 @@ static bool bank_eligible(const pddc_pipeline *p, size_t nsamples)
     return stage0_i8_kind_raw(p, nsamples) == 2;    /* (the matrix-core form, nsamples >= hist, one word in the window) */
 }
 
-/* the round's launches: groups[g] = member indices, banked in order; returns the number of groups */
+/* the same for the tuned decimate-by-10 first stage: exactly when the batch would take the I8xD10 route (at least one
+ * stage-0 output, one word in the history window), with bank_eligible's exclusions.  -> its first output's phase (0 .. 9),
+ * or -1 */
+static int bank_phase_d10(const pddc_pipeline *p, size_t nsamples)
+{
+    if (!(p->flags & PDDC_F_MIX) || (p->flags & (PDDC_F_OUT_PACKED24 | PDDC_F_NO_FAST)))
+        return -1;
+    if (p->overlap || p->carry_pending || p->time_stage0 || p->fail_at_stage >= 0)
+        return -1;
+    if (p->opt.i8x_blocks != 0 || p->opt.i8x_chunk != 0 || (p->opt.i8x_layout != -1 && p->opt.i8x_layout != 0))
+        return -1;
+    if (nsamples == 0 || choose_route(p, nsamples, false).route != Route::I8xD10)
+        return -1;
+    size_t off, n1;
+    unsigned long long m0;
+    stage_outputs(p->st[0].consumed, nsamples, p->st[0].decim, 1, &off, &m0, &n1);
+    return (int)off;
+}
+
+/* may member i share a launch this round: still the stream the bank saw last, and aligned */
+static bool bank_aligned(const pddc_bank *b, int i)
+{
+    return b->m[i] && b->al[i] && b->m[i]->hist_ver == b->ver[i];
+}
+
+/* the round's launches: groups[g] = member indices, banked in order (the decimate-by-8 groups, then the decimate-by-10
+ * pairs: channel 0 the member with the longer history, whose history the loaders read); returns the number of groups */
 static int bank_plan(const pddc_bank *b, size_t nsamples, int groups[PDDC_BANK_MAX][kFirI8xBankMax], int gsize[PDDC_BANK_MAX],
                      unsigned *mask)
 {
@@ -2827,6 +2854,21 @@ static int bank_plan(const pddc_bank *b, size_t nsamples, int groups[PDDC_BANK_M
             }
             gsize[ng++] = size;
             at += size;
+        }
+    }
+    /* decimate by 10: one launch reads one phase (in_off = first + delay), so members pair up by their batch's first-output
+     * phase; longer histories first, and a member left without a partner runs alone */
+    for (int phase = 0; phase < 10; ++phase) {
+        int idx[PDDC_BANK_MAX], k = 0;
+        for (int i = 0; i < b->n; ++i)
+            if (bank_aligned(b, i) && bank_phase_d10(b->m[i], nsamples) == phase)
+                idx[k++] = i;
+        std::stable_sort(idx, idx + k, [&](int x, int y) { return b->m[x]->st[0].hist > b->m[y]->st[0].hist; });
+        for (int at = 0; at + 1 < k; at += 2) {
+            groups[ng][0] = idx[at];
+            groups[ng][1] = idx[at + 1];
+            *mask |= 1u << idx[at] | 1u << idx[at + 1];
+            gsize[ng++] = 2;
         }
     }
     return ng;
@@ -2925,9 +2967,11 @@ int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void 
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream_v;
     int groups[PDDC_BANK_MAX][kFirI8xBankMax], gsize[PDDC_BANK_MAX];
-    unsigned mask = 0;
+    unsigned mask = 0, was_al = 0;
     const int ng = bank_plan(b, nsamples, groups, gsize, &mask);
-    /* the banked members' first-stage records (the I8x route's, with their tables brought up to date on s) */
+    for (int i = 0; i < b->n; ++i)
+        was_al |= (bank_aligned(b, i) ? 1u : 0u) << i;
+    /* the banked members' first-stage records (the I8x or I8xD10 route's, with their tables brought up to date on s) */
     BatchPlan bp[PDDC_BANK_MAX];
     FirstLaunch rec[PDDC_BANK_MAX];
     int rc;
@@ -2936,23 +2980,26 @@ int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void 
             continue;
         pddc_pipeline *p = b->m[i];
         /* (what process_batch does first: drop the tuning-word segments that ended before the history window -- banked
-         * means one word in it, so the route stays I8x, but the segments kept are part of the stream state save_state
-         * writes) */
+         * means one word in it, so the route stays I8x / I8xD10, but the segments kept are part of the stream state
+         * save_state writes) */
         (void)mixed_history(p);
         plan_batch(p, nsamples, bp[i]);
+        const Route route = p->st[0].decim == 10 ? Route::I8xD10 : Route::I8x;
         float *dst;
-        if ((rc = stage_dst(p, 0, bp[i], d_out[i], s, &dst)) || (rc = build_first(p, Route::I8x, bp[i], d_packed, dst, true, s, rec[i])))
+        if ((rc = stage_dst(p, 0, bp[i], d_out[i], s, &dst)) || (rc = build_first(p, route, bp[i], d_packed, dst, true, s, rec[i])))
             return rc;
     }
-    /* one launch per group: the input and its history once, every member its own channel */
+    /* one launch per group: the input and its history once, every member its own channel (decimate by 10: the pair's
+     * phase -- in_off, n_out -- and channel 0's history, the longer one, from fb.a) */
     for (int g = 0; g < ng; ++g) {
         FirI8xBank fb;
-        fb.a = rec[groups[g][0]].ax;
+        const FirstLaunch &r0 = rec[groups[g][0]];
+        fb.a = r0.ax;
         for (int c = 0; c < gsize[g]; ++c) {
             const FirI8xArgs &q = rec[groups[g][c]].ax;
-            fb.ch[c] = FirI8xBankCh{ q.atab, q.out, q.hist_out, q.scale, { q.ct[0], q.ct[1] }, q.n0, q.freg, q.phase_off };
+            fb.ch[c] = FirI8xBankCh{ q.atab, q.out, q.hist_out, q.scale, { q.ct[0], q.ct[1] }, q.hist_len, q.n0, q.freg, q.phase_off };
         }
-        HIP_TRY(launch_fir_i8x_bank(fb, gsize[g], rec[groups[g][0]].hist, s));
+        HIP_TRY(r0.route == Route::I8xD10 ? launch_fir_i8x_bank_d10(fb, gsize[g], s) : launch_fir_i8x_bank(fb, gsize[g], r0.hist, s));
     }
     /* behind it, per member: the stages after the first, the commit -- process_batch's.  (A failure from here on -- a HIP
      * error, or one an unbanked member's own process_batch reports, such as its overlap workspace -- leaves the members
@@ -2960,8 +3007,12 @@ int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void 
     for (int i = 0; i < b->n; ++i) {
         pddc_pipeline *p = b->m[i];
         if (mask >> i & 1) {
+            Stage &s0 = p->st[0];
+            if (nsamples < (size_t)s0.hist)         /* (decimate by 10: the kernel wrote no history -- build_first) */
+                HIP_TRY(launch_hist_update(s0.d_hist[s0.cur ^ 1], s0.d_hist[s0.cur], s0.hist, d_packed, (long long)nsamples,
+                                           s0.hist_elem, s));
             for (int k = 1; k < p->nstages; ++k)
-                if ((rc = run_stage(p, k, Route::I8x, bp[i], d_packed, d_out[i], s)))
+                if ((rc = run_stage(p, k, rec[i].route, bp[i], d_packed, d_out[i], s)))
                     return rc;                      /* (members before this one have moved on: the stream is broken) */
             commit_batch(p, bp[i]);
             n_out[i] = bp[i].n_in[p->nstages];
@@ -2969,10 +3020,13 @@ int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void 
             return rc;
         }
     }
-    /* every member's stage-0 history is now the batch's last samples -- the bank's next history -- if the batch held that many */
+    /* every member's stage-0 history is now the batch's last samples -- the bank's next history -- if the batch held that many.
+     * A decimate-by-10 member that was aligned also stays so through a shorter batch: its history is then the last samples
+     * of the bank's stream all the same (its rounds see batches of any multiple of 8 that walk the phase through 0 .. 9) */
     for (int i = 0; i < b->n; ++i) {
+        const bool kept = was_al >> i & 1 && b->m[i]->st[0].decim == 10;
         b->ver[i] = b->m[i]->hist_ver;
-        b->al[i] = nsamples >= (size_t)b->m[i]->st[0].hist;
+        b->al[i] = nsamples >= (size_t)b->m[i]->st[0].hist || kept;
     }
     if (n_banked)
         *n_banked = __builtin_popcount(mask);

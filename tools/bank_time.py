@@ -9,7 +9,11 @@ is timed from a kernel trace instead -- `--legs K LOG2` runs `steps` gang rounds
 the kernel writes device memory) and `steps` bank rounds of the same K members, under
 `rocprofv3 --kernel-trace -d DIR -o NAME -- ...`; `--summarize DB...` then prints per trace the gang's k_fir_i8x_many
 (one launch, the member as the grid's second dimension: K reads of the batch) against the bank's k_fir_i8x_bank launches
-of a round (median kernel time per round)."""
+of a round (median kernel time per round).
+--d10: the decimate-by-10 pairs instead -- K = 2, 4, 8 members of the drop-in API's 2, 1.6, 2, 1 MS/s plans (a 54 / 51 / 54 /
+49-tap tuned /10 first stage, hist 56 / 56 / 56 / 48, then /4, /5, /4, /8), one k_fir_i8x_bank<64, 2, 10> launch per pair,
+against K solo process() calls (the I8xD10 route: k_fir_i8x<64, 2, false, 0, 10> and the second stage, per member);
+with --rounds-only: bank rounds of K = 2 (--only-k) at 2^28 for a kernel trace."""
 import argparse
 import importlib
 import os
@@ -41,6 +45,19 @@ def members(k, ns, ntaps):
     return pipes, outs
 
 
+D10_CYCLE = [2000000, 1600000, 2000000, 1000000]
+
+
+def members_d10(k, ns):
+    pipes = []
+    for i in range(k):
+        p = pkg.Pipeline([(d, t) for d, t, _ in pkg.api_plan(D10_CYCLE[i % len(D10_CYCLE)])], mix=True)
+        p.set_freg(FREGS[i])
+        pipes.append(p)
+    outs = [torch.empty((p.max_output(ns) + 8, 2), dtype=torch.float32, device=dev) for p in pipes]
+    return pipes, outs
+
+
 def median_ms(fn, steps, st):
     for _ in range(3):
         fn()
@@ -57,10 +74,12 @@ def median_ms(fn, steps, st):
 
 
 def row(k, log2, steps, ntaps=48):
+    """ntaps 0: the decimate-by-10 members (members_d10)"""
     ns = 1 << log2
     st = torch.cuda.current_stream(dev)
     d_in = pkg.synth_lcg(6 * ns, 12345, 0, dev)
-    bp, bo = members(k, ns, ntaps)
+    make = (lambda k, ns: members_d10(k, ns)) if ntaps == 0 else (lambda k, ns: members(k, ns, ntaps))
+    bp, bo = make(k, ns)
     bank = pkg.Bank(bp)
     ptrs, caps = [o.data_ptr() for o in bo], [o.shape[0] for o in bo]
 
@@ -74,7 +93,7 @@ def row(k, log2, steps, ntaps=48):
     for p in bp:
         p.close()
     del bo
-    sp, so = members(k, ns, ntaps)
+    sp, so = make(k, ns)
 
     def solo_round():
         for p, o in zip(sp, so):
@@ -128,7 +147,7 @@ def summarize(dbs):
         c = sqlite3.connect(db)
         rows = c.execute("select name, grid_y, end - start from kernels order by start").fetchall()
         gang = [d for n, gy, d in rows if "k_fir_i8x_many" in n]
-        bank = [(int(re.search(r"k_fir_i8x_bank<\d+, (\d)>", n).group(1)), d) for n, gy, d in rows if "k_fir_i8x_bank" in n]
+        bank = [(int(re.search(r"k_fir_i8x_bank<\d+, (\d)(?:, \d+)?>", n).group(1)), d) for n, gy, d in rows if "k_fir_i8x_bank" in n]
         ks = {gy for n, gy, d in rows if "k_fir_i8x_many" in n}
         k = max(ks) if ks else 0
         per_round = []
@@ -152,12 +171,38 @@ def main():
     ap.add_argument("--max-log2", type=int, default=28)
     ap.add_argument("--only-k", type=int, default=0)
     ap.add_argument("--rounds-only", action="store_true")
+    ap.add_argument("--d10", action="store_true", help="the decimate-by-10 pairs (see the module's text)")
     a = ap.parse_args()
     if a.summarize:
         summarize(a.summarize)
         return
     if a.legs:
         legs(a.legs[0], a.legs[1], a.steps)
+        return
+    if a.d10 and a.rounds_only:
+        ns, k = 1 << 28, a.only_k or 2
+        bp, bo = members_d10(k, ns)
+        bank = pkg.Bank(bp)
+        d_in = pkg.synth_lcg(6 * ns, 12345, 0, dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        mask, launches = bank.schedule(ns)
+        for _ in range(a.steps):
+            _, nb = bank.process_ptr(d_in.data_ptr(), ns, [o.data_ptr() for o in bo], [o.shape[0] for o in bo], st)
+            assert nb == k, nb
+        torch.cuda.synchronize()
+        bank.close()
+        print(f"{a.steps} bank rounds, K = {k} decimate-by-10 members, 2^28 samples, {launches} bank launches per round")
+        return
+    if a.d10:
+        print(f"bank round vs K solo process() calls, decimate-by-10 members (2 / 1.6 / 2 / 1 MS/s plans), median of {a.steps}, ms")
+        print(f"{'K':>2} {'log2':>4} {'launches':>8} {'bank':>9} {'K solo':>9} {'ratio':>6} {'bank/K':>8}")
+        for k in [a.only_k] if a.only_k else [2, 4, 8]:
+            for log2 in (22, 24, 26, 28):
+                if log2 > a.max_log2:
+                    continue
+                r = row(k, log2, a.steps, ntaps=0)
+                print(f"{k:>2} {log2:>4} {r['launches']:>8} {r['bank_ms']:>9.4f} {r['solo_ms']:>9.4f} "
+                      f"{r['solo_ms'] / r['bank_ms']:>6.2f} {r['bank_ms'] / k:>8.4f}", flush=True)
         return
     if a.rounds_only:
         ns = 1 << 28
