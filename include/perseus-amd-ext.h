@@ -118,6 +118,20 @@ uint32_t perseus_amd_effective_batch(perseus_descr *descr);
  * next, paced stream at 2^22 again.  Not while streaming (PERSEUS_ASYNCSTARTED). */
 int perseus_amd_set_batch(perseus_descr *descr, uint32_t batch_samples);
 
+/* Panorama, DDC modes only (wire mode: PERSEUS_FNNOTAVAIL): the averaged power spectrum of the ADC-rate stream the
+ * receiver's GPU batches hold (include/perseus_ddc.h, pddc_spectrum_*: definition, sizes, flags).  Nothing in the reference
+ * corresponds to it.  enable: between perseus_open() and perseus_start_async_input() (PERSEUS_ASYNCSTARTED while
+ * streaming); nfft 1024 / 2048 / 4096 / 8192 with hop nfft or nfft/2 (else PERSEUS_ERRPARAM), nfft = 0 disables; window
+ * float[nfft], copied, NULL = periodic Hann; flags 0 or PDDC_SPEC_PEAK (0x1).  From the next start on every GPU batch of
+ * the receiver also goes through the receiver's own spectrum object, on the stream its kernels run on (a gang round: per
+ * member, on the gang's stream).  Disabled, a stream's launches and statistics are what they were without it.
+ * read: host buffers float[nfft] (either may be NULL; peak only with PDDC_SPEC_PEAK), *nsegments = segments accumulated
+ * since the last clear; clear != 0 zeroes sums and peak afterwards, the segment grid goes on.  From any thread while
+ * streaming (it waits for the batches submitted so far), and after the stream ended, until the next start, enable or
+ * close; PERSEUS_FNNOTAVAIL when no stream has run with the panorama enabled. */
+int perseus_amd_spectrum_enable(perseus_descr *descr, int nfft, int hop, const float *window, uint32_t flags);
+int perseus_amd_spectrum_read(perseus_descr *descr, float *sum, float *peak, uint64_t *nsegments, int clear);
+
 /* state introspection (for tests and tools) */
 uint32_t perseus_amd_get_freg(perseus_descr *descr);          /* NCO word, perseus-sdr.c:584 */
 int      perseus_amd_get_sampling_rate(perseus_descr *descr); /* selected rate in S/s, 0 if none */

@@ -405,6 +405,50 @@ int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void 
  * (a decimate-by-8 group of one is a launch of the solo kernel and counts; a decimate-by-10 pair is one launch) */
 int pddc_bank_schedule(const pddc_bank *b, size_t nsamples, unsigned *banked_mask, int *launches);
 
+/* ---- panorama: averaged power spectrum of the packed stream --------------------
+ * Stands in for NOTHING in the reference: the FPGA has no spectrum output and the reference's
+ * example clients compute none; a client that wants one works on the host from the callback
+ * buffers.  Here the packed ADC-rate samples are read once, as they lie in HBM (the same d_packed
+ * a pipeline or a bank reads), and no float copy of them is ever written.
+ *
+ * x[n] = I[n] + j Q[n], the float32 values of pddc_unpack24_f32, n counted since create / reset;
+ * w[0 .. N) the caller's real window, N = nfft in {1024, 2048, 4096, 8192}, hop = N or N/2.
+ * Segment s covers samples [s hop, s hop + N);  X_s[k] = sum_n w[n] x[s hop + n] exp(-2 pi i k n / N),
+ * k = 0 .. N-1, DC first (a tone exp(+2 pi i k0 n / N) lands in bin k0);
+ *   sum[k]  = sum over the COMPLETE segments of |X_s[k]|^2    (no normalisation: float full scale squared)
+ *   peak[k] = max over the same segments                        (PDDC_SPEC_PEAK)
+ * The segment grid belongs to the stream, not to the batch: the object carries the last
+ * N - hop + (length mod hop) packed samples (fewer than N) across process() calls, so the set of
+ * segments does not depend on how the stream is cut; a batch may be shorter than a segment.
+ * Sums are accumulated without atomics in an order fixed by the batch sizes: the same batches give
+ * the same bits (another cut of the same stream may differ in the last bits).
+ * Stream-ordered like pddc_pipeline_process: one stream per object, one thread at a time.
+ * process() queues two launches and moves the host-side counters only after both were accepted; a
+ * refused call (PDDC_EINVAL: nsamples not a multiple of 8, d_packed NULL or not 16-byte aligned)
+ * queues nothing.  Argument errors are answered before any device access; with good arguments and
+ * no device create answers PDDC_ENODEV. */
+typedef struct pddc_spectrum pddc_spectrum;
+#define PDDC_SPEC_PEAK 0x1u      /* also keep peak[k] */
+int pddc_spectrum_create(pddc_spectrum **out, int device, int nfft, int hop, const float *window /* [nfft], copied */,
+                         uint32_t flags);
+int pddc_spectrum_destroy(pddc_spectrum *s);
+int pddc_spectrum_reset(pddc_spectrum *s);       /* sums, peak, tail, sample counter; synchronises the device */
+int pddc_spectrum_process(pddc_spectrum *s, const void *d_packed, size_t nsamples, void *stream);
+/* what is accumulated since the last clear: d_sum / d_peak float32[nfft] on the device (either may be NULL; d_peak must
+ * be NULL without PDDC_SPEC_PEAK); *nsegments (host) is known from sizes alone, like process()'s *n_out; clear != 0
+ * zeroes sums and peak afterwards, in stream order -- the tail and the segment grid go on */
+int pddc_spectrum_read(pddc_spectrum *s, void *d_sum, void *d_peak, uint64_t *nsegments, int clear, void *stream);
+/* Every batch the pipeline is PUSHED from now on (pddc_pipeline_push_host_async / _push_synth_async, a gang round) also
+ * goes through `s`: the same device batch, on the stream the batch's kernels run on (the pipeline's own, or the gang's),
+ * so a pddc_spectrum_read on another stream comes after pddc_pipeline_wait.  s == NULL detaches.  The pipeline does not
+ * own `s`: detach or destroy the pipeline first.  pddc_pipeline_process itself is unchanged (the caller has d_packed). */
+int pddc_pipeline_attach_spectrum(pddc_pipeline *p, pddc_spectrum *s);
+/* segments the NEXT process() of nsamples completes */
+uint64_t pddc_spectrum_next_segments(const pddc_spectrum *s, size_t nsamples);
+/* the same without an object (host arithmetic, no device): segments completed by nsamples more samples of a stream
+ * that already holds samples_before; 0 for unsupported sizes */
+uint64_t pddc_spectrum_segments(int nfft, int hop, uint64_t samples_before, size_t nsamples);
+
 /* pinned host memory for the two calls above */
 int pddc_host_alloc(void **h_ptr, size_t nbytes);
 int pddc_host_free(void *h_ptr);

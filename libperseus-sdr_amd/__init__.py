@@ -180,6 +180,18 @@ def ddc_lib() -> C.CDLL:
     L.pddc_bank_process.restype = C.c_int
     L.pddc_bank_schedule.argtypes = [vp, sz, C.POINTER(C.c_uint), C.POINTER(C.c_int)]
     L.pddc_bank_schedule.restype = C.c_int
+    L.pddc_spectrum_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_uint32]
+    L.pddc_spectrum_create.restype = C.c_int
+    L.pddc_spectrum_destroy.argtypes = [vp]
+    L.pddc_spectrum_reset.argtypes = [vp]
+    L.pddc_spectrum_process.argtypes = [vp, vp, sz, vp]
+    L.pddc_spectrum_read.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64), C.c_int, vp]
+    for f in (L.pddc_spectrum_destroy, L.pddc_spectrum_reset, L.pddc_spectrum_process, L.pddc_spectrum_read):
+        f.restype = C.c_int
+    L.pddc_spectrum_next_segments.argtypes = [vp, sz]
+    L.pddc_spectrum_next_segments.restype = C.c_uint64
+    L.pddc_spectrum_segments.argtypes = [C.c_int, C.c_int, C.c_uint64, sz]
+    L.pddc_spectrum_segments.restype = C.c_uint64
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
     L.pddc_pipeline_time_stage0_inline.restype = C.c_int
@@ -652,6 +664,95 @@ class Bank:
     __del__ = close
 
 
+PDDC_SPEC_PEAK = 0x1
+
+
+def hann_window(nfft: int):
+    """The periodic Hann window, float32[nfft]: 0.5 - 0.5 cos(2 pi n / nfft) in double, rounded once."""
+    import numpy as np
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(nfft) / nfft)).astype(np.float32)
+
+
+def spectrum_dbfs(sum_, nsegments: int, window):
+    """10 log10(P / (nsegments (sum w)^2)): a full-scale complex tone on a bin centre reads 0 dBFS.  `sum_` a torch tensor
+    or an array (what Spectrum.read returns first), `window` the window the spectrum was made with.  -> numpy float64."""
+    import numpy as np
+    p = sum_.detach().cpu().numpy() if hasattr(sum_, "detach") else np.asarray(sum_)
+    w = np.asarray(window, dtype=np.float64)
+    ref = float(nsegments) * w.sum() ** 2
+    with np.errstate(divide="ignore"):
+        return 10.0 * np.log10(p.astype(np.float64) / ref)
+
+
+class Spectrum:
+    """pddc_spectrum: the panorama -- |FFT|^2 of windowed segments of the packed ADC-rate stream, summed (and optionally
+    peak-held) over the complete segments since the last clear (include/perseus_ddc.h).  nfft in 1024 / 2048 / 4096 / 8192,
+    hop nfft (default) or nfft/2, window float32[nfft] (default: periodic Hann).  The segment grid belongs to the stream:
+    batches may be cut anywhere on a multiple of 8 samples."""
+
+    def __init__(self, nfft: int, hop=None, window=None, device: int = 0, peak: bool = False):
+        import numpy as np
+        self.nfft, self.hop, self.device, self.peak = int(nfft), int(nfft if hop is None else hop), device, bool(peak)
+        if window is None:
+            if self.nfft <= 0:
+                raise PddcError(-1, "spectrum: nfft must be positive")
+            window = hann_window(self.nfft)
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float32).reshape(-1))
+        if w.size != self.nfft:
+            raise PddcError(-1, f"spectrum: window of {w.size} values for nfft {self.nfft}")
+        self.window = w
+        h = C.c_void_p()
+        check(ddc_lib().pddc_spectrum_create(C.byref(h), device, self.nfft, self.hop,
+                                             w.ctypes.data_as(C.POINTER(C.c_float)), PDDC_SPEC_PEAK if peak else 0))
+        self._h = h
+
+    def _stream(self, stream):
+        import torch
+        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+
+    def process(self, packed, nsamples=None, stream=None) -> int:
+        """One batch: a torch uint8 CUDA tensor of packed samples (or a device address with nsamples).  -> the segments
+        this batch completed."""
+        if hasattr(packed, "data_ptr"):
+            ptr = packed.data_ptr()
+            if nsamples is None:
+                nsamples = packed.numel() // 6
+        else:
+            ptr = int(packed)
+            if nsamples is None:
+                raise PddcError(-1, "spectrum: a device address needs nsamples")
+        L = ddc_lib()
+        n = int(L.pddc_spectrum_next_segments(self._h, nsamples))
+        check(L.pddc_spectrum_process(self._h, ptr, nsamples, self._stream(stream)))
+        return n
+
+    def read(self, clear: bool = False, stream=None):
+        """-> (sum float32[nfft], peak float32[nfft] or None, nsegments) accumulated since the last clear"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        s = torch.empty(self.nfft, dtype=torch.float32, device=dev)
+        p = torch.empty(self.nfft, dtype=torch.float32, device=dev) if self.peak else None
+        n = C.c_uint64()
+        check(ddc_lib().pddc_spectrum_read(self._h, s.data_ptr(), p.data_ptr() if self.peak else None, C.byref(n),
+                                           1 if clear else 0, self._stream(stream)))
+        return s, p, int(n.value)
+
+    def reset(self):
+        check(ddc_lib().pddc_spectrum_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            ddc_lib().pddc_spectrum_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def spectrum_segments(nfft: int, hop: int, samples_before: int, nsamples: int) -> int:
+    """pddc_spectrum_segments: host arithmetic, no device"""
+    return int(ddc_lib().pddc_spectrum_segments(nfft, hop, samples_before, nsamples))
+
+
 class PinnedBuffer:
     """nbytes of pinned host memory (pddc_host_alloc) viewed as a numpy uint8 array."""
 
@@ -762,6 +863,10 @@ def sdr_lib() -> C.CDLL:
     L.perseus_open.argtypes = [C.c_int]
     L.perseus_open.restype = vp
     L.perseus_close.argtypes = [vp]
+    L.perseus_amd_spectrum_enable.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_uint32]
+    L.perseus_amd_spectrum_enable.restype = C.c_int
+    L.perseus_amd_spectrum_read.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.c_int]
+    L.perseus_amd_spectrum_read.restype = C.c_int
     L.perseus_firmware_download.argtypes = [vp, C.c_char_p]
     L.perseus_get_product_id.argtypes = [vp, C.POINTER(EepromProdId)]
     L.perseus_set_attenuator.argtypes = [vp, C.c_uint8]

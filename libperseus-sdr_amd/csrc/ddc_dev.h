@@ -17,6 +17,17 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+/* 3 dwords (12 bytes) = 2 packed samples -> MSB-aligned int32 (value * 256) I0, Q0, I1, Q1: the byte selectors of
+ * k_unpack24's unpack8_msb (ddc_kernels.hip), one v_perm_b32 per component */
+__device__ __forceinline__ void unpack2_msb(uint32_t a, uint32_t b, uint32_t c, int32_t &i0, int32_t &q0, int32_t &i1,
+                                            int32_t &q1)
+{
+    i0 = (int32_t)__builtin_amdgcn_perm(a, a, 0x0201000cu);   /* bytes 0..2  */
+    q0 = (int32_t)__builtin_amdgcn_perm(b, a, 0x0504030cu);   /* bytes 3..5  */
+    i1 = (int32_t)__builtin_amdgcn_perm(c, b, 0x0403020cu);   /* bytes 6..8  */
+    q1 = (int32_t)(c & 0xffffff00u);                          /* bytes 9..11 */
+}
+
 /* exp(-j*2*pi*phase/2^32) from the exact 32-bit phase: quadrant reduction in
  * integers, then minimax polynomials on [-pi/4, pi/4] (abs error < 1e-7). */
 __device__ __forceinline__ void nco_lo(uint32_t phase, float &c, float &s)

@@ -169,6 +169,7 @@ struct pddc_pipeline {
     /* bank (pddc_bank_*): the bank this pipeline belongs to, and a counter of everything that moved its stage-0 history
      * (every batch, reset / seek, restore_state, set_taps on stage 0): the bank compares it with what it saw last    */
     struct pddc_bank *bank = nullptr;
+    struct pddc_spectrum *spectrum = nullptr;   /* pddc_pipeline_attach_spectrum: every pushed batch goes through it too */
     unsigned long long hist_ver = 0;
     /* kernel selection (pddc_pipeline_set_option; defaults = what the measurements chose; the environment is looked at
      * once, when the pipeline is created, never on the data path) */
@@ -2429,6 +2430,8 @@ static int push_async(pddc_pipeline *p, const void *h_packed, bool synth, uint32
                                    direct ? out_capacity : sl.out_cap, &n_out, p->own_stream);
     if (rc)
         return rc;
+    if (p->spectrum && (rc = pddc_spectrum_process(p->spectrum, sl.d_in, nsamples, p->own_stream)))
+        return rc;
     if ((rc = pddc_pipeline_fence(p, p->own_stream)))     /* overlap mode: the D2H copy needs the tail's output */
         return rc;
     HIP_TRY(hipEventRecord(sl.ev_comp, p->own_stream));
@@ -2486,6 +2489,14 @@ int pddc_pipeline_wait_ticket(pddc_pipeline *p, int ticket)
     HIP_TRY(hipSetDevice(p->device));
     if (p->slot[ticket].ev_wait)
         HIP_TRY(hipEventSynchronize(p->slot[ticket].ev_wait));
+    return PDDC_OK;
+}
+
+int pddc_pipeline_attach_spectrum(pddc_pipeline *p, pddc_spectrum *s)
+{
+    if (!p)
+        return fail(PDDC_EINVAL, "null pipeline");
+    p->spectrum = s;
     return PDDC_OK;
 }
 
@@ -2739,6 +2750,13 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
         if (n_ganged)
             *n_ganged += k;
     }
+    /* a member's panorama reads the member's own device batch, on the gang's stream (nothing is shared between members) */
+    for (int i = 0; i < n; ++i)
+        if (items[i].pipe->spectrum) {
+            const int rc = pddc_spectrum_process(items[i].pipe->spectrum, items[i].pipe->slot[si[i]].d_in, nsamples, s);
+            if (rc)
+                return rc;
+        }
     /* the outputs leave, one event for the round: every member's ticket waits for it */
     hipEvent_t ev = g->ev[g->next_ev];
     g->next_ev = (g->next_ev + 1) & 3;

@@ -1,0 +1,451 @@
+/*
+ * ddc_spectrum.hip -- the panorama: averaged power spectrum of the packed ADC stream (gfx950 only).
+ *
+ *   k_spectrum<N, PEAK>   per segment of N samples: load packed (3 x global_load_dwordx4 per 8 samples), de-interleave
+ *                with v_perm, convert (bit-exact pddc_unpack24_f32 values), times the window, N-point transform inside
+ *                the workgroup (LDS + registers), |X|^2 added to per-thread per-bin sums.  No float copy of the input
+ *                ever reaches HBM: 6 B read per sample, 4*N (8*N with the peak hold) written per BLOCK.
+ *   k_spectrum_fold       second pass: the blocks' partial sums into the running sums (double, ascending block order),
+ *                the peak partials into the running peak, and the packed tail carried to the next batch.
+ *   k_spectrum_read       running sums -> float32 (and the optional clear).
+ *
+ * Transform: Stockham autosort, decimation in time, radices 16 * 16 * {4, 8, 16} (N = 1024, 2048, 4096) and
+ * 16 * 16 * 8 * 4 (N = 8192); a radix-R pass keeps a thread's R points in registers (radix 16 = 4 x 4, radix 8 = 4 x 2 with
+ * the constants of W16), so a segment crosses LDS once per pass.  A block has N/16 threads (at most 256).
+ *   pass p (sub-transforms of Ns done):  v[r] = in[j + r N/R] * W(Ns R)^(r k), k = j mod Ns;  FFT_R;
+ *                                        out[(j / Ns) Ns R + k + r Ns] = v[r]
+ * Natural order comes out of the last pass, whose outputs stay in registers: thread j holds bins j + r N/R.
+ * Twiddles: one table per pass, [r - 1][k], built on the host in double and rounded once; it lives in LDS beside the
+ * data for the whole (persistent) launch -- consecutive lanes read consecutive k, conflict free.  No device sine or cosine, no
+ * recurrence.
+ * LDS images: the loaders write 8 consecutive samples per lane (4 x ds_write_b128) and pass 1 writes 16 consecutive
+ * points per lane; both would put a lane group on one bank set, so both images are XOR-swizzled (swz0, swz1) such
+ * that the writes AND the stride-1 b64 reads of the next pass are conflict free.  The later images are plain.
+ * Bytes and registers per N: DESIGN.md 4 "Panorama".
+ *
+ * Walk: block b takes segments b, b + G, b + 2G, ... (G = grid) -- neighbouring blocks read neighbouring memory at
+ * any moment; the next segment's 48-byte groups are loaded into registers before the present one is transformed.
+ * Sums: a thread owns its bins for the whole launch, adds its segments in ascending order, and writes its row of the
+ * partial array once; the fold adds the rows in ascending order in double.  No atomics: the bits depend on
+ * (nseg, G) alone.
+ */
+#include "ddc_spectrum.h"
+#include "ddc_dev.h"
+
+#include <cmath>
+
+namespace pddc {
+
+static constexpr float kSpecUnpackScale = 0x1.000002p-31f;   /* as k_unpack24: (float)(v24 * 256) * this */
+
+template <int N> struct SpecPlan;
+template <> struct SpecPlan<1024> { static constexpr int NP = 3, R2 = 4, R3 = 1, BLOCKS_PER_CU = 8; };
+template <> struct SpecPlan<2048> { static constexpr int NP = 3, R2 = 8, R3 = 1, BLOCKS_PER_CU = 4; };
+template <> struct SpecPlan<4096> { static constexpr int NP = 3, R2 = 16, R3 = 1, BLOCKS_PER_CU = 2; };
+template <> struct SpecPlan<8192> { static constexpr int NP = 4, R2 = 8, R3 = 4, BLOCKS_PER_CU = 1; };
+
+/* radices of the passes of size n: 16, 16, r2[, r3] */
+static void spec_radices(int n, int (&r)[4], int &np)
+{
+    r[0] = r[1] = 16;
+    r[3] = 1;
+    np = 3;
+    switch (n) {
+    case 1024: r[2] = 4; break;
+    case 2048: r[2] = 8; break;
+    case 4096: r[2] = 16; break;
+    default: r[2] = 8; r[3] = 4; np = 4; break;
+    }
+}
+
+int spectrum_twiddle_len(int nfft)
+{
+    int r[4], np, ns = 16, len = 0;
+    spec_radices(nfft, r, np);
+    for (int p = 1; p < np; ++p) {
+        len += (r[p] - 1) * ns;
+        ns *= r[p];
+    }
+    return 2 * len;
+}
+
+void spectrum_build_twiddles(int nfft, float *tw)
+{
+    int r[4], np, ns = 16;
+    spec_radices(nfft, r, np);
+    size_t o = 0;
+    for (int p = 1; p < np; ++p) {
+        for (int q = 1; q < r[p]; ++q)
+            for (int k = 0; k < ns; ++k) {
+                const double a = -2.0 * M_PI * (double)((long long)q * k) / (double)(ns * r[p]);
+                tw[o++] = (float)cos(a);
+                tw[o++] = (float)sin(a);
+            }
+        ns *= r[p];
+    }
+}
+
+int spectrum_max_blocks(int nfft, int ncu)
+{
+    const int per = nfft == 1024 ? SpecPlan<1024>::BLOCKS_PER_CU
+                    : nfft == 2048 ? SpecPlan<2048>::BLOCKS_PER_CU
+                    : nfft == 4096 ? SpecPlan<4096>::BLOCKS_PER_CU
+                                   : SpecPlan<8192>::BLOCKS_PER_CU;
+    return per * ncu;
+}
+
+/* ------------------------------------------------------------------------ */
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 cmulw(float2 a, float2 w)
+{
+    return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
+}
+
+/* a * W16^M, M a compile-time constant: the trivial ones cost no multiply */
+template <int M> __device__ __forceinline__ float2 mul_w16(float2 a)
+{
+    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, H = 0.70710678118654752f;
+    if (M == 0)
+        return a;
+    if (M == 4)
+        return make_float2(a.y, -a.x);
+    if (M == 2)
+        return make_float2((a.x + a.y) * H, (a.y - a.x) * H);
+    if (M == 6)
+        return make_float2((a.y - a.x) * H, -(a.x + a.y) * H);
+    if (M == 1)
+        return cmulw(a, make_float2(C1, -S1));
+    if (M == 3)
+        return cmulw(a, make_float2(S1, -C1));
+    if (M == 9)
+        return cmulw(a, make_float2(-C1, S1));
+    return a;
+}
+
+/* 4-point transform in place, natural order */
+__device__ __forceinline__ void fft4(float2 &a0, float2 &a1, float2 &a2, float2 &a3)
+{
+    const float2 t0 = cadd(a0, a2), t1 = csub(a0, a2), t2 = cadd(a1, a3), t3 = csub(a1, a3);
+    a0 = cadd(t0, t2);
+    a2 = csub(t0, t2);
+    a1 = make_float2(t1.x + t3.y, t1.y - t3.x);
+    a3 = make_float2(t1.x - t3.y, t1.y + t3.x);
+}
+
+/* R-point transform of v[0 .. R) in registers; X[k] ends up in v[fft_pos<R>(k)] */
+template <int R> __device__ __forceinline__ constexpr int fft_pos(int k)
+{
+    return R == 16 ? 4 * (k & 3) + (k >> 2) : R == 8 ? 2 * (k & 3) + (k >> 2) : k;
+}
+
+template <int R> __device__ __forceinline__ void fft_reg(float2 (&v)[R]);
+template <> __device__ __forceinline__ void fft_reg<4>(float2 (&v)[4]) { fft4(v[0], v[1], v[2], v[3]); }
+template <> __device__ __forceinline__ void fft_reg<8>(float2 (&v)[8])
+{
+    /* n = 2 n1 + n2: two 4-point transforms over n1, W8^(n2 k1), four 2-point ones over n2 */
+    fft4(v[0], v[2], v[4], v[6]);
+    fft4(v[1], v[3], v[5], v[7]);
+    v[3] = mul_w16<2>(v[3]);
+    v[5] = mul_w16<4>(v[5]);
+    v[7] = mul_w16<6>(v[7]);
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) {
+        const float2 a = v[2 * k1], b = v[2 * k1 + 1];
+        v[2 * k1] = cadd(a, b);
+        v[2 * k1 + 1] = csub(a, b);
+    }
+}
+template <> __device__ __forceinline__ void fft_reg<16>(float2 (&v)[16])
+{
+    /* n = 4 n1 + n2: four 4-point transforms over n1 (A[n2][k1] at v[4 k1 + n2]), W16^(n2 k1), four over n2 */
+#pragma unroll
+    for (int n2 = 0; n2 < 4; ++n2)
+        fft4(v[n2], v[4 + n2], v[8 + n2], v[12 + n2]);
+    v[5] = mul_w16<1>(v[5]);
+    v[6] = mul_w16<2>(v[6]);
+    v[7] = mul_w16<3>(v[7]);
+    v[9] = mul_w16<2>(v[9]);
+    v[10] = mul_w16<4>(v[10]);
+    v[11] = mul_w16<6>(v[11]);
+    v[13] = mul_w16<3>(v[13]);
+    v[14] = mul_w16<6>(v[14]);
+    v[15] = mul_w16<9>(v[15]);
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1)
+        fft4(v[4 * k1], v[4 * k1 + 1], v[4 * k1 + 2], v[4 * k1 + 3]);
+}
+
+/* LDS images (indices in float2): 0 the loaders' (a lane writes 4 chunks of 16 B = samples 8g .. 8g+7: the chunk's
+ * low two bits XOR bits 1..2 of g), 1 pass 1's (a lane writes points 16j .. 16j+15: the low four bits XOR j's) */
+template <int SWZ> __device__ __forceinline__ int spec_swz(int i)
+{
+    return SWZ == 0 ? i ^ (((i >> 4) & 3) << 1) : SWZ == 1 ? i ^ ((i >> 4) & 15) : i;
+}
+
+/* one pass; LAST: the outputs go to the thread's sums instead of LDS (bin j + r N/R at acc[b * R + r]) */
+template <int N, int NT, int R, int NS, int SWZ_IN, int SWZ_OUT, bool LAST, bool PEAK, int NACC>
+__device__ __forceinline__ void spec_pass(float2 *buf, const float2 *tw, float (&acc)[NACC], float (&pk)[NACC])
+{
+    constexpr int NB = N / R / NT;
+    const int tid = threadIdx.x;
+    float2 v[NB][R];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = tid + b * NT;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            v[b][r] = buf[spec_swz<SWZ_IN>(j + r * (N / R))];
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = tid + b * NT;
+        if (NS > 1) {
+            const int k = j & (NS - 1);
+#pragma unroll
+            for (int r = 1; r < R; ++r)
+                v[b][r] = cmulw(v[b][r], tw[(r - 1) * NS + k]);
+        }
+        fft_reg<R>(v[b]);
+    }
+    if (LAST) {
+        static_assert(!LAST || NACC == NB * R, "a thread's bins");
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float2 x = v[b][fft_pos<R>(r)];
+                const float p = x.x * x.x + x.y * x.y;
+                acc[(b * R + r) % NACC] += p;
+                if (PEAK)
+                    pk[(b * R + r) % NACC] = fmaxf(pk[(b * R + r) % NACC], p);
+            }
+        __syncthreads();          /* the next segment's loaders write where this pass read */
+    } else {
+        __syncthreads();          /* everybody has read */
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int j = tid + b * NT;
+            const int k = j & (NS - 1);
+            const int j0 = (j - k) * R + k;
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                buf[spec_swz<SWZ_OUT>(j0 + r * NS)] = v[b][fft_pos<R>(r)];
+        }
+        __syncthreads();
+    }
+}
+
+template <int N, bool PEAK>
+__global__ __launch_bounds__(N / 16 < 256 ? N / 16 : 256) void k_spectrum(SpectrumArgs p)
+{
+    using Plan = SpecPlan<N>;
+    constexpr int NT = N / 16 < 256 ? N / 16 : 256;
+    constexpr int NG = N / 8 / NT;               /* 48-byte groups a thread loads per segment */
+    constexpr int NACC = N / NT;                 /* bins a thread owns */
+    constexpr int R2 = Plan::R2, R3 = Plan::R3;
+    constexpr int TW1 = 0, TW2 = 15 * 16, TW3 = TW2 + (R2 - 1) * 256, TWN = TW3 + (R3 > 1 ? (R3 - 1) * 256 * R2 : 0);
+    extern __shared__ __attribute__((aligned(16))) float2 spec_lds[];
+    float2 *buf = spec_lds;                      /* [N] */
+    float2 *tw = spec_lds + N;                   /* [TWN] */
+    const int tid = threadIdx.x;
+
+    for (int i = tid; i < TWN; i += NT)
+        tw[i] = reinterpret_cast<const float2 *>(p.twiddles)[i];
+    /* a thread's groups sit at the same place of every segment: its window values stay in registers */
+    float win[NG][8];
+#pragma unroll
+    for (int u = 0; u < NG; ++u) {
+        const f32x4 *w = reinterpret_cast<const f32x4 *>(p.window + 8 * (tid + u * NT));
+        const f32x4 a = w[0], b = w[1];
+        win[u][0] = a.x; win[u][1] = a.y; win[u][2] = a.z; win[u][3] = a.w;
+        win[u][4] = b.x; win[u][5] = b.y; win[u][6] = b.z; win[u][7] = b.w;
+    }
+    float acc[NACC], pk[NACC];
+#pragma unroll
+    for (int i = 0; i < NACC; ++i)
+        acc[i] = pk[i] = 0.0f;
+
+    u32x4 raw[NG][3];
+    auto load_seg = [&](long long seg) {
+        const long long v0 = seg * p.hop;
+#pragma unroll
+        for (int u = 0; u < NG; ++u) {
+            const long long v = v0 + 8LL * (tid + u * NT);      /* tail_len is a multiple of 8: a group lies on one side */
+            const uint8_t *src = v < p.tail_len ? p.tail + v * 6 : p.batch + (v - p.tail_len) * 6;
+            const u32x4 *s = reinterpret_cast<const u32x4 *>(src);
+            raw[u][0] = __builtin_nontemporal_load(s);
+            raw[u][1] = __builtin_nontemporal_load(s + 1);
+            raw[u][2] = __builtin_nontemporal_load(s + 2);
+        }
+    };
+
+    long long seg = blockIdx.x;
+    if (seg < p.nseg)
+        load_seg(seg);
+    __syncthreads();                             /* the twiddles are in place */
+    for (; seg < p.nseg; seg += gridDim.x) {
+#pragma unroll
+        for (int u = 0; u < NG; ++u) {
+            const int g = tid + u * NT;
+            f32x4 o[4];
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                /* 12 bytes = 2 samples: I0 Q0 I1 Q1, MSB-aligned (value * 256) as k_unpack24 places them */
+                const uint32_t a = raw[u][(3 * h) >> 2][(3 * h) & 3], b = raw[u][(3 * h + 1) >> 2][(3 * h + 1) & 3],
+                               c = raw[u][(3 * h + 2) >> 2][(3 * h + 2) & 3];
+                int32_t i0, q0, i1, q1;
+                unpack2_msb(a, b, c, i0, q0, i1, q1);
+                o[h].x = ((float)i0 * kSpecUnpackScale) * win[u][2 * h];
+                o[h].y = ((float)q0 * kSpecUnpackScale) * win[u][2 * h];
+                o[h].z = ((float)i1 * kSpecUnpackScale) * win[u][2 * h + 1];
+                o[h].w = ((float)q1 * kSpecUnpackScale) * win[u][2 * h + 1];
+            }
+            f32x4 *dst = reinterpret_cast<f32x4 *>(buf);
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
+                dst[4 * g + (h ^ ((g >> 1) & 3))] = o[h];
+        }
+        if (seg + gridDim.x < p.nseg)
+            load_seg(seg + gridDim.x);
+        __syncthreads();
+        spec_pass<N, NT, 16, 1, 0, 1, false, PEAK>(buf, tw + TW1, acc, pk);
+        spec_pass<N, NT, 16, 16, 1, 2, false, PEAK>(buf, tw + TW1, acc, pk);
+        if (R3 > 1) {
+            spec_pass<N, NT, R2, 256, 2, 2, false, PEAK>(buf, tw + TW2, acc, pk);
+            spec_pass<N, NT, (R3 > 1 ? R3 : 4), 256 * R2, 2, 2, true, PEAK>(buf, tw + TW3, acc, pk);
+        } else {
+            spec_pass<N, NT, R2, 256, 2, 2, true, PEAK>(buf, tw + TW2, acc, pk);
+        }
+    }
+    /* the block's row of partial sums: thread j's bins are j + b NT + r N/R of the last pass */
+    constexpr int RL = R3 > 1 ? R3 : R2;
+    constexpr int NB = N / RL / NT;
+    float *ps = p.part_sum + (size_t)blockIdx.x * N;
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < RL; ++r) {
+            const int bin = tid + b * NT + r * (N / RL);
+            ps[bin] = acc[b * RL + r];
+            if (PEAK)
+                p.part_peak[(size_t)blockIdx.x * N + bin] = pk[b * RL + r];
+        }
+}
+
+/* ------------------------------------------------------------------------ */
+/* 256 threads: 32 bins x 8 slices of the partial rows; a slice adds its rows in ascending order, then slice 0 adds the
+ * eight slice sums in ascending order -- all in double.  Blocks past the bins carry the tail (16-byte copies). */
+__global__ __launch_bounds__(256) void k_spectrum_fold(SpectrumFoldArgs p)
+{
+    __shared__ double ssum[8][32];
+    __shared__ float speak[8][32];
+    const int nbin_blocks = p.nfft / 32;
+    if ((int)blockIdx.x < nbin_blocks) {
+        if (p.nparts == 0)
+            return;
+        const int kk = threadIdx.x & 31, sl = threadIdx.x >> 5;
+        const int bin = blockIdx.x * 32 + kk;
+        double s = 0.0;
+        float m = 0.0f;
+        for (int b = sl; b < p.nparts; b += 8) {
+            s += (double)p.part_sum[(size_t)b * p.nfft + bin];
+            if (p.part_peak)
+                m = fmaxf(m, p.part_peak[(size_t)b * p.nfft + bin]);
+        }
+        ssum[sl][kk] = s;
+        speak[sl][kk] = m;
+        __syncthreads();
+        if (sl == 0) {
+            double t = ssum[0][kk];
+            float mm = speak[0][kk];
+            for (int i = 1; i < 8; ++i) {
+                t += ssum[i][kk];
+                mm = fmaxf(mm, speak[i][kk]);
+            }
+            p.acc_sum[bin] += t;
+            if (p.part_peak)
+                p.acc_peak[bin] = fmaxf(p.acc_peak[bin], mm);
+        }
+        return;
+    }
+    /* new_tail[c] = (tail-then-batch)[keep_from*6/16 + c], 16-byte chunks: every length is a multiple of 8 samples = 48 B */
+    const long long nchunks = p.new_len * 6 / 16;
+    const long long tail_chunks = p.tail_len * 6 / 16, from = p.keep_from * 6 / 16;
+    const long long stride = (long long)(gridDim.x - nbin_blocks) * 256;
+    for (long long c = (long long)(blockIdx.x - nbin_blocks) * 256 + threadIdx.x; c < nchunks; c += stride) {
+        const long long v = from + c;
+        const u32x4 *src = v < tail_chunks ? reinterpret_cast<const u32x4 *>(p.tail) + v
+                                           : reinterpret_cast<const u32x4 *>(p.batch) + (v - tail_chunks);
+        reinterpret_cast<u32x4 *>(p.new_tail)[c] = *src;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_spectrum_read(int nfft, double *acc_sum, float *acc_peak, float *d_sum,
+                                                       float *d_peak, int clear)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= nfft)
+        return;
+    if (d_sum)
+        d_sum[k] = (float)acc_sum[k];
+    if (d_peak && acc_peak)
+        d_peak[k] = acc_peak[k];
+    if (clear) {
+        acc_sum[k] = 0.0;
+        if (acc_peak)
+            acc_peak[k] = 0.0f;
+    }
+}
+
+/* ------------------------------------------------------------------------ */
+template <int N, bool PEAK> static hipError_t launch_spectrum_t(const SpectrumArgs &a, int blocks, hipStream_t s)
+{
+    constexpr int NT = N / 16 < 256 ? N / 16 : 256;
+    const size_t lds = sizeof(float) * ((size_t)2 * N + (size_t)spectrum_twiddle_len(N));
+    static bool raised[64] = {};      /* (two threads may both set the attribute: the same value, harmless) */
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess)
+        return e;
+    if (!raised[dev & 63]) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spectrum<N, PEAK>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess)
+            return e;
+        raised[dev & 63] = true;
+    }
+    hipLaunchKernelGGL((k_spectrum<N, PEAK>), dim3((unsigned)blocks), dim3(NT), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_spectrum(int nfft, const SpectrumArgs &a, int blocks, hipStream_t s)
+{
+    const bool peak = a.part_peak != nullptr;
+    switch (nfft) {
+    case 1024: return peak ? launch_spectrum_t<1024, true>(a, blocks, s) : launch_spectrum_t<1024, false>(a, blocks, s);
+    case 2048: return peak ? launch_spectrum_t<2048, true>(a, blocks, s) : launch_spectrum_t<2048, false>(a, blocks, s);
+    case 4096: return peak ? launch_spectrum_t<4096, true>(a, blocks, s) : launch_spectrum_t<4096, false>(a, blocks, s);
+    case 8192: return peak ? launch_spectrum_t<8192, true>(a, blocks, s) : launch_spectrum_t<8192, false>(a, blocks, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_spectrum_fold(const SpectrumFoldArgs &a, hipStream_t s)
+{
+    const int nbin_blocks = a.nfft / 32;
+    const long long nchunks = a.new_len * 6 / 16;
+    const int copy_blocks = (int)((nchunks + 255) / 256 < 32 ? (nchunks + 255) / 256 : 32);
+    hipLaunchKernelGGL(k_spectrum_fold, dim3((unsigned)(nbin_blocks + copy_blocks)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_spectrum_read(int nfft, double *acc_sum, float *acc_peak, float *d_sum, float *d_peak, int clear,
+                                hipStream_t s)
+{
+    hipLaunchKernelGGL(k_spectrum_read, dim3((unsigned)((nfft + 255) / 256)), dim3(256), 0, s, nfft, acc_sum, acc_peak,
+                       d_sum, d_peak, clear);
+    return hipGetLastError();
+}
+
+} // namespace pddc

@@ -167,6 +167,12 @@ struct perseus_descr_ds {
     uint64_t retune_at[MAX_RETUNES];   /* first ADC sample of every tuning-word segment */
     uint32_t retune_word[MAX_RETUNES];
     int n_retunes;
+    /* panorama (perseus_amd_spectrum_enable): the settings, and the object of the current / last stream.  It outlives the
+     * stream so that a bounded run can be read after it ended; the next start, enable or close lets it go */
+    int spec_nfft, spec_hop;
+    uint32_t spec_flags;
+    float *spec_window;
+    pddc_spectrum *spec;
     pthread_mutex_t pump_lock;  /* held by the delivery thread while it works on this descriptor */
 };
 
@@ -1061,6 +1067,7 @@ static void *worker_fn(void *arg)
 void perseus_set_debug(int level) { perseus_dbg_level = level; }
 
 static uint32_t effective_batch(const perseus_descr *d);
+static void spec_drop(perseus_descr *d);
 
 static void default_config(perseus_descr *d)
 {
@@ -1227,6 +1234,7 @@ int perseus_close(perseus_descr *d)
         return errornone(0);
     if (d->streaming)
         perseus_stop_async_input(d);
+    spec_drop(d);
     d->is_open = 0;
     return errornone(0);
 }
@@ -1420,6 +1428,14 @@ int perseus_is_preserie(perseus_descr *d, int *flag)
     return errornone(0);
 }
 
+static void spec_drop(perseus_descr *d)
+{
+    if (d->spec) {
+        pddc_spectrum_destroy(d->spec);
+        d->spec = NULL;
+    }
+}
+
 static void free_stream(perseus_descr *d)
 {
     free(d->ring);
@@ -1441,7 +1457,7 @@ static void free_stream(perseus_descr *d)
     d->fifo_len = d->fifo_cap = d->fifo_rd = 0;
     memset(&d->os, 0, sizeof(d->os));
     if (d->pipe) {
-        pddc_pipeline_destroy(d->pipe);
+        pddc_pipeline_destroy(d->pipe);      /* (the panorama's object stays: perseus_amd_spectrum_read after the stream) */
         d->pipe = NULL;
     }
     if (d->fp) {
@@ -1534,6 +1550,15 @@ static int start_locked(perseus_descr *d, uint32_t buffersize, perseus_input_cal
             return errorset(PERSEUS_DEVCONF, "GPU pipeline creation failed (%d): %s", rc, pddc_last_error());
         }
         pddc_pipeline_set_freg(d->pipe, d->freg);
+        spec_drop(d);
+        if (d->spec_nfft) {
+            rc = pddc_spectrum_create(&d->spec, dev, d->spec_nfft, d->spec_hop, d->spec_window, d->spec_flags);
+            if (rc != PDDC_OK) {
+                free_stream(d);
+                return errorset(PERSEUS_DEVCONF, "panorama creation failed (%d): %s", rc, pddc_last_error());
+            }
+            pddc_pipeline_attach_spectrum(d->pipe, d->spec);
+        }
         d->batch_eff = effective_batch(d);                     /* (perseus_amd_effective_batch reports it while the stream runs) */
         d->out_cap = pddc_pipeline_max_output(d->pipe, d->batch_eff) + 8;
         /* the synthetic stream is generated on the GPU (bit-identical to the host loop,
@@ -1700,6 +1725,85 @@ int perseus_amd_set_batch(perseus_descr *d, uint32_t batch_samples)
         d->batch_auto = 0;
         d->cfg.batch_samples = batch_samples;
     }
+    return errornone(0);
+}
+
+int perseus_amd_spectrum_enable(perseus_descr *d, int nfft, int hop, const float *window, uint32_t flags)
+{
+    if (d == NULL)
+        return errorset(PERSEUS_NULLDESCR, "null descriptor");
+    if (!d->is_open)
+        return errorset(PERSEUS_DEVNOTOPEN, "device not open");
+    if (d->streaming)
+        return errorset(PERSEUS_ASYNCSTARTED, "cannot reconfigure while streaming");
+    if (d->cfg.mode == PERSEUS_AMD_MODE_WIRE)
+        return errorset(PERSEUS_FNNOTAVAIL, "the panorama needs a DDC mode (the wire mode has no GPU batch)");
+    if (nfft != 0 && ((nfft != 1024 && nfft != 2048 && nfft != 4096 && nfft != 8192) || (hop != nfft && hop != nfft / 2)))
+        return errorset(PERSEUS_ERRPARAM, "panorama: nfft %d (1024, 2048, 4096, 8192 or 0 = off), hop %d (nfft or nfft/2)", nfft, hop);
+    if (flags & ~PDDC_SPEC_PEAK)
+        return errorset(PERSEUS_ERRPARAM, "panorama: unknown flags 0x%x", flags);
+    spec_drop(d);
+    free(d->spec_window);
+    d->spec_window = NULL;
+    d->spec_nfft = d->spec_hop = 0;
+    d->spec_flags = 0;
+    if (nfft == 0)
+        return errornone(0);
+    d->spec_window = (float *)malloc(sizeof(float) * (size_t)nfft);
+    if (!d->spec_window)
+        return errorset(PERSEUS_NOMEM, "out of memory");
+    for (int n = 0; n < nfft; n++)          /* NULL: the periodic Hann window, in double, rounded once */
+        d->spec_window[n] = window ? window[n] : (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)n / (double)nfft));
+    d->spec_nfft = nfft;
+    d->spec_hop = hop;
+    d->spec_flags = flags;
+    return errornone(0);
+}
+
+int perseus_amd_spectrum_read(perseus_descr *d, float *sum, float *peak, uint64_t *nsegments, int clear)
+{
+    if (d == NULL)
+        return errorset(PERSEUS_NULLDESCR, "null descriptor");
+    const int on_worker = g_thread_on && pthread_equal(pthread_self(), g_thread);   /* (from a callback: the lock is ours) */
+    if (!on_worker)
+        pthread_mutex_lock(&d->pump_lock);
+    int rc = PDDC_OK, err = 0;
+    if (!d->spec)
+        err = 1;
+    else if (peak && !(d->spec_flags & PDDC_SPEC_PEAK))
+        err = 2;
+    else {
+        /* every batch submitted so far first, then the read-out (and the clear) on the null stream, finished before the
+         * delivery thread gets the descriptor back: stream order by waiting */
+        const size_t nb = sizeof(float) * (size_t)d->spec_nfft;
+        void *d_sum = NULL, *d_peak = NULL;
+        if (d->pipe)
+            rc = pddc_pipeline_wait(d->pipe);
+        if (rc == PDDC_OK)
+            rc = pddc_set_device(d->gpu_dev);
+        if (rc == PDDC_OK && sum)
+            rc = pddc_malloc(&d_sum, nb);
+        if (rc == PDDC_OK && peak)
+            rc = pddc_malloc(&d_peak, nb);
+        if (rc == PDDC_OK)
+            rc = pddc_spectrum_read(d->spec, d_sum, d_peak, nsegments, clear, NULL);
+        if (rc == PDDC_OK && sum)
+            rc = pddc_memcpy_d2h(sum, d_sum, nb, NULL);
+        if (rc == PDDC_OK && peak)
+            rc = pddc_memcpy_d2h(peak, d_peak, nb, NULL);
+        if (rc == PDDC_OK)
+            rc = pddc_stream_sync(NULL);
+        pddc_free(d_sum);
+        pddc_free(d_peak);
+    }
+    if (!on_worker)
+        pthread_mutex_unlock(&d->pump_lock);
+    if (err == 1)
+        return errorset(PERSEUS_FNNOTAVAIL, "no panorama: perseus_amd_spectrum_enable before the stream starts");
+    if (err == 2)
+        return errorset(PERSEUS_ERRPARAM, "panorama enabled without PDDC_SPEC_PEAK");
+    if (rc != PDDC_OK)
+        return errorset(PERSEUS_DEVCONF, "panorama read failed (%d): %s", rc, pddc_last_error());
     return errornone(0);
 }
 

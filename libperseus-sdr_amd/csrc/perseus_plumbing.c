@@ -29,6 +29,9 @@
  */
 #include "../../include/perseus-amd-ext.h"
 
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <fcntl.h>
 #include <pthread.h>
 #include <stdatomic.h>
@@ -141,9 +144,34 @@ static void *fifo_thread(void *arg)
 
 #define MAX_RX 8
 
+/* -P: the ten strongest bins of the run's panorama in dBFS (Hann window: 0 dBFS = a full-scale tone on a bin centre) */
+static void print_panorama(perseus_descr *d, int nfft)
+{
+    float *sum = (float *)malloc(sizeof(float) * (size_t)nfft);
+    uint64_t nseg = 0;
+    if (!sum || perseus_amd_spectrum_read(d, sum, NULL, &nseg, 0) < 0 || nseg == 0) {
+        fprintf(stderr, "panorama: %s\n", nseg == 0 && sum ? "no complete segment" : perseus_errorstr());
+        free(sum);
+        return;
+    }
+    const double ref = (double)nseg * (0.5 * nfft) * (0.5 * nfft);      /* (sum of the periodic Hann window)^2 = (N/2)^2 */
+    printf("panorama nfft=%d segments=%llu\n", nfft, (unsigned long long)nseg);
+    for (int r = 0; r < 10; r++) {
+        int best = 0;
+        for (int k = 1; k < nfft; k++)
+            if (sum[k] > sum[best])
+                best = k;
+        const int kk = best < nfft / 2 ? best : best - nfft;
+        printf("panorama bin %5d  %+12.1f Hz  %8.2f dBFS\n", best, 80e6 * kk / nfft,
+               sum[best] > 0 ? 10.0 * log10(sum[best] / ref) : -999.0);
+        sum[best] = -1.0f;
+    }
+    free(sum);
+}
+
 int main(int argc, char **argv)
 {
-    int rate = 95000, nb = 6, bs = 1024, dbg = 3, seconds = 10, as_float = 0, test_fe = 1, nrx = 1, multi = 0;
+    int rate = 95000, nb = 6, bs = 1024, dbg = 3, seconds = 10, as_float = 0, test_fe = 1, nrx = 1, multi = 0, pano = 0;
     long max_buffers = 0;
     int bench_w = -1, bench_k = 0;
     double freq = 7000000.0;
@@ -151,7 +179,7 @@ int main(int argc, char **argv)
     const char *fifo = NULL;
     pthread_t fifo_tid;
     int c;
-    while ((c = getopt(argc, argv, "s:n:b:d:t:o:f:m:F:N:B:pah")) != -1) {
+    while ((c = getopt(argc, argv, "s:n:b:d:t:o:f:m:F:N:B:P:pah")) != -1) {
         switch (c) {
         case 's': rate = atoi(optarg); break;
         case 'n': nb = atoi(optarg); break;
@@ -169,10 +197,11 @@ int main(int argc, char **argv)
                 return 2;
             }
             break;
+        case 'P': pano = atoi(optarg); break;             /* panorama of nfft points (DDC modes): the ten strongest bins at the end */
         case 'p': as_float = 1; break;
         case 'a': test_fe = 0; break;
         default:
-            fprintf(stderr, "usage: %s [-s rate] [-n nb] [-b bs] [-f hz] [-t sec] [-m buffers] [-o file] [-p] [-a] [-d dbg]\n",
+            fprintf(stderr, "usage: %s [-s rate] [-n nb] [-b bs] [-f hz] [-t sec] [-m buffers] [-o file] [-P nfft] [-p] [-a] [-d dbg]\n",
                     argv[0]);
             return 2;
         }
@@ -332,6 +361,10 @@ int main(int argc, char **argv)
     else if (strcmp(outname, "none") != 0)
         s.out = fopen(outname, "wb");
 
+    if (pano && perseus_amd_spectrum_enable(d, pano, pano, NULL, 0) < 0) {
+        fprintf(stderr, "-P %d: %s\n", pano, perseus_errorstr());
+        return 2;
+    }
     const int rc = perseus_start_async_input(d, (uint32_t)(nb * bs),
                                              (as_float || s.ddc) ? on_buffer_float : on_buffer_int32, &s);
     if (rc < 0) {
@@ -361,6 +394,8 @@ int main(int argc, char **argv)
         pthread_join(fifo_tid, NULL);
         unlink(fifo);
     }
+    if (pano)
+        print_panorama(d, pano);
     fprintf(stderr, "final NCO word: %u\n", perseus_amd_get_freg(d));
     if (s.out && s.out != stdout)
         fclose(s.out);
