@@ -449,6 +449,53 @@ uint64_t pddc_spectrum_next_segments(const pddc_spectrum *s, size_t nsamples);
  * that already holds samples_before; 0 for unsupported sizes */
 uint64_t pddc_spectrum_segments(int nfft, int hop, uint64_t samples_before, size_t nsamples);
 
+/* ---- channelizer: M uniform channels of the packed stream as time series --------
+ * Stands in for NOTHING in the reference either (the FPGA delivers one tuned channel).  All M
+ * equally spaced channels of the ADC-rate stream, each filtered by the caller's real prototype
+ * low-pass and decimated, as complex samples -- from ONE read of the packed batch (a polyphase
+ * filter bank by weighted overlap-add: the panorama's transform behind a longer, folded window).
+ *
+ * x[n] = I[n] + j Q[n], the float32 values of pddc_unpack24_f32, n counted since create / reset.
+ * M = nchan in {1024, 2048, 4096}; prototype w[0 .. L), real float32, L = proto_len = P M with
+ * P in {1, 2, 4, 8} taps per branch and L <= 16384; hop D in {M, M/2} (critically sampled /
+ * oversampled by 2).  Row s exists once sample s D + L - 1 is in the stream (zero history is NOT
+ * assumed: only complete windows, like the panorama's complete segments):
+ *   y[s][k] = sum_{n=0}^{L-1} w[n] x[s D + n] exp(-2 pi i k (s D + n) / M),     k = 0 .. M-1
+ * The phase is counted from the stream's sample 0, so channel k is a proper base-band series: a
+ * tone exp(+2 pi i k0 n / M) gives the constant sum(w) in channel k0, every row.  (With D = M/2
+ * the factor exp(-2 pi i k s D / M) is the sign (-1)^(k s).)  In the terms of a tuned pipeline:
+ * channel k is the decimate-by-D FIR h = [0, w[L-1], .., w[0]] behind the NCO word k 2^32 / M,
+ * output s + L/D of a stream with zero history.
+ * Channel range: only channels (first + i) mod M, i < count, are written; a row is `count`
+ * complex float32, interleaved (re, im), rows consecutive: out[s count + i].
+ * Stream semantics are the panorama's: the row grid belongs to the stream, the object carries the
+ * last (fewer than L) packed samples across process() calls, a batch may be shorter than L, and
+ * batches cut anywhere on a multiple of 8 samples give the same rows -- here the same BITS: a
+ * row's bits depend on (M, D, P, w, the samples) alone, not on the cut, the range or the launch.
+ * process() knows the row count from sizes alone, checks every argument before any device access
+ * and before anything is queued (PDDC_EINVAL: nsamples not a multiple of 8, d_packed NULL or not
+ * 16-byte aligned, d_out NULL or not 8-byte aligned when rows are due; PDDC_ECAPACITY:
+ * out_capacity_rows too small -- nothing queued, no state moved), and moves its counters only
+ * after every launch was accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * create: argument errors are answered before any device access; good arguments and no device:
+ * PDDC_ENODEV.  flags: 0 (reserved). */
+typedef struct pddc_channelizer pddc_channelizer;
+int pddc_channelizer_create(pddc_channelizer **out, int device, int nchan, int hop,
+                            const float *proto /* [proto_len], copied */, int proto_len, int first, int count,
+                            uint32_t flags);
+int pddc_channelizer_destroy(pddc_channelizer *c);
+int pddc_channelizer_reset(pddc_channelizer *c);      /* tail, sample and row counters; synchronises the device */
+/* one batch; d_out: out_capacity_rows rows of `count` complex float32; *n_rows (host, may be NULL) = rows written */
+int pddc_channelizer_process(pddc_channelizer *c, const void *d_packed, size_t nsamples, void *d_out,
+                             size_t out_capacity_rows, size_t *n_rows, void *stream);
+/* another channel range, from the next process() on (the rows go on without a gap) */
+int pddc_channelizer_set_range(pddc_channelizer *c, int first, int count);
+/* rows the NEXT process() of nsamples writes */
+uint64_t pddc_channelizer_next_rows(const pddc_channelizer *c, size_t nsamples);
+/* the same without an object (host arithmetic, no device): rows completed by nsamples more samples of a stream that
+ * already holds samples_before; 0 for unsupported sizes */
+uint64_t pddc_channelizer_rows(int nchan, int hop, int proto_len, uint64_t samples_before, size_t nsamples);
+
 /* pinned host memory for the two calls above */
 int pddc_host_alloc(void **h_ptr, size_t nbytes);
 int pddc_host_free(void *h_ptr);

@@ -192,6 +192,19 @@ def ddc_lib() -> C.CDLL:
     L.pddc_spectrum_next_segments.restype = C.c_uint64
     L.pddc_spectrum_segments.argtypes = [C.c_int, C.c_int, C.c_uint64, sz]
     L.pddc_spectrum_segments.restype = C.c_uint64
+    L.pddc_channelizer_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int,
+                                          C.c_int, C.c_uint32]
+    L.pddc_channelizer_destroy.argtypes = [vp]
+    L.pddc_channelizer_reset.argtypes = [vp]
+    L.pddc_channelizer_process.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), vp]
+    L.pddc_channelizer_set_range.argtypes = [vp, C.c_int, C.c_int]
+    for f in (L.pddc_channelizer_create, L.pddc_channelizer_destroy, L.pddc_channelizer_reset,
+              L.pddc_channelizer_process, L.pddc_channelizer_set_range):
+        f.restype = C.c_int
+    L.pddc_channelizer_next_rows.argtypes = [vp, sz]
+    L.pddc_channelizer_next_rows.restype = C.c_uint64
+    L.pddc_channelizer_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, sz]
+    L.pddc_channelizer_rows.restype = C.c_uint64
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
     L.pddc_pipeline_time_stage0_inline.restype = C.c_int
@@ -751,6 +764,96 @@ class Spectrum:
 def spectrum_segments(nfft: int, hop: int, samples_before: int, nsamples: int) -> int:
     """pddc_spectrum_segments: host arithmetic, no device"""
     return int(ddc_lib().pddc_spectrum_segments(nfft, hop, samples_before, nsamples))
+
+
+def channelizer_prototype(nchan: int, taps_per_branch: int, beta: float = 8.0):
+    """A default prototype low-pass for Channelizer: Kaiser-windowed sinc of length taps_per_branch * nchan, cutoff
+    fs / (2 nchan) (a channel's half spacing), computed in double, scaled to unity DC gain (sum w = 1) and rounded once
+    to float32.  With one tap per branch the sinc's main lobe spans the whole window: the bank then is little more than a
+    Kaiser-windowed transform.  -> numpy float32[taps_per_branch * nchan]."""
+    import numpy as np
+    n = int(nchan) * int(taps_per_branch)
+    if n <= 0:
+        raise PddcError(-1, "channelizer_prototype: nchan and taps_per_branch must be positive")
+    t = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    w = np.sinc(t / nchan) * np.kaiser(n, float(beta))
+    return (w / w.sum()).astype(np.float32)
+
+
+class Channelizer:
+    """pddc_channelizer: all nchan (1024 / 2048 / 4096) equally spaced channels of the packed ADC-rate stream as complex
+    time series, from one read of the batch (include/perseus_ddc.h).  proto: the real prototype low-pass, float32 of 1, 2,
+    4 or 8 times nchan taps, at most 16384 (channelizer_prototype gives a usable one); hop nchan (default) or nchan/2;
+    first / count: the channels (first + i) mod nchan, i < count, that are written (default: all).  The row grid belongs
+    to the stream: batches may be cut anywhere on a multiple of 8 samples, and give the same bits."""
+
+    def __init__(self, nchan: int, proto, hop=None, first: int = 0, count=None, device: int = 0):
+        import numpy as np
+        self.nchan, self.hop, self.device = int(nchan), int(nchan if hop is None else hop), device
+        self.first, self.count = int(first), int(self.nchan if count is None else count)
+        w = np.ascontiguousarray(np.asarray(proto, dtype=np.float32).reshape(-1))
+        self.proto = w
+        h = C.c_void_p()
+        check(ddc_lib().pddc_channelizer_create(C.byref(h), device, self.nchan, self.hop,
+                                                w.ctypes.data_as(C.POINTER(C.c_float)), w.size, self.first, self.count, 0))
+        self._h = h
+
+    def _stream(self, stream):
+        import torch
+        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+
+    def next_rows(self, nsamples: int) -> int:
+        """rows the next process() of nsamples writes (known from sizes alone)"""
+        return int(ddc_lib().pddc_channelizer_next_rows(self._h, nsamples))
+
+    def process(self, packed, nsamples=None, out=None, stream=None):
+        """One batch: a torch uint8 CUDA tensor of packed samples (or a device address with nsamples).  -> complex64
+        tensor [rows, count] (a view of `out`, a contiguous CUDA tensor of complex64 or float32 pairs, if given)."""
+        import torch
+        if hasattr(packed, "data_ptr"):
+            ptr = packed.data_ptr()
+            if nsamples is None:
+                nsamples = packed.numel() // 6
+        else:
+            ptr = int(packed)
+            if nsamples is None:
+                raise PddcError(-1, "channelizer: a device address needs nsamples")
+        L = ddc_lib()
+        rows = self.next_rows(nsamples) if nsamples % 8 == 0 else 0
+        if out is None:
+            out = torch.empty((rows, self.count), dtype=torch.complex64, device=torch.device("cuda", self.device))
+            cap = rows
+        else:
+            if not out.is_contiguous():
+                raise PddcError(-1, "channelizer: out must be contiguous")
+            if out.dtype != torch.complex64:
+                out = torch.view_as_complex(out.view(-1, 2))
+            out = out.view(-1)
+            cap = out.numel() // self.count
+        n = C.c_size_t()
+        check(L.pddc_channelizer_process(self._h, ptr, nsamples, out.data_ptr() if out.numel() else None, cap,
+                                         C.byref(n), self._stream(stream)))
+        return out.view(-1)[:n.value * self.count].view(n.value, self.count)
+
+    def set_range(self, first: int, count: int):
+        """another channel range, from the next process() on"""
+        check(ddc_lib().pddc_channelizer_set_range(self._h, first, count))
+        self.first, self.count = int(first), int(count)
+
+    def reset(self):
+        check(ddc_lib().pddc_channelizer_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            ddc_lib().pddc_channelizer_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def channelizer_rows(nchan: int, hop: int, proto_len: int, samples_before: int, nsamples: int) -> int:
+    """pddc_channelizer_rows: host arithmetic, no device"""
+    return int(ddc_lib().pddc_channelizer_rows(nchan, hop, proto_len, samples_before, nsamples))
 
 
 class PinnedBuffer:

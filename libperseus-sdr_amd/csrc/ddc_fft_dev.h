@@ -1,0 +1,212 @@
+/*
+ * ddc_fft_dev.h -- the in-workgroup Stockham transform shared by the panorama (ddc_spectrum.hip) and the channelizer
+ * (ddc_channelizer.hip): plans, register transforms, LDS images, one pass.  Internal; gfx950 only.
+ *
+ * Transform: Stockham autosort, decimation in time, radices 16 * 16 * {4, 8, 16} (N = 1024, 2048, 4096) and
+ * 16 * 16 * 8 * 4 (N = 8192); a radix-R pass keeps a thread's R points in registers (radix 16 = 4 x 4, radix 8 = 4 x 2 with
+ * the constants of W16), so a segment crosses LDS once per pass.  A block has N/16 threads (at most 256).
+ *   pass p (sub-transforms of Ns done):  v[r] = in[j + r N/R] * W(Ns R)^(r k), k = j mod Ns;  FFT_R;
+ *                                        out[(j / Ns) Ns R + k + r Ns] = v[r]
+ * Natural order comes out of the last pass, whose outputs stay in registers: thread j holds bins j + r N/R.
+ * Twiddles: one table per pass, [r - 1][k], built on the host in double and rounded once (spectrum_build_twiddles,
+ * ddc_spectrum.h).
+ */
+#ifndef PDDC_DDC_FFT_DEV_H
+#define PDDC_DDC_FFT_DEV_H
+
+#include "ddc_dev.h"
+
+namespace pddc {
+
+static constexpr float kSpecUnpackScale = 0x1.000002p-31f;   /* as k_unpack24: (float)(v24 * 256) * this */
+
+template <int N> struct SpecPlan;
+template <> struct SpecPlan<1024> { static constexpr int NP = 3, R2 = 4, R3 = 1, BLOCKS_PER_CU = 8; };
+template <> struct SpecPlan<2048> { static constexpr int NP = 3, R2 = 8, R3 = 1, BLOCKS_PER_CU = 4; };
+template <> struct SpecPlan<4096> { static constexpr int NP = 3, R2 = 16, R3 = 1, BLOCKS_PER_CU = 2; };
+template <> struct SpecPlan<8192> { static constexpr int NP = 4, R2 = 8, R3 = 4, BLOCKS_PER_CU = 1; };
+
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 cmulw(float2 a, float2 w)
+{
+    return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
+}
+
+/* a * W16^M, M a compile-time constant: the trivial ones cost no multiply */
+template <int M> __device__ __forceinline__ float2 mul_w16(float2 a)
+{
+    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, H = 0.70710678118654752f;
+    if (M == 0)
+        return a;
+    if (M == 4)
+        return make_float2(a.y, -a.x);
+    if (M == 2)
+        return make_float2((a.x + a.y) * H, (a.y - a.x) * H);
+    if (M == 6)
+        return make_float2((a.y - a.x) * H, -(a.x + a.y) * H);
+    if (M == 1)
+        return cmulw(a, make_float2(C1, -S1));
+    if (M == 3)
+        return cmulw(a, make_float2(S1, -C1));
+    if (M == 9)
+        return cmulw(a, make_float2(-C1, S1));
+    return a;
+}
+
+/* 4-point transform in place, natural order */
+__device__ __forceinline__ void fft4(float2 &a0, float2 &a1, float2 &a2, float2 &a3)
+{
+    const float2 t0 = cadd(a0, a2), t1 = csub(a0, a2), t2 = cadd(a1, a3), t3 = csub(a1, a3);
+    a0 = cadd(t0, t2);
+    a2 = csub(t0, t2);
+    a1 = make_float2(t1.x + t3.y, t1.y - t3.x);
+    a3 = make_float2(t1.x - t3.y, t1.y + t3.x);
+}
+
+/* R-point transform of v[0 .. R) in registers; X[k] ends up in v[fft_pos<R>(k)] */
+template <int R> __device__ __forceinline__ constexpr int fft_pos(int k)
+{
+    return R == 16 ? 4 * (k & 3) + (k >> 2) : R == 8 ? 2 * (k & 3) + (k >> 2) : k;
+}
+
+template <int R> __device__ __forceinline__ void fft_reg(float2 (&v)[R]);
+template <> __device__ __forceinline__ void fft_reg<4>(float2 (&v)[4]) { fft4(v[0], v[1], v[2], v[3]); }
+template <> __device__ __forceinline__ void fft_reg<8>(float2 (&v)[8])
+{
+    /* n = 2 n1 + n2: two 4-point transforms over n1, W8^(n2 k1), four 2-point ones over n2 */
+    fft4(v[0], v[2], v[4], v[6]);
+    fft4(v[1], v[3], v[5], v[7]);
+    v[3] = mul_w16<2>(v[3]);
+    v[5] = mul_w16<4>(v[5]);
+    v[7] = mul_w16<6>(v[7]);
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) {
+        const float2 a = v[2 * k1], b = v[2 * k1 + 1];
+        v[2 * k1] = cadd(a, b);
+        v[2 * k1 + 1] = csub(a, b);
+    }
+}
+template <> __device__ __forceinline__ void fft_reg<16>(float2 (&v)[16])
+{
+    /* n = 4 n1 + n2: four 4-point transforms over n1 (A[n2][k1] at v[4 k1 + n2]), W16^(n2 k1), four over n2 */
+#pragma unroll
+    for (int n2 = 0; n2 < 4; ++n2)
+        fft4(v[n2], v[4 + n2], v[8 + n2], v[12 + n2]);
+    v[5] = mul_w16<1>(v[5]);
+    v[6] = mul_w16<2>(v[6]);
+    v[7] = mul_w16<3>(v[7]);
+    v[9] = mul_w16<2>(v[9]);
+    v[10] = mul_w16<4>(v[10]);
+    v[11] = mul_w16<6>(v[11]);
+    v[13] = mul_w16<3>(v[13]);
+    v[14] = mul_w16<6>(v[14]);
+    v[15] = mul_w16<9>(v[15]);
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1)
+        fft4(v[4 * k1], v[4 * k1 + 1], v[4 * k1 + 2], v[4 * k1 + 3]);
+}
+
+/* LDS images (indices in float2): 0 the loaders' (a lane writes 4 chunks of 16 B = samples 8g .. 8g+7: the chunk's
+ * low two bits XOR bits 1..2 of g), 1 pass 1's (a lane writes points 16j .. 16j+15: the low four bits XOR j's).
+ * The loaders write 8 consecutive samples per lane (4 x ds_write_b128) and pass 1 writes 16 consecutive points per
+ * lane; both would put a lane group on one bank set, so both images are XOR-swizzled such that the writes AND the
+ * stride-1 b64 reads of the next pass are conflict free.  The later images are plain. */
+template <int SWZ> __device__ __forceinline__ int spec_swz(int i)
+{
+    return SWZ == 0 ? i ^ (((i >> 4) & 3) << 1) : SWZ == 1 ? i ^ ((i >> 4) & 15) : i;
+}
+
+/* one pass; LAST: the outputs go to the thread's sums instead of LDS (bin j + r N/R at acc[b * R + r]) */
+template <int N, int NT, int R, int NS, int SWZ_IN, int SWZ_OUT, bool LAST, bool PEAK, int NACC>
+__device__ __forceinline__ void spec_pass(float2 *buf, const float2 *tw, float (&acc)[NACC], float (&pk)[NACC])
+{
+    constexpr int NB = N / R / NT;
+    const int tid = threadIdx.x;
+    float2 v[NB][R];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = tid + b * NT;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            v[b][r] = buf[spec_swz<SWZ_IN>(j + r * (N / R))];
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = tid + b * NT;
+        if (NS > 1) {
+            const int k = j & (NS - 1);
+#pragma unroll
+            for (int r = 1; r < R; ++r)
+                v[b][r] = cmulw(v[b][r], tw[(r - 1) * NS + k]);
+        }
+        fft_reg<R>(v[b]);
+    }
+    if (LAST) {
+        static_assert(!LAST || NACC == NB * R, "a thread's bins");
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const float2 x = v[b][fft_pos<R>(r)];
+                const float p = x.x * x.x + x.y * x.y;
+                acc[(b * R + r) % NACC] += p;
+                if (PEAK)
+                    pk[(b * R + r) % NACC] = fmaxf(pk[(b * R + r) % NACC], p);
+            }
+        __syncthreads();          /* the next segment's loaders write where this pass read */
+    } else {
+        __syncthreads();          /* everybody has read */
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int j = tid + b * NT;
+            const int k = j & (NS - 1);
+            const int j0 = (j - k) * R + k;
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                buf[spec_swz<SWZ_OUT>(j0 + r * NS)] = v[b][fft_pos<R>(r)];
+        }
+        __syncthreads();
+    }
+}
+
+/* a pass between LDS images without the sums (the channelizer's passes before the last) */
+template <int N, int NT, int R, int NS, int SWZ_IN, int SWZ_OUT>
+__device__ __forceinline__ void spec_pass_mid(float2 *buf, const float2 *tw)
+{
+    float none[1], nonep[1];
+    spec_pass<N, NT, R, NS, SWZ_IN, SWZ_OUT, false, false, 1>(buf, tw, none, nonep);
+}
+
+/* the LAST pass handing the bins to a store instead of to the sums: f(bin, X[bin]) for the thread's bins
+ * j + b NT + r N/R, r outermost per b -- consecutive lanes hold consecutive bins */
+template <int N, int NT, int R, int NS, int SWZ_IN, class F>
+__device__ __forceinline__ void spec_pass_out(float2 *buf, const float2 *tw, F f)
+{
+    constexpr int NB = N / R / NT;
+    const int tid = threadIdx.x;
+    float2 v[NB][R];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = tid + b * NT;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            v[b][r] = buf[spec_swz<SWZ_IN>(j + r * (N / R))];
+    }
+    __syncthreads();              /* everybody has read: the next row's loaders may write while the stores go out */
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int j = tid + b * NT;
+        const int k = j & (NS - 1);
+#pragma unroll
+        for (int r = 1; r < R; ++r)
+            v[b][r] = cmulw(v[b][r], tw[(r - 1) * NS + k]);
+        fft_reg<R>(v[b]);
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            f(j + r * (N / R), v[b][fft_pos<R>(r)]);
+    }
+}
+
+} // namespace pddc
+#endif
