@@ -496,6 +496,60 @@ uint64_t pddc_channelizer_next_rows(const pddc_channelizer *c, size_t nsamples);
  * already holds samples_before; 0 for unsupported sizes */
 uint64_t pddc_channelizer_rows(int nchan, int hop, int proto_len, uint64_t samples_before, size_t nsamples);
 
+/* ---- tuner: many freely tuned narrowband receivers behind the channelizer --------
+ * K receivers, each with its own 32-bit NCO word, read the channelizer's rows on the device and
+ * give K narrowband complex series.  The channelizer: M = nchan, D = hop, prototype w[0 .. L),
+ * range first / count, b = log2 M, rows y[s][k], s counted from the stream's first row.  Receiver
+ * j with word F_j (frequency F_j fs / 2^32, the sign convention of pddc_nco_freg: a tone at that
+ * frequency comes out at 0 Hz):
+ *   channel  k_j = ((F_j + 2^(31-b)) mod 2^32) >> (32 - b)   (nearest centre, wrapping to 0 at the top)
+ *   residue  r_j = (int32)(F_j - (k_j << (32 - b))),   in [-2^(31-b), 2^(31-b))
+ *   phase    theta_j[s] = (r_j (s D) + phi_j) mod 2^32, all in unsigned 32-bit arithmetic (s D taken
+ *            mod 2^32); phi_j = 0 at create and reset
+ *   z_j[s]   = y[s][k_j] exp(-2 pi i theta_j[s] / 2^32)
+ *   out_j[m] = sum_{t<T} h[t] z_j[m R + T - 1 - t],   m = 0, 1, ..: it exists once row m R + T - 1 is
+ *            in the stream (complete windows only, no zero history).  h: real float32 low-pass of
+ *            T = ntaps taps, R = decim: both common to all receivers.  Output rate fs / (D R).
+ * This is the receiver tuned to F_j: z_j[s] = sum_n w[n] e^{+2 pi i r_j n / 2^32} x[s D + n]
+ * e^{-2 pi i (F_j (s D + n) + phi_j) / 2^32} -- the stream mixed with the accumulator F_j n + phi_j
+ * and filtered by the prototype shifted by r_j towards its channel centre.
+ * Retune: set_freq(j, F') takes effect at the next row the tuner is given, row s0.  The accumulator
+ * is continuous (the increment changes, never the phase): phi_j' = phi_j + (F_j - F') (s0 D) mod 2^32.
+ * Rows before s0 keep the z they had, so the first T - 1 outputs after a retune mix old and new
+ * tuning.  A word whose channel lies outside the channel range: PDDC_EINVAL, nothing changed.
+ * Stream semantics are the channelizer's: the tuner counts rows itself and must be given every row
+ * since create / reset, in order, as [nrows][count] complex float32 of the CURRENT range
+ * (set_range follows pddc_channelizer_set_range, between two batches); it carries what the next
+ * outputs need of the last rows (fewer than T per receiver) across process() calls; a batch may
+ * hold any number of rows, 0 included.  Output: out[j out_stride + m], complex float32, m counted
+ * from 0 in every call.  The bits of out_j[m] depend on (M, D, F_j and its retune history, h, R, the
+ * rows) alone: not on the cut into batches, K, j, the other receivers or the channel range.
+ * process() knows the output count from sizes alone, checks every argument before any device
+ * access and before anything is queued (PDDC_EINVAL: d_rows NULL or not 8-byte aligned when
+ * nrows > 0, d_out NULL or not 8-byte aligned when outputs are due; PDDC_ECAPACITY: out_stride
+ * smaller than the outputs due -- nothing queued, no state moved), and moves its counters only
+ * after every launch was accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * Limits: 1 <= nrx <= 1024, 1 <= ntaps <= 512, 1 <= decim <= 64, flags 0.  create: argument errors
+ * (a word outside the range among them) before any device access; good arguments, no device:
+ * PDDC_ENODEV. */
+typedef struct pddc_tuner pddc_tuner;
+int pddc_tuner_create(pddc_tuner **out, int device, int nchan, int hop, int first, int count,   /* the channelizer's */
+                      const uint32_t *freg /* [nrx], copied */, int nrx, const float *taps /* [ntaps], copied */,
+                      int ntaps, int decim, uint32_t flags);
+int pddc_tuner_destroy(pddc_tuner *t);
+int pddc_tuner_reset(pddc_tuner *t);                  /* row counter, carried rows, phase offsets; synchronises the device */
+int pddc_tuner_set_freq(pddc_tuner *t, int rx, uint32_t freg);
+int pddc_tuner_set_range(pddc_tuner *t, int first, int count);        /* every receiver must lie inside it */
+/* one batch of rows; *n_out (host, may be NULL) = outputs written per receiver */
+int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_out, size_t out_stride,
+                       size_t *n_out, void *stream);
+/* outputs per receiver the NEXT process() of nrows writes */
+uint64_t pddc_tuner_next_outputs(const pddc_tuner *t, size_t nrows);
+/* the same without an object (host arithmetic, no device); 0 for unsupported sizes */
+uint64_t pddc_tuner_outputs(int ntaps, int decim, uint64_t rows_before, size_t nrows);
+/* channel and residue of a word (host arithmetic, no device); either pointer may be NULL */
+int pddc_tuner_channel(int nchan, uint32_t freg, int *channel, int32_t *residue);
+
 /* pinned host memory for the two calls above */
 int pddc_host_alloc(void **h_ptr, size_t nbytes);
 int pddc_host_free(void *h_ptr);

@@ -205,6 +205,21 @@ def ddc_lib() -> C.CDLL:
     L.pddc_channelizer_next_rows.restype = C.c_uint64
     L.pddc_channelizer_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, sz]
     L.pddc_channelizer_rows.restype = C.c_uint64
+    L.pddc_tuner_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32),
+                                    C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_uint32]
+    L.pddc_tuner_destroy.argtypes = [vp]
+    L.pddc_tuner_reset.argtypes = [vp]
+    L.pddc_tuner_set_freq.argtypes = [vp, C.c_int, C.c_uint32]
+    L.pddc_tuner_set_range.argtypes = [vp, C.c_int, C.c_int]
+    L.pddc_tuner_process.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), vp]
+    L.pddc_tuner_channel.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int32)]
+    for f in (L.pddc_tuner_create, L.pddc_tuner_destroy, L.pddc_tuner_reset, L.pddc_tuner_set_freq,
+              L.pddc_tuner_set_range, L.pddc_tuner_process, L.pddc_tuner_channel):
+        f.restype = C.c_int
+    L.pddc_tuner_next_outputs.argtypes = [vp, sz]
+    L.pddc_tuner_next_outputs.restype = C.c_uint64
+    L.pddc_tuner_outputs.argtypes = [C.c_int, C.c_int, C.c_uint64, sz]
+    L.pddc_tuner_outputs.restype = C.c_uint64
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
     L.pddc_pipeline_time_stage0_inline.restype = C.c_int
@@ -854,6 +869,129 @@ class Channelizer:
 def channelizer_rows(nchan: int, hop: int, proto_len: int, samples_before: int, nsamples: int) -> int:
     """pddc_channelizer_rows: host arithmetic, no device"""
     return int(ddc_lib().pddc_channelizer_rows(nchan, hop, proto_len, samples_before, nsamples))
+
+
+def tuner_prototype(nchan: int, taps_per_branch: int, beta=None):
+    """A prototype low-pass for a Channelizer of hop nchan/2 that feeds a Tuner: Kaiser-windowed sinc of length
+    taps_per_branch * nchan with its cutoff (-6 dB) at fs / nchan, one channel spacing -- twice channelizer_prototype's,
+    which is 6 dB down exactly where a receiver midway between two centres sits.  The pass band then covers half a
+    spacing plus the receiver's half width, and the stop band starts where the row rate 2 fs / nchan folds back into
+    it (1.5 spacings minus that half width).  beta None: from Kaiser's estimate for a transition of 0.8 spacings,
+    A = 14.36 * 0.8 * taps_per_branch + 7.95 dB, beta = 0.1102 (A - 8.7) (A > 50) -- 4.98 / 10.0 for 4 / 8 taps per branch.
+    What it reaches for a receiver of half width 0.1 spacings (tests/test_tuner_cpu.py::test_design_helpers computes
+    it): the worst-placed receiver (half a spacing off its centre) sees 0.034 dB / 0.0002 dB of pass-band variation with
+    4 / 8 taps per branch where channelizer_prototype gives 6.1 / 12.7 dB, and everything that folds into it is 53.7 /
+    98.5 dB down (M = 1024; 4096 alike).  Double, sum 1, rounded once.  -> numpy float32[taps_per_branch * nchan]."""
+    import numpy as np
+    n = int(nchan) * int(taps_per_branch)
+    if n <= 0:
+        raise PddcError(-1, "tuner_prototype: nchan and taps_per_branch must be positive")
+    if beta is None:
+        a = 14.36 * 0.8 * taps_per_branch + 7.95
+        beta = 0.1102 * (a - 8.7) if a > 50 else 0.5842 * max(a - 21.0, 0.0) ** 0.4 + 0.07886 * max(a - 21.0, 0.0)
+    t = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    w = np.sinc(2.0 * t / nchan) * np.kaiser(n, float(beta))
+    return (w / w.sum()).astype(np.float32)
+
+
+def tuner_lowpass(ntaps: int, decim: int, cutoff=None, beta: float = 8.0):
+    """The Tuner's common low-pass on rows: Kaiser-windowed sinc of ntaps taps, -6 dB at `cutoff` cycles per row
+    (default 0.35 / decim: 70 % of the output rate's Nyquist frequency), double, sum 1, rounded once.
+    -> numpy float32[ntaps]."""
+    import numpy as np
+    ntaps, decim = int(ntaps), int(decim)
+    if ntaps <= 0 or decim <= 0:
+        raise PddcError(-1, "tuner_lowpass: ntaps and decim must be positive")
+    fc = 0.35 / decim if cutoff is None else float(cutoff)
+    t = np.arange(ntaps, dtype=np.float64) - (ntaps - 1) / 2.0
+    h = np.sinc(2.0 * fc * t) * np.kaiser(ntaps, float(beta))
+    return (h / h.sum()).astype(np.float32)
+
+
+def tuner_outputs(ntaps: int, decim: int, rows_before: int, nrows: int) -> int:
+    """pddc_tuner_outputs: host arithmetic, no device"""
+    return int(ddc_lib().pddc_tuner_outputs(ntaps, decim, rows_before, nrows))
+
+
+def tuner_channel(nchan: int, freg: int):
+    """pddc_tuner_channel: (channel, residue) of a 32-bit NCO word; host arithmetic, no device"""
+    k, r = C.c_int(), C.c_int32()
+    check(ddc_lib().pddc_tuner_channel(nchan, int(freg) & 0xFFFFFFFF, C.byref(k), C.byref(r)))
+    return int(k.value), int(r.value)
+
+
+class Tuner:
+    """pddc_tuner: len(freqs) narrowband receivers behind `channelizer` (its nchan, hop and channel range), each tuned
+    with its own 32-bit NCO word (pddc_nco_freg's convention), all filtered by the real low-pass `taps` on rows and
+    decimated by `decim`: output rate fs / (hop * decim) (include/perseus_ddc.h).  Feed it every batch of rows the
+    Channelizer returns, in order, on the same stream; after Channelizer.set_range call set_range here too.  Outputs
+    are bit-identical however the rows are cut into batches."""
+
+    def __init__(self, channelizer, freqs, taps, decim: int):
+        import numpy as np
+        ch = channelizer
+        self.nchan, self.hop, self.device = ch.nchan, ch.hop, ch.device
+        self.first, self.count = ch.first, ch.count
+        f = np.ascontiguousarray(np.asarray(freqs, dtype=np.uint64).reshape(-1) & 0xFFFFFFFF, dtype=np.uint32)
+        h = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1))
+        self.nrx, self.taps, self.decim = int(f.size), h, int(decim)
+        hd = C.c_void_p()
+        check(ddc_lib().pddc_tuner_create(C.byref(hd), self.device, self.nchan, self.hop, self.first, self.count,
+                                          f.ctypes.data_as(C.POINTER(C.c_uint32)), f.size,
+                                          h.ctypes.data_as(C.POINTER(C.c_float)), h.size, self.decim, 0))
+        self._h = hd
+
+    def _stream(self, stream):
+        import torch
+        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+
+    def next_outputs(self, nrows: int) -> int:
+        """outputs per receiver the next process() of nrows rows writes (known from sizes alone)"""
+        return int(ddc_lib().pddc_tuner_next_outputs(self._h, nrows))
+
+    def process(self, rows, nrows=None, out=None, stream=None):
+        """One batch of rows: the complex64 CUDA tensor [nrows, count] Channelizer.process returned (or a device
+        address with nrows).  -> complex64 [nrx, outputs] (a view of `out`, a contiguous CUDA tensor [nrx, capacity] of
+        complex64, if given: receiver j's series starts at out[j, 0])."""
+        import torch
+        if hasattr(rows, "data_ptr"):
+            if not rows.is_contiguous():
+                raise PddcError(-1, "tuner: rows must be contiguous")
+            if nrows is None:
+                nrows = (rows.numel() if rows.dtype == torch.complex64 else rows.numel() // 2) // self.count
+            ptr = rows.data_ptr() if nrows else None
+        else:
+            ptr = int(rows)
+            if nrows is None:
+                raise PddcError(-1, "tuner: a device address needs nrows")
+        n_due = self.next_outputs(nrows)
+        if out is None:
+            out = torch.empty((self.nrx, n_due), dtype=torch.complex64, device=torch.device("cuda", self.device))
+        elif out.dtype != torch.complex64 or out.dim() != 2 or out.shape[0] != self.nrx or not out.is_contiguous():
+            raise PddcError(-1, "tuner: out must be a contiguous complex64 tensor [nrx, capacity]")
+        n = C.c_size_t()
+        check(ddc_lib().pddc_tuner_process(self._h, ptr, nrows, out.data_ptr() if out.numel() else None, out.shape[1],
+                                           C.byref(n), self._stream(stream)))
+        return out[:, :n.value]
+
+    def set_freq(self, rx: int, freg: int):
+        """retune receiver rx from the next row on; the phase accumulator goes on without a step"""
+        check(ddc_lib().pddc_tuner_set_freq(self._h, rx, int(freg) & 0xFFFFFFFF))
+
+    def set_range(self, first: int, count: int):
+        """the Channelizer's new range (Channelizer.set_range), from the next process() on"""
+        check(ddc_lib().pddc_tuner_set_range(self._h, first, count))
+        self.first, self.count = int(first), int(count)
+
+    def reset(self):
+        check(ddc_lib().pddc_tuner_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            ddc_lib().pddc_tuner_destroy(self._h)
+            self._h = None
+
+    __del__ = close
 
 
 class PinnedBuffer:
