@@ -712,11 +712,40 @@ def spectrum_dbfs(sum_, nsegments: int, window):
         return 10.0 * np.log10(p.astype(np.float64) / ref)
 
 
-class Spectrum:
+def _packed_arg(kind, packed, nsamples):
+    """a torch uint8 CUDA tensor of packed samples, or a device address with nsamples -> (address, nsamples)"""
+    if hasattr(packed, "data_ptr"):
+        return packed.data_ptr(), packed.numel() // 6 if nsamples is None else nsamples
+    if nsamples is None:
+        raise PddcError(-1, f"{kind}: a device address needs nsamples")
+    return int(packed), nsamples
+
+
+class _StreamObject:
+    """What Spectrum, Channelizer and Tuner share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    _kind = ""
+
+    def _stream(self, stream):
+        import torch
+        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+
+    def reset(self):
+        check(getattr(ddc_lib(), f"pddc_{self._kind}_reset")(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(ddc_lib(), f"pddc_{self._kind}_destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Spectrum(_StreamObject):
     """pddc_spectrum: the panorama -- |FFT|^2 of windowed segments of the packed ADC-rate stream, summed (and optionally
     peak-held) over the complete segments since the last clear (include/perseus_ddc.h).  nfft in 1024 / 2048 / 4096 / 8192,
     hop nfft (default) or nfft/2, window float32[nfft] (default: periodic Hann).  The segment grid belongs to the stream:
     batches may be cut anywhere on a multiple of 8 samples."""
+    _kind = "spectrum"
 
     def __init__(self, nfft: int, hop=None, window=None, device: int = 0, peak: bool = False):
         import numpy as np
@@ -734,21 +763,10 @@ class Spectrum:
                                              w.ctypes.data_as(C.POINTER(C.c_float)), PDDC_SPEC_PEAK if peak else 0))
         self._h = h
 
-    def _stream(self, stream):
-        import torch
-        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-
     def process(self, packed, nsamples=None, stream=None) -> int:
         """One batch: a torch uint8 CUDA tensor of packed samples (or a device address with nsamples).  -> the segments
         this batch completed."""
-        if hasattr(packed, "data_ptr"):
-            ptr = packed.data_ptr()
-            if nsamples is None:
-                nsamples = packed.numel() // 6
-        else:
-            ptr = int(packed)
-            if nsamples is None:
-                raise PddcError(-1, "spectrum: a device address needs nsamples")
+        ptr, nsamples = _packed_arg(self._kind, packed, nsamples)
         L = ddc_lib()
         n = int(L.pddc_spectrum_next_segments(self._h, nsamples))
         check(L.pddc_spectrum_process(self._h, ptr, nsamples, self._stream(stream)))
@@ -764,16 +782,6 @@ class Spectrum:
         check(ddc_lib().pddc_spectrum_read(self._h, s.data_ptr(), p.data_ptr() if self.peak else None, C.byref(n),
                                            1 if clear else 0, self._stream(stream)))
         return s, p, int(n.value)
-
-    def reset(self):
-        check(ddc_lib().pddc_spectrum_reset(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            ddc_lib().pddc_spectrum_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 def spectrum_segments(nfft: int, hop: int, samples_before: int, nsamples: int) -> int:
@@ -795,12 +803,13 @@ def channelizer_prototype(nchan: int, taps_per_branch: int, beta: float = 8.0):
     return (w / w.sum()).astype(np.float32)
 
 
-class Channelizer:
+class Channelizer(_StreamObject):
     """pddc_channelizer: all nchan (1024 / 2048 / 4096) equally spaced channels of the packed ADC-rate stream as complex
     time series, from one read of the batch (include/perseus_ddc.h).  proto: the real prototype low-pass, float32 of 1, 2,
     4 or 8 times nchan taps, at most 16384 (channelizer_prototype gives a usable one); hop nchan (default) or nchan/2;
     first / count: the channels (first + i) mod nchan, i < count, that are written (default: all).  The row grid belongs
     to the stream: batches may be cut anywhere on a multiple of 8 samples, and give the same bits."""
+    _kind = "channelizer"
 
     def __init__(self, nchan: int, proto, hop=None, first: int = 0, count=None, device: int = 0):
         import numpy as np
@@ -813,10 +822,6 @@ class Channelizer:
                                                 w.ctypes.data_as(C.POINTER(C.c_float)), w.size, self.first, self.count, 0))
         self._h = h
 
-    def _stream(self, stream):
-        import torch
-        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
-
     def next_rows(self, nsamples: int) -> int:
         """rows the next process() of nsamples writes (known from sizes alone)"""
         return int(ddc_lib().pddc_channelizer_next_rows(self._h, nsamples))
@@ -825,14 +830,7 @@ class Channelizer:
         """One batch: a torch uint8 CUDA tensor of packed samples (or a device address with nsamples).  -> complex64
         tensor [rows, count] (a view of `out`, a contiguous CUDA tensor of complex64 or float32 pairs, if given)."""
         import torch
-        if hasattr(packed, "data_ptr"):
-            ptr = packed.data_ptr()
-            if nsamples is None:
-                nsamples = packed.numel() // 6
-        else:
-            ptr = int(packed)
-            if nsamples is None:
-                raise PddcError(-1, "channelizer: a device address needs nsamples")
+        ptr, nsamples = _packed_arg(self._kind, packed, nsamples)
         L = ddc_lib()
         rows = self.next_rows(nsamples) if nsamples % 8 == 0 else 0
         if out is None:
@@ -854,16 +852,6 @@ class Channelizer:
         """another channel range, from the next process() on"""
         check(ddc_lib().pddc_channelizer_set_range(self._h, first, count))
         self.first, self.count = int(first), int(count)
-
-    def reset(self):
-        check(ddc_lib().pddc_channelizer_reset(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            ddc_lib().pddc_channelizer_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 def channelizer_rows(nchan: int, hop: int, proto_len: int, samples_before: int, nsamples: int) -> int:
@@ -920,12 +908,13 @@ def tuner_channel(nchan: int, freg: int):
     return int(k.value), int(r.value)
 
 
-class Tuner:
+class Tuner(_StreamObject):
     """pddc_tuner: len(freqs) narrowband receivers behind `channelizer` (its nchan, hop and channel range), each tuned
     with its own 32-bit NCO word (pddc_nco_freg's convention), all filtered by the real low-pass `taps` on rows and
     decimated by `decim`: output rate fs / (hop * decim) (include/perseus_ddc.h).  Feed it every batch of rows the
     Channelizer returns, in order, on the same stream; after Channelizer.set_range call set_range here too.  Outputs
     are bit-identical however the rows are cut into batches."""
+    _kind = "tuner"
 
     def __init__(self, channelizer, freqs, taps, decim: int):
         import numpy as np
@@ -940,10 +929,6 @@ class Tuner:
                                           f.ctypes.data_as(C.POINTER(C.c_uint32)), f.size,
                                           h.ctypes.data_as(C.POINTER(C.c_float)), h.size, self.decim, 0))
         self._h = hd
-
-    def _stream(self, stream):
-        import torch
-        return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
 
     def next_outputs(self, nrows: int) -> int:
         """outputs per receiver the next process() of nrows rows writes (known from sizes alone)"""
@@ -982,16 +967,6 @@ class Tuner:
         """the Channelizer's new range (Channelizer.set_range), from the next process() on"""
         check(ddc_lib().pddc_tuner_set_range(self._h, first, count))
         self.first, self.count = int(first), int(count)
-
-    def reset(self):
-        check(ddc_lib().pddc_tuner_reset(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            ddc_lib().pddc_tuner_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 class PinnedBuffer:

@@ -1,8 +1,8 @@
 /*
  * ddc_channelizer.cpp -- host side of the channelizer (include/perseus_ddc.h, pddc_channelizer_*): the object, its
- * carried tail and counters, and the two launches of a batch.  The kernels are in ddc_channelizer.hip.
+ * counters, and the two launches of a batch.  The carried tail is a PackedCarry (ddc_packed.h); the kernels are in
+ * ddc_channelizer.hip.
  */
-#include "../../include/perseus_ddc.h"
 #include "ddc_channelizer.h"
 #include "ddc_kernels.h"
 #include "ddc_spectrum.h"
@@ -12,28 +12,13 @@
 
 using namespace pddc;
 
-extern "C" int pddc_set_error_(int code, const char *fmt, ...);
-
-#define CHAN_TRY(expr)                                                                                          \
-    do {                                                                                                        \
-        hipError_t e__ = (expr);                                                                                \
-        if (e__ != hipSuccess)                                                                                  \
-            return pddc_set_error_(e__ == hipErrorOutOfMemory ? PDDC_ENOMEM                                     \
-                                   : (e__ == hipErrorNoDevice || e__ == hipErrorInvalidDevice) ? PDDC_ENODEV    \
-                                                                                               : PDDC_EHIP,     \
-                                   "%s: %s", #expr, hipGetErrorString(e__));                                    \
-    } while (0)
-
 struct pddc_channelizer {
     int device = 0;
     int nchan = 0, hop = 0, proto_len = 0;
     int first = 0, count = 0;
     int target_blocks = 0;
     float *d_proto = nullptr, *d_tw = nullptr;
-    uint8_t *d_tail[2] = { nullptr, nullptr };      /* proto_len * 6 bytes each; process() reads [cur] and writes [cur ^ 1] */
-    int cur = 0;
-    uint64_t tail_len = 0;                          /* samples in d_tail[cur], < proto_len     */
-    uint64_t samples = 0;                           /* stream length since create / reset      */
+    PackedCarry in;                                 /* the carried tail (a window of proto_len) and the stream length */
     uint64_t rows = 0;                              /* rows delivered since create / reset     */
 };
 
@@ -49,39 +34,27 @@ static bool chan_sizes_ok(int nchan, int hop, int proto_len)
     return p == 1 || p == 2 || p == 4 || p == 8;
 }
 
-static bool chan_range_ok(int nchan, int first, int count)
-{
-    return first >= 0 && first < nchan && count >= 1 && count <= nchan;
-}
-
-static uint64_t chan_complete(int hop, int proto_len, uint64_t len)
-{
-    return len >= (uint64_t)proto_len ? (len - (uint64_t)proto_len) / (uint64_t)hop + 1 : 0;
-}
-
 static void chan_free(pddc_channelizer *c)
 {
     hipFree(c->d_proto);
     hipFree(c->d_tw);
-    hipFree(c->d_tail[0]);
-    hipFree(c->d_tail[1]);
+    c->in.free();
     delete c;
 }
 
 static int chan_create(pddc_channelizer *c, const float *proto)
 {
-    CHAN_TRY(hipSetDevice(c->device));
+    PDDC_HIP_TRY(hipSetDevice(c->device));
     int ncu = 0;
-    CHAN_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
+    PDDC_HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
     c->target_blocks = channelize_target_blocks(c->nchan, c->proto_len / c->nchan, c->hop, ncu > 0 ? ncu : 256);
     std::vector<float> tw((size_t)spectrum_twiddle_len(c->nchan));
     spectrum_build_twiddles(c->nchan, tw.data());
-    CHAN_TRY(hipMalloc(&c->d_proto, (size_t)c->proto_len * sizeof(float)));
-    CHAN_TRY(hipMalloc(&c->d_tw, tw.size() * sizeof(float)));
-    CHAN_TRY(hipMalloc(&c->d_tail[0], (size_t)c->proto_len * 6));
-    CHAN_TRY(hipMalloc(&c->d_tail[1], (size_t)c->proto_len * 6));
-    CHAN_TRY(hipMemcpy(c->d_proto, proto, (size_t)c->proto_len * sizeof(float), hipMemcpyHostToDevice));
-    CHAN_TRY(hipMemcpy(c->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
+    PDDC_HIP_TRY(hipMalloc(&c->d_proto, (size_t)c->proto_len * sizeof(float)));
+    PDDC_HIP_TRY(hipMalloc(&c->d_tw, tw.size() * sizeof(float)));
+    PDDC_HIP_TRY(c->in.alloc((size_t)c->proto_len));
+    PDDC_HIP_TRY(hipMemcpy(c->d_proto, proto, (size_t)c->proto_len * sizeof(float), hipMemcpyHostToDevice));
+    PDDC_HIP_TRY(hipMemcpy(c->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
     return PDDC_OK;
 }
 
@@ -91,12 +64,12 @@ uint64_t pddc_channelizer_rows(int nchan, int hop, int proto_len, uint64_t sampl
 {
     if (!chan_sizes_ok(nchan, hop, proto_len))
         return 0;
-    return chan_complete(hop, proto_len, samples_before + nsamples) - chan_complete(hop, proto_len, samples_before);
+    return windows_complete(proto_len, hop, samples_before + nsamples) - windows_complete(proto_len, hop, samples_before);
 }
 
 uint64_t pddc_channelizer_next_rows(const pddc_channelizer *c, size_t nsamples)
 {
-    return c ? pddc_channelizer_rows(c->nchan, c->hop, c->proto_len, c->samples, nsamples) : 0;
+    return c ? pddc_channelizer_rows(c->nchan, c->hop, c->proto_len, c->in.samples, nsamples) : 0;
 }
 
 int pddc_channelizer_create(pddc_channelizer **out, int device, int nchan, int hop, const float *proto, int proto_len,
@@ -112,17 +85,12 @@ int pddc_channelizer_create(pddc_channelizer **out, int device, int nchan, int h
                                nchan, hop, proto_len, kChanMaxProto);
     if (!proto)
         return pddc_set_error_(PDDC_EINVAL, "channelizer: null prototype");
-    if (!chan_range_ok(nchan, first, count))
+    if (!channel_range_ok(nchan, first, count))
         return pddc_set_error_(PDDC_EINVAL, "channelizer: first %d (0 .. nchan-1), count %d (1 .. nchan)", first, count);
     if (flags)
         return pddc_set_error_(PDDC_EINVAL, "channelizer: unknown flags 0x%x", flags);
-    const int ndev = pddc_device_count();
-    if (ndev < 0)
-        return ndev;
-    if (ndev == 0)
-        return pddc_set_error_(PDDC_ENODEV, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev)
-        return pddc_set_error_(PDDC_ENODEV, "device %d out of range (%d visible)", device, ndev);
+    if (const int rc = pddc_check_device_(device))
+        return rc;
     pddc_channelizer *c = new (std::nothrow) pddc_channelizer;
     if (!c)
         return pddc_set_error_(PDDC_ENOMEM, "out of memory");
@@ -155,10 +123,9 @@ int pddc_channelizer_reset(pddc_channelizer *c)
 {
     if (!c)
         return pddc_set_error_(PDDC_EINVAL, "null argument");
-    CHAN_TRY(hipSetDevice(c->device));
-    CHAN_TRY(hipDeviceSynchronize());
-    c->tail_len = 0;
-    c->samples = 0;
+    PDDC_HIP_TRY(hipSetDevice(c->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());
+    c->in.reset();
     c->rows = 0;
     return PDDC_OK;
 }
@@ -167,7 +134,7 @@ int pddc_channelizer_set_range(pddc_channelizer *c, int first, int count)
 {
     if (!c)
         return pddc_set_error_(PDDC_EINVAL, "null argument");
-    if (!chan_range_ok(c->nchan, first, count))
+    if (!channel_range_ok(c->nchan, first, count))
         return pddc_set_error_(PDDC_EINVAL, "channelizer: first %d (0 .. nchan-1), count %d (1 .. nchan)", first, count);
     c->first = first;
     c->count = count;
@@ -179,12 +146,10 @@ int pddc_channelizer_process(pddc_channelizer *c, const void *d_packed, size_t n
 {
     if (!c)
         return pddc_set_error_(PDDC_EINVAL, "null argument");
-    if (nsamples % 8)
-        return pddc_set_error_(PDDC_EINVAL, "nsamples (%zu) must be a multiple of 8", nsamples);
-    if (nsamples && (!d_packed || ((uintptr_t)d_packed & 15)))
-        return pddc_set_error_(PDDC_EINVAL, "d_packed must be a 16-byte aligned device pointer");
-    const uint64_t len = c->tail_len + nsamples;           /* tail-then-batch */
-    const uint64_t nrows = chan_complete(c->hop, c->proto_len, len);
+    if (const int rc = PackedCarry::check(d_packed, nsamples))
+        return rc;
+    const PackedCarry::Plan plan = c->in.plan(nsamples, c->proto_len, c->hop);
+    const uint64_t nrows = plan.n_complete;
     if (nrows && (!d_out || ((uintptr_t)d_out & 7)))
         return pddc_set_error_(PDDC_EINVAL, "d_out must be an 8-byte aligned device pointer");
     if (nrows > out_capacity_rows)
@@ -194,8 +159,7 @@ int pddc_channelizer_process(pddc_channelizer *c, const void *d_packed, size_t n
         *n_rows = 0;
     if (!nsamples)
         return PDDC_OK;
-    CHAN_TRY(hipSetDevice(c->device));
-    const uint64_t keep_from = nrows * (uint64_t)c->hop;
+    PDDC_HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     if (nrows) {
         const int taps = c->proto_len / c->nchan, units = taps * (c->nchan / c->hop);
@@ -208,9 +172,7 @@ int pddc_channelizer_process(pddc_channelizer *c, const void *d_packed, size_t n
             run = run < floor_rows ? floor_rows : run;
         }
         ChannelizeArgs a{};
-        a.tail = c->d_tail[c->cur];
-        a.batch = static_cast<const uint8_t *>(d_packed);
-        a.tail_len = (long long)c->tail_len;
+        a.in = c->in.stream(d_packed);
         a.nrows = (long long)nrows;
         a.run = run < 1 ? 1 : run;
         a.row_parity = (unsigned)(c->rows & 1);
@@ -219,20 +181,11 @@ int pddc_channelizer_process(pddc_channelizer *c, const void *d_packed, size_t n
         a.proto = c->d_proto;
         a.twiddles = c->d_tw;
         a.out = static_cast<float *>(d_out);
-        CHAN_TRY(launch_channelize(c->nchan, taps, c->hop, a, st));
+        PDDC_HIP_TRY(launch_channelize(c->nchan, taps, c->hop, a, st));
     }
-    ChannelizeTailArgs t{};
-    t.tail = c->d_tail[c->cur];
-    t.batch = static_cast<const uint8_t *>(d_packed);
-    t.new_tail = c->d_tail[c->cur ^ 1];
-    t.tail_len = (long long)c->tail_len;
-    t.keep_from = (long long)keep_from;
-    t.new_len = (long long)(len - keep_from);
-    CHAN_TRY(launch_channelize_tail(t, st));
+    PDDC_HIP_TRY(launch_channelize_tail(c->in.carry(plan, d_packed), st));
     /* both launches were accepted: only now do the host-side counters move */
-    c->cur ^= 1;
-    c->tail_len = len - keep_from;
-    c->samples += nsamples;
+    c->in.commit(plan, nsamples);
     c->rows += nrows;
     if (n_rows)
         *n_rows = (size_t)nrows;

@@ -5,7 +5,7 @@
  *                (Q = 1 critically sampled, Q = 2 oversampled by 2).  Per row s: u[r] = sum_p w[r + p M] x[s D + r + p M],
  *                the M-point transform of u (ddc_fft_dev.h, the panorama's), times (-1)^(k s) for Q = 2, the channels
  *                (first + i) mod M, i < count, stored as complex float32, row-major.
- *   k_channelize_tail       the packed tail carried to the next batch (16-byte copies, double-buffered by the host).
+ *   k_channelize_tail       the packed tail carried to the next batch (ddc_packed.h).
  *
  * Walk: block b owns the RUN of consecutive rows [b run, (b + 1) run).  The stream is cut into UNITS of D samples; row s
  * needs units s .. s + P Q - 1, of which only the newest comes from HBM (3 x global_load_dwordx4 per 8 samples, loaded
@@ -88,14 +88,8 @@ __global__ __launch_bounds__(M / 16 < 256 ? M / 16 : 256) void k_channelize(Chan
     auto load_unit = [&](long long t) {          /* unit t of the run: samples (row0 + t) D .. + D */
         const long long v0 = (row0 + t) * D;
 #pragma unroll
-        for (int uu = 0; uu < NGU; ++uu) {
-            const long long v = v0 + 8LL * (tid + uu * NT);     /* tail_len is a multiple of 8: a group lies on one side */
-            const uint8_t *src = v < a.tail_len ? a.tail + v * 6 : a.batch + (v - a.tail_len) * 6;
-            const u32x4 *s = reinterpret_cast<const u32x4 *>(src);
-            raw[uu][0] = __builtin_nontemporal_load(s);
-            raw[uu][1] = __builtin_nontemporal_load(s + 1);
-            raw[uu][2] = __builtin_nontemporal_load(s + 2);
-        }
+        for (int uu = 0; uu < NGU; ++uu)
+            a.in.load_group(v0 + 8LL * (tid + uu * NT), raw[uu]);
     };
     auto ring_put = [&](int slot) {
 #pragma unroll
@@ -134,13 +128,9 @@ __global__ __launch_bounds__(M / 16 < 256 ? M / 16 : 256) void k_channelize(Chan
                 }
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
-                    /* 12 bytes = 2 samples: I0 Q0 I1 Q1, MSB-aligned (value * 256) as k_unpack24 places them */
-                    const uint32_t wa = x[(3 * h) >> 2][(3 * h) & 3], wb = x[(3 * h + 1) >> 2][(3 * h + 1) & 3],
-                                   wc = x[(3 * h + 2) >> 2][(3 * h + 2) & 3];
-                    int32_t i0, q0, i1, q1;
-                    unpack2_msb(wa, wb, wc, i0, q0, i1, q1);
-                    const float fi0 = (float)i0 * kSpecUnpackScale, fq0 = (float)q0 * kSpecUnpackScale;
-                    const float fi1 = (float)i1 * kSpecUnpackScale, fq1 = (float)q1 * kSpecUnpackScale;
+                    PDDC_UNPACK_GROUP_MSB(x, h, i0, q0, i1, q1);
+                    const float fi0 = (float)i0 * kPackedUnpackScale, fq0 = (float)q0 * kPackedUnpackScale;
+                    const float fi1 = (float)i1 * kPackedUnpackScale, fq1 = (float)q1 * kPackedUnpackScale;
                     const float w0 = win[p][u][2 * h], w1 = win[p][u][2 * h + 1];
                     if (p == 0) {
                         acc[2 * h] = make_float2(fi0 * w0, fq0 * w0);
@@ -186,18 +176,9 @@ __global__ __launch_bounds__(M / 16 < 256 ? M / 16 : 256) void k_channelize(Chan
     }
 }
 
-/* new_tail[c] = (tail-then-batch)[keep_from*6/16 + c], 16-byte chunks: every length is a multiple of 8 samples = 48 B */
-__global__ __launch_bounds__(256) void k_channelize_tail(ChannelizeTailArgs p)
+__global__ __launch_bounds__(256) void k_channelize_tail(PackedCarryArgs p)
 {
-    const long long nchunks = p.new_len * 6 / 16;
-    const long long tail_chunks = p.tail_len * 6 / 16, from = p.keep_from * 6 / 16;
-    const long long stride = (long long)gridDim.x * 256;
-    for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < nchunks; c += stride) {
-        const long long v = from + c;
-        const u32x4 *src = v < tail_chunks ? reinterpret_cast<const u32x4 *>(p.tail) + v
-                                           : reinterpret_cast<const u32x4 *>(p.batch) + (v - tail_chunks);
-        reinterpret_cast<u32x4 *>(p.new_tail)[c] = *src;
-    }
+    PDDC_CARRY_TAIL(p, 0)
 }
 
 /* ------------------------------------------------------------------------ */
@@ -205,21 +186,8 @@ template <int M, int P, int Q> static hipError_t launch_channelize_t(const Chann
 {
     constexpr int NT = M / 16 < 256 ? M / 16 : 256;
     const size_t lds = channelize_lds_bytes(M, P, M / Q);
-    static bool raised[64] = {};      /* (two threads may both set the attribute: the same value, harmless) */
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess)
-        return e;
-    if (!raised[dev & 63]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_channelize<M, P, Q>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return e;
-        raised[dev & 63] = true;
-    }
     const long long blocks = (a.nrows + a.run - 1) / a.run;
-    hipLaunchKernelGGL((k_channelize<M, P, Q>), dim3((unsigned)blocks), dim3(NT), lds, s, a);
-    return hipGetLastError();
+    return launch_dynamic_lds<&k_channelize<M, P, Q>>(lds, dim3((unsigned)blocks), dim3(NT), lds, s, a);
 }
 
 template <int M, int P> static hipError_t launch_channelize_q(int q, const ChannelizeArgs &a, hipStream_t s)
@@ -254,12 +222,11 @@ hipError_t launch_channelize(int nchan, int taps_per_branch, int hop, const Chan
     }
 }
 
-hipError_t launch_channelize_tail(const ChannelizeTailArgs &a, hipStream_t s)
+hipError_t launch_channelize_tail(const PackedCarryArgs &a, hipStream_t s)
 {
-    const long long nchunks = a.new_len * 6 / 16;
-    if (nchunks <= 0)
+    const int blocks = carry_tail_blocks(a.new_len);
+    if (blocks <= 0)
         return hipSuccess;
-    const int blocks = (int)((nchunks + 255) / 256 < 32 ? (nchunks + 255) / 256 : 32);
     hipLaunchKernelGGL(k_channelize_tail, dim3((unsigned)blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -18,8 +18,6 @@
 
 namespace pddc {
 
-static constexpr float kSpecUnpackScale = 0x1.000002p-31f;   /* as k_unpack24: (float)(v24 * 256) * this */
-
 template <int N> struct SpecPlan;
 template <> struct SpecPlan<1024> { static constexpr int NP = 3, R2 = 4, R3 = 1, BLOCKS_PER_CU = 8; };
 template <> struct SpecPlan<2048> { static constexpr int NP = 3, R2 = 8, R3 = 1, BLOCKS_PER_CU = 4; };

@@ -57,6 +57,7 @@
  */
 #include "ddc_kernels.h"
 #include "ddc_dev.h"
+#include "ddc_host.h"
 
 #include <cmath>
 #include <cstdio>
@@ -1289,33 +1290,15 @@ static hipError_t launch_fir8_t(InFmt fmt, bool mix, const Fir8Args &a, hipStrea
     const size_t lds_launch = a.tail.nblocks > 0 && a.tail.lds > lds ? a.tail.lds : lds;
     const size_t lds_attr = lds > kCarryLdsCap ? lds : kCarryLdsCap;
     const dim3 grid((unsigned)(sc.nblocks + a.tail.nblocks)), blk(NT);
-#define PDDC_LAUNCH(FMT, MIXV)                                                                    \
-    do {                                                                                          \
-        static unsigned long long attr_done = 0;   /* one bit per device: the attribute is per device */ \
-        int dev__ = 0;                                                                            \
-        (void)hipGetDevice(&dev__);                                                               \
-        if (!(attr_done >> (dev__ & 63) & 1ull)) {                                                \
-            hipError_t e = hipFuncSetAttribute(                                                   \
-                reinterpret_cast<const void *>(&k_fir8<NTB, R, FMT, MIXV, 0, NT>),                \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_attr);                       \
-            if (e != hipSuccess)                                                                  \
-                return e;                                                                         \
-            attr_done |= 1ull << (dev__ & 63);                                                    \
-        }                                                                                         \
-        hipLaunchKernelGGL((k_fir8<NTB, R, FMT, MIXV, 0, NT>), grid, blk, lds_launch, s, a, ntiles, sc.S, sc.K); \
-    } while (0)
-    if (fmt == IN_PACKED24) {
-        if (mix)
-            PDDC_LAUNCH(IN_PACKED24, true);
-        else
-            PDDC_LAUNCH(IN_PACKED24, false);
-    } else if constexpr (NT == 256) {
-        PDDC_LAUNCH(IN_F32C, false);
-    } else {
-        return hipErrorInvalidValue;         /* 128-thread blocks exist for the packed first stage only */
-    }
-#undef PDDC_LAUNCH
-    return hipGetLastError();
+    if (fmt == IN_PACKED24)
+        return mix ? launch_dynamic_lds<&k_fir8<NTB, R, IN_PACKED24, true, 0, NT>>(lds_attr, grid, blk, lds_launch, s, a,
+                                                                                  ntiles, sc.S, sc.K)
+                   : launch_dynamic_lds<&k_fir8<NTB, R, IN_PACKED24, false, 0, NT>>(lds_attr, grid, blk, lds_launch, s, a,
+                                                                                   ntiles, sc.S, sc.K);
+    if constexpr (NT == 256)
+        return launch_dynamic_lds<&k_fir8<NTB, R, IN_F32C, false, 0, NT>>(lds_attr, grid, blk, lds_launch, s, a, ntiles,
+                                                                         sc.S, sc.K);
+    return hipErrorInvalidValue;             /* 128-thread blocks exist for the packed first stage only */
 }
 
 /* fused pair: packed input -> [mix] -> /8 (NTB blocks) -> /8 (<= 64 taps) */
@@ -1339,28 +1322,10 @@ static hipError_t launch_fir8_fused2_t(bool mix, const Fir8Args &a, hipStream_t 
     const size_t lds_launch = a.tail.nblocks > 0 && a.tail.lds > lds ? a.tail.lds : lds;
     const size_t lds_attr = lds > kCarryLdsCap ? lds : kCarryLdsCap;
     const dim3 grid((unsigned)(sc.nblocks + a.tail.nblocks)), blk(256);
-#define PDDC_LAUNCH2(MIXV)                                                                        \
-    do {                                                                                          \
-        static unsigned long long attr_done = 0;                                                  \
-        int dev__ = 0;                                                                            \
-        (void)hipGetDevice(&dev__);                                                               \
-        if (!(attr_done >> (dev__ & 63) & 1ull)) {                                                \
-            hipError_t e = hipFuncSetAttribute(                                                   \
-                reinterpret_cast<const void *>(&k_fir8<NTB, R, IN_PACKED24, MIXV, 8>),            \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_attr);                       \
-            if (e != hipSuccess)                                                                  \
-                return e;                                                                         \
-            attr_done |= 1ull << (dev__ & 63);                                                    \
-        }                                                                                         \
-        hipLaunchKernelGGL((k_fir8<NTB, R, IN_PACKED24, MIXV, 8>), grid, blk, lds_launch, s, a, ntiles, \
-                           sc.S, sc.K);                                                           \
-    } while (0)
-    if (mix)
-        PDDC_LAUNCH2(true);
-    else
-        PDDC_LAUNCH2(false);
-#undef PDDC_LAUNCH2
-    return hipGetLastError();
+    return mix ? launch_dynamic_lds<&k_fir8<NTB, R, IN_PACKED24, true, 8>>(lds_attr, grid, blk, lds_launch, s, a, ntiles,
+                                                                          sc.S, sc.K)
+               : launch_dynamic_lds<&k_fir8<NTB, R, IN_PACKED24, false, 8>>(lds_attr, grid, blk, lds_launch, s, a, ntiles,
+                                                                           sc.S, sc.K);
 }
 
 size_t fir8_fused2_lds_bytes(int ntb, int R)
@@ -1444,28 +1409,10 @@ static hipError_t launch_fir8_fused3_t(bool mix, const Fir8Args &a, hipStream_t 
         return hipErrorInvalidValue;
     const Fir8Sched sc = fir8_schedule(ntiles, R, true, 256, q.g);
     const dim3 grid((unsigned)sc.nblocks), blk(256);
-#define PDDC_LAUNCH3(MIXV)                                                                        \
-    do {                                                                                          \
-        static unsigned long long attr_done = 0;                                                  \
-        int dev__ = 0;                                                                            \
-        (void)hipGetDevice(&dev__);                                                               \
-        if (!(attr_done >> (dev__ & 63) & 1ull)) {                                                \
-            hipError_t e = hipFuncSetAttribute(                                                   \
-                reinterpret_cast<const void *>(&k_fir8<NTB, R, IN_PACKED24, MIXV, 8, 256, SL3>), \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap);                        \
-            if (e != hipSuccess)                                                                  \
-                return e;                                                                         \
-            attr_done |= 1ull << (dev__ & 63);                                                    \
-        }                                                                                         \
-        hipLaunchKernelGGL((k_fir8<NTB, R, IN_PACKED24, MIXV, 8, 256, SL3>), grid, blk, lds, s, a, ntiles, \
-                           sc.S, sc.K);                                                           \
-    } while (0)
-    if (mix)
-        PDDC_LAUNCH3(true);
-    else
-        PDDC_LAUNCH3(false);
-#undef PDDC_LAUNCH3
-    return hipGetLastError();
+    return mix ? launch_dynamic_lds<&k_fir8<NTB, R, IN_PACKED24, true, 8, 256, SL3>>(lds_cap, grid, blk, lds, s, a, ntiles,
+                                                                                    sc.S, sc.K)
+               : launch_dynamic_lds<&k_fir8<NTB, R, IN_PACKED24, false, 8, 256, SL3>>(lds_cap, grid, blk, lds, s, a, ntiles,
+                                                                                     sc.S, sc.K);
 }
 
 hipError_t launch_fir8_fused3(int ntb, int R, bool mix, const Fir8Args &a, hipStream_t s)
@@ -1518,27 +1465,10 @@ static hipError_t launch_fir8_many_t(bool mix, const Fir8Many &m, int n, hipStre
      * chunk counter -- 8 streams 242-254 vs 246 GS/s through the API, no gain, not kept.)                          */
     const Fir8Sched sc = fir8_schedule(ntiles, R, NTB2 != 0);
     const dim3 grid((unsigned)sc.nblocks, (unsigned)n), blk(256);
-#define PDDC_LAUNCHM(MIXV)                                                                        \
-    do {                                                                                          \
-        static unsigned long long attr_done = 0;                                                  \
-        int dev__ = 0;                                                                            \
-        (void)hipGetDevice(&dev__);                                                               \
-        if (!(attr_done >> (dev__ & 63) & 1ull)) {                                                \
-            hipError_t e = hipFuncSetAttribute(                                                   \
-                reinterpret_cast<const void *>(&k_fir8_many<NTB, R, IN_PACKED24, MIXV, NTB2>),    \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
-            if (e != hipSuccess)                                                                  \
-                return e;                                                                         \
-            attr_done |= 1ull << (dev__ & 63);                                                    \
-        }                                                                                         \
-        hipLaunchKernelGGL((k_fir8_many<NTB, R, IN_PACKED24, MIXV, NTB2>), grid, blk, lds, s, m, ntiles, sc.S, sc.K); \
-    } while (0)
-    if (mix)
-        PDDC_LAUNCHM(true);
-    else
-        PDDC_LAUNCHM(false);
-#undef PDDC_LAUNCHM
-    return hipGetLastError();
+    return mix ? launch_dynamic_lds<&k_fir8_many<NTB, R, IN_PACKED24, true, NTB2>>(lds, grid, blk, lds, s, m, ntiles, sc.S,
+                                                                                  sc.K)
+               : launch_dynamic_lds<&k_fir8_many<NTB, R, IN_PACKED24, false, NTB2>>(lds, grid, blk, lds, s, m, ntiles, sc.S,
+                                                                                   sc.K);
 }
 
 bool fir8_many_supported(int kind, int ntb, int R)
@@ -1833,32 +1763,12 @@ static hipError_t launch_firp_t(int infmt, bool mix, const FirpArgs &a, int ntap
     const long long ntiles = (a.n_out + G::TO - 1) / G::TO;
     if (ntiles > 0x7fffffffLL)
         return hipErrorInvalidValue;
-    const size_t lds_launch = lds;
     const dim3 grid((unsigned)ntiles), blk(256);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-#define PDDC_FIRP(FMT, MX)                                                                         \
-    do {                                                                                          \
-        static bool attr_done[64] = { false };                                                    \
-        if (!attr_done[dev & 63]) {                                                               \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_firp<D, P, FMT, MX>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
-            if (e != hipSuccess)                                                                  \
-                return e;                                                                         \
-            attr_done[dev & 63] = true;                                                           \
-        }                                                                                         \
-        hipLaunchKernelGGL((k_firp<D, P, FMT, MX>), grid, blk, lds_launch, s, a);                 \
-    } while (0)
-    if (infmt == IN_PACKED24) {
-        if (mix)
-            PDDC_FIRP(IN_PACKED24, true);
-        else
-            PDDC_FIRP(IN_PACKED24, false);
-    } else {
-        PDDC_FIRP(IN_F32C, false);
-    }
-#undef PDDC_FIRP
-    return hipGetLastError();
+    constexpr size_t lds_cap = 96u * 1024u;
+    if (infmt == IN_PACKED24)
+        return mix ? launch_dynamic_lds<&k_firp<D, P, IN_PACKED24, true>>(lds_cap, grid, blk, lds, s, a)
+                   : launch_dynamic_lds<&k_firp<D, P, IN_PACKED24, false>>(lds_cap, grid, blk, lds, s, a);
+    return launch_dynamic_lds<&k_firp<D, P, IN_F32C, false>>(lds_cap, grid, blk, lds, s, a);
 }
 
 /* same contract as launch_fir_generic / launch_fir_generic_packed; `taps2` = (h, h) pairs zero padded to
@@ -1955,22 +1865,12 @@ hipError_t launch_gen_tail(const GenTail &t, hipStream_t s)
     if (t.kind == 1)
         return launch_firp(IN_F32C, false, t.in, t.hist, t.H, t.first, t.n_out, t.D, t.taps2, t.ntaps, t.out, t.hist_out,
                            t.n_batch, nullptr, s);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    static bool attr_done[64] = { false };
-    if (!attr_done[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fir_generic<1, false, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess)
-            return e;
-        attr_done[dev & 63] = true;
-    }
+    /* the whole LDS, as launch_fir_generic_any asks for the same function */
     const GenMixArgs mx = {};
-    hipLaunchKernelGGL((k_fir_generic<1, false, false>), dim3((unsigned)t.nblocks), dim3(256), t.lds, s,
-                       reinterpret_cast<const float2 *>(t.in), reinterpret_cast<const float2 *>(t.hist), t.H, t.first,
-                       t.n_out, t.D, (const float PDDC_CONSTANT *)t.taps, t.ntaps, reinterpret_cast<float2 *>(t.out),
-                       t.span, t.a, reinterpret_cast<float2 *>(t.hist_out), t.n_batch, mx);
-    return hipGetLastError();
+    return launch_dynamic_lds<&k_fir_generic<1, false, false>>(
+        160 * 1024, dim3((unsigned)t.nblocks), dim3(256), t.lds, s, reinterpret_cast<const float2 *>(t.in),
+        reinterpret_cast<const float2 *>(t.hist), t.H, t.first, t.n_out, t.D, (const float PDDC_CONSTANT *)t.taps, t.ntaps,
+        reinterpret_cast<float2 *>(t.out), t.span, t.a, reinterpret_cast<float2 *>(t.hist_out), t.n_batch, mx);
 }
 
 /* the tails of several streams in one launch: blockIdx.y is the stream */
@@ -1997,18 +1897,7 @@ hipError_t launch_gen_tail_many(const GenTailMany &m, int n, hipStream_t s)
     }
     if (nb <= 0)
         return hipSuccess;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    static bool attr_done[64] = { false };
-    if (!attr_done[dev & 63]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gen_tail_many),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess)
-            return e;
-        attr_done[dev & 63] = true;
-    }
-    hipLaunchKernelGGL(k_gen_tail_many, dim3((unsigned)nb, (unsigned)n), dim3(256), lds, s, m);
-    return hipGetLastError();
+    return launch_dynamic_lds<&k_gen_tail_many>(160 * 1024, dim3((unsigned)nb, (unsigned)n), dim3(256), lds, s, m);
 }
 
 /* ======================================================================== */

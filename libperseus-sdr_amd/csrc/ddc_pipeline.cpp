@@ -10,7 +10,7 @@
  * There is no CPU implementation behind these entry points: if HIP reports no
  * device they fail with PDDC_ENODEV.
  */
-#include "../../include/perseus_ddc.h"
+#include "ddc_host.h"
 #include "ddc_kernels.h"
 
 #include <algorithm>
@@ -45,16 +45,6 @@ extern "C" __attribute__((visibility("hidden"))) int pddc_set_error_(int code, c
     va_end(ap);
     return code;
 }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess)                                                                     \
-            return fail(e__ == hipErrorOutOfMemory ? PDDC_ENOMEM                                   \
-                        : (e__ == hipErrorNoDevice || e__ == hipErrorInvalidDevice) ? PDDC_ENODEV  \
-                                                                                    : PDDC_EHIP,   \
-                        "%s: %s", #expr, hipGetErrorString(e__));                                  \
-    } while (0)
 
 /* ------------------------------------------------------------------------ */
 struct Stage {
@@ -304,8 +294,8 @@ static int upload_taps(pddc_pipeline *p, int si)
         const size_t Z = 3 * (size_t)s.decim + 8;
         std::vector<float> padded(Z + (size_t)s.ntaps + Z + 8, 0.0f);
         std::copy(s.taps.begin(), s.taps.begin() + s.ntaps, padded.begin() + (long)Z);
-        HIP_TRY(hipMalloc(&s.d_taps_base, sizeof(float) * padded.size()));
-        HIP_TRY(hipMemcpy(s.d_taps_base, padded.data(), sizeof(float) * padded.size(), hipMemcpyHostToDevice));
+        PDDC_HIP_TRY(hipMalloc(&s.d_taps_base, sizeof(float) * padded.size()));
+        PDDC_HIP_TRY(hipMemcpy(s.d_taps_base, padded.data(), sizeof(float) * padded.size(), hipMemcpyHostToDevice));
         s.d_taps = s.d_taps_base + Z;
         std::vector<float> dup(2 * padded.size());
         for (size_t k = 0; k < padded.size(); ++k)
@@ -313,8 +303,8 @@ static int upload_taps(pddc_pipeline *p, int si)
         if (s.d_taps_dup_base)
             hipFree(s.d_taps_dup_base);
         s.d_taps_dup_base = nullptr;
-        HIP_TRY(hipMalloc(&s.d_taps_dup_base, sizeof(float) * dup.size()));
-        HIP_TRY(hipMemcpy(s.d_taps_dup_base, dup.data(), sizeof(float) * dup.size(), hipMemcpyHostToDevice));
+        PDDC_HIP_TRY(hipMalloc(&s.d_taps_dup_base, sizeof(float) * dup.size()));
+        PDDC_HIP_TRY(hipMemcpy(s.d_taps_dup_base, dup.data(), sizeof(float) * dup.size(), hipMemcpyHostToDevice));
         s.d_taps_dup = s.d_taps_dup_base + 2 * Z;
     }
     if (s.d_taps_poly) {
@@ -347,8 +337,8 @@ static int upload_taps(pddc_pipeline *p, int si)
         if (fir_i8x_build_tables(s.taps.data(), s.ntaps, i8_hist, false, 0u, tab.data(), &sc, ct, &e2)) {
             std::vector<uint16_t> h16((size_t)kFirI8Taps16Len);
             fir_i8_taps16(s.taps.data(), s.ntaps, i8_hist, h16.data());
-            HIP_TRY(hipMalloc(&s.d_taps_f16, h16.size() * sizeof(uint16_t)));
-            HIP_TRY(hipMemcpy(s.d_taps_f16, h16.data(), h16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            PDDC_HIP_TRY(hipMalloc(&s.d_taps_f16, h16.size() * sizeof(uint16_t)));
+            PDDC_HIP_TRY(hipMemcpy(s.d_taps_f16, h16.data(), h16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
             s.i8_two_e = std::ldexp(1.0f, e2);
         }
     }
@@ -358,8 +348,8 @@ static int upload_taps(pddc_pipeline *p, int si)
         std::vector<float> t2(2 * (size_t)firp_taps_len(s.decim, s.ntaps), 0.0f);
         for (int k = 0; k < s.ntaps; ++k)
             t2[2 * (size_t)k] = t2[2 * (size_t)k + 1] = s.taps[k] * tap_scale;
-        HIP_TRY(hipMalloc(&s.d_taps_firp, sizeof(float) * t2.size()));
-        HIP_TRY(hipMemcpy(s.d_taps_firp, t2.data(), sizeof(float) * t2.size(), hipMemcpyHostToDevice));
+        PDDC_HIP_TRY(hipMalloc(&s.d_taps_firp, sizeof(float) * t2.size()));
+        PDDC_HIP_TRY(hipMemcpy(s.d_taps_firp, t2.data(), sizeof(float) * t2.size(), hipMemcpyHostToDevice));
     }
     if (s.interp > 1 && resample_lds_supported(s.interp, s.decim, s.ntaps)) {
         s.poly_k = (s.ntaps + s.interp - 1) / s.interp;
@@ -370,8 +360,8 @@ static int upload_taps(pddc_pipeline *p, int si)
                 const int k = j * s.interp + ph;
                 g[(size_t)ph * s.poly_kp + j] = k < s.ntaps ? s.taps[k] : 0.0f;
             }
-        HIP_TRY(hipMalloc(&s.d_taps_poly, sizeof(float) * g.size()));
-        HIP_TRY(hipMemcpy(s.d_taps_poly, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
+        PDDC_HIP_TRY(hipMalloc(&s.d_taps_poly, sizeof(float) * g.size()));
+        PDDC_HIP_TRY(hipMemcpy(s.d_taps_poly, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
     }
     s.ntb = stage_fused_capable(s) ? pick_ntb(s.ntaps) : 0;
     /* a second stage that can be fused behind stage 0 always uses 8 tap blocks
@@ -389,8 +379,8 @@ static int upload_taps(pddc_pipeline *p, int si)
                 const int k = 8 * j + 7 - e;
                 blk[(size_t)j * 8 + e] = k < s.ntaps ? s.taps[k] * tap_scale : 0.0f;
             }
-        HIP_TRY(hipMalloc(&s.d_taps_blk, sizeof(float) * blk.size()));
-        HIP_TRY(hipMemcpy(s.d_taps_blk, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
+        PDDC_HIP_TRY(hipMalloc(&s.d_taps_blk, sizeof(float) * blk.size()));
+        PDDC_HIP_TRY(hipMemcpy(s.d_taps_blk, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
     }
     return PDDC_OK;
 }
@@ -493,13 +483,27 @@ int pddc_fir_i8_taps16(const float *taps, int ntaps, int hist, uint16_t *out, si
     return PDDC_OK;
 }
 
-static int require_device(void)
+static int require_device(int *count = nullptr)
 {
     int n = pddc_device_count();
     if (n < 0)
         return n;
     if (n == 0)
         return fail(PDDC_ENODEV, "no HIP device visible (this library has no CPU fallback)");
+    if (count)
+        *count = n;
+    return PDDC_OK;
+}
+
+/* ... and `device` is one of them: for the library's other translation units (ddc_host.h); not exported */
+extern "C" __attribute__((visibility("hidden"))) int pddc_check_device_(int device)
+{
+    int n = 0;
+    const int rc = require_device(&n);
+    if (rc)
+        return rc;
+    if (device < 0 || device >= n)
+        return fail(PDDC_ENODEV, "device %d out of range (%d visible)", device, n);
     return PDDC_OK;
 }
 
@@ -508,7 +512,7 @@ int pddc_set_device(int device)
     int rc = require_device();
     if (rc)
         return rc;
-    HIP_TRY(hipSetDevice(device));
+    PDDC_HIP_TRY(hipSetDevice(device));
     return PDDC_OK;
 }
 
@@ -519,7 +523,7 @@ int pddc_malloc(void **d_ptr, size_t nbytes)
     int rc = require_device();
     if (rc)
         return rc;
-    HIP_TRY(hipMalloc(d_ptr, nbytes ? nbytes : 16));
+    PDDC_HIP_TRY(hipMalloc(d_ptr, nbytes ? nbytes : 16));
     return PDDC_OK;
 }
 
@@ -548,7 +552,7 @@ static int malloc_apart_impl(void **d_ptr, size_t nbytes, const void *d_partner,
         *ms_worst = 0.0f;
     if (!d_partner || partner_bytes < (64u << 20) || nbytes < min_bytes || max_candidates <= 1 ||
         ((uintptr_t)d_partner & 15)) {
-        HIP_TRY(hipMalloc(d_ptr, nbytes));             /* too small to matter (or nothing to stay away from) */
+        PDDC_HIP_TRY(hipMalloc(d_ptr, nbytes));             /* too small to matter (or nothing to stay away from) */
         return PDDC_OK;
     }
     size_t spacer_bytes = (size_t)8 << 30;
@@ -565,7 +569,7 @@ static int malloc_apart_impl(void **d_ptr, size_t nbytes, const void *d_partner,
         (void)hipGetLastError();
         const size_t budget = free_b / 2;
         if (budget < 2 * nbytes + spacer_bytes) {
-            HIP_TRY(hipMalloc(d_ptr, asked));
+            PDDC_HIP_TRY(hipMalloc(d_ptr, asked));
             return PDDC_OK;
         }
         const size_t per = nbytes + spacer_bytes;
@@ -577,8 +581,8 @@ static int malloc_apart_impl(void **d_ptr, size_t nbytes, const void *d_partner,
     std::vector<void *> cands, spacers;
     std::vector<float> ms;
     hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    PDDC_HIP_TRY(hipEventCreate(&e0));
+    PDDC_HIP_TRY(hipEventCreate(&e1));
     auto cleanup = [&](void *keep) {
         for (void *c : cands)
             if (c != keep)
@@ -621,7 +625,7 @@ static int malloc_apart_impl(void **d_ptr, size_t nbytes, const void *d_partner,
         if (e != hipSuccess) {                          /* a probe that fails costs the search, not the buffer */
             (void)hipGetLastError();
             cleanup(nullptr);
-            HIP_TRY(hipMalloc(d_ptr, asked));
+            PDDC_HIP_TRY(hipMalloc(d_ptr, asked));
             return PDDC_OK;
         }
         ms.push_back(t / 5.0f);
@@ -663,25 +667,25 @@ int pddc_malloc_apart(void **d_ptr, size_t nbytes, const void *d_partner, size_t
 int pddc_free(void *d_ptr)
 {
     if (d_ptr)
-        HIP_TRY(hipFree(d_ptr));
+        PDDC_HIP_TRY(hipFree(d_ptr));
     return PDDC_OK;
 }
 
 int pddc_memcpy_h2d(void *d_dst, const void *h_src, size_t nbytes, void *stream)
 {
-    HIP_TRY(hipMemcpyAsync(d_dst, h_src, nbytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    PDDC_HIP_TRY(hipMemcpyAsync(d_dst, h_src, nbytes, hipMemcpyHostToDevice, (hipStream_t)stream));
     return PDDC_OK;
 }
 
 int pddc_memcpy_d2h(void *h_dst, const void *d_src, size_t nbytes, void *stream)
 {
-    HIP_TRY(hipMemcpyAsync(h_dst, d_src, nbytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    PDDC_HIP_TRY(hipMemcpyAsync(h_dst, d_src, nbytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
     return PDDC_OK;
 }
 
 int pddc_stream_sync(void *stream)
 {
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    PDDC_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return PDDC_OK;
 }
 
@@ -703,8 +707,8 @@ int pddc_unpack24_f32(const void *d_packed, size_t nsamples, void *d_out, void *
         return rc;
     if ((rc = check_unpack_args(d_packed, d_out, nsamples)))
         return rc;
-    HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, d_out, false, false, 0, 0, 0, nullptr, nullptr,
-                            (hipStream_t)stream));
+    PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, d_out, false, false, 0, 0, 0, nullptr, nullptr,
+                                 (hipStream_t)stream));
     return PDDC_OK;
 }
 
@@ -715,8 +719,8 @@ int pddc_unpack24_i32(const void *d_packed, size_t nsamples, void *d_out, void *
         return rc;
     if ((rc = check_unpack_args(d_packed, d_out, nsamples)))
         return rc;
-    HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, d_out, true, false, 0, 0, 0, nullptr, nullptr,
-                            (hipStream_t)stream));
+    PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, d_out, true, false, 0, 0, 0, nullptr, nullptr,
+                                 (hipStream_t)stream));
     return PDDC_OK;
 }
 
@@ -727,7 +731,7 @@ int pddc_pack24_f32(const void *d_in, size_t nsamples, void *d_out, void *stream
         return rc;
     if ((rc = check_unpack_args(d_in, d_out, nsamples)))
         return rc;
-    HIP_TRY(launch_pack24(static_cast<const float *>(d_in), (long long)nsamples, d_out, (hipStream_t)stream));
+    PDDC_HIP_TRY(launch_pack24(static_cast<const float *>(d_in), (long long)nsamples, d_out, (hipStream_t)stream));
     return PDDC_OK;
 }
 
@@ -738,7 +742,7 @@ int pddc_synth_lcg(void *d_dst, size_t nbytes, uint32_t seed, uint64_t byte_offs
         return rc;
     if (nbytes && (!d_dst || ((uintptr_t)d_dst & 15)))
         return fail(PDDC_EINVAL, "destination must be a 16-byte aligned device pointer");
-    HIP_TRY(launch_synth_lcg(d_dst, nbytes, seed, byte_offset, (hipStream_t)stream));
+    PDDC_HIP_TRY(launch_synth_lcg(d_dst, nbytes, seed, byte_offset, (hipStream_t)stream));
     return PDDC_OK;
 }
 
@@ -773,7 +777,7 @@ int pddc_pipeline_create(pddc_pipeline **out, int device, const pddc_stage_desc 
     int ndev = pddc_device_count();
     if (device < 0 || device >= ndev)
         return fail(PDDC_ENODEV, "device %d out of range (0..%d)", device, ndev - 1);
-    HIP_TRY(hipSetDevice(device));
+    PDDC_HIP_TRY(hipSetDevice(device));
 
     pddc_pipeline *p = new (std::nothrow) pddc_pipeline();
     if (!p)
@@ -961,8 +965,8 @@ int pddc_pipeline_reset(pddc_pipeline *p)
 {
     if (!p)
         return fail(PDDC_EINVAL, "null pipeline");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
+    PDDC_HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());
     p->n0 = 0;
     p->phase_off = 0;
     p->freg_applied = p->freg;
@@ -972,15 +976,15 @@ int pddc_pipeline_reset(pddc_pipeline *p)
     p->carry_pending = false;                         /* a reset stream has no tail to finish */
     p->ov_parity = 0;
     p->segs.assign(1, pddc_pipeline::WordSeg{ 0, p->freg, 0u });      /* samples before the start are zeros */
-    HIP_TRY(hipMemset(p->d_sched, 0, 64));
+    PDDC_HIP_TRY(hipMemset(p->d_sched, 0, 64));
     if (p->d_flags)
-        HIP_TRY(hipMemset(p->d_flags, 0, sizeof(unsigned) * (size_t)fir8_fused3_max_chunks()));
+        PDDC_HIP_TRY(hipMemset(p->d_flags, 0, sizeof(unsigned) * (size_t)fir8_fused3_max_chunks()));
     for (int i = 0; i < p->nstages; ++i) {
         Stage &s = p->st[i];
         s.consumed = 0;
         s.cur = 0;
         for (int b = 0; b < 2; ++b)
-            HIP_TRY(hipMemset(s.d_hist[b], 0, (size_t)s.hist * (size_t)s.hist_elem + 64));
+            PDDC_HIP_TRY(hipMemset(s.d_hist[b], 0, (size_t)s.hist * (size_t)s.hist_elem + 64));
     }
     return PDDC_OK;
 }
@@ -1134,8 +1138,8 @@ int pddc_pipeline_set_taps(pddc_pipeline *p, int stage, const float *taps, int n
         return fail(PDDC_EINVAL, "ntaps %d does not fit the stage geometry (history %d)", ntaps, s.hist);
     if (s.interp <= 1 && !fir_generic_supported(s.decim, ntaps))
         return fail(PDDC_EINVAL, "decimate-by-%d with %d taps does not fit the LDS", s.decim, ntaps);
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
+    PDDC_HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());
     const int keep_ntb = s.ntb;
     s.ntaps = ntaps;
     s.taps.assign(taps, taps + ntaps);
@@ -1159,8 +1163,8 @@ int pddc_pipeline_set_taps(pddc_pipeline *p, int stage, const float *taps, int n
             }
         hipFree(s.d_taps_blk);
         s.d_taps_blk = nullptr;
-        HIP_TRY(hipMalloc(&s.d_taps_blk, sizeof(float) * blk.size()));
-        HIP_TRY(hipMemcpy(s.d_taps_blk, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
+        PDDC_HIP_TRY(hipMalloc(&s.d_taps_blk, sizeof(float) * blk.size()));
+        PDDC_HIP_TRY(hipMemcpy(s.d_taps_blk, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
     }
     if (stage <= 2)
         return setup_stage3(p);
@@ -1421,11 +1425,11 @@ static int i8x_prepare(pddc_pipeline *p, bool mix, bool fuse2, hipStream_t s, Fi
     if (!(x.cur >= 0 && x.freg == word && x.mix == mix && x.fuse2 == fuse2 && x.taps_ver == p->taps_ver && x.stream == s)) {
         if (x.cur >= 0) {
             if (x.stream == s) {
-                HIP_TRY(hipEventRecord(x.slot[x.cur].left, s));
+                PDDC_HIP_TRY(hipEventRecord(x.slot[x.cur].left, s));
                 x.slot[x.cur].left_valid = true;
             } else {
                 /* another stream (joining or leaving a gang): whatever reads the old tables there has to be through */
-                HIP_TRY(hipDeviceSynchronize());
+                PDDC_HIP_TRY(hipDeviceSynchronize());
                 for (auto &sl : x.slot)
                     sl.left_valid = false;
             }
@@ -1433,12 +1437,12 @@ static int i8x_prepare(pddc_pipeline *p, bool mix, bool fuse2, hipStream_t s, Fi
         const int nx = (x.cur + 1) & 3;
         pddc_pipeline::I8xSlot &sl = x.slot[nx];
         if (!sl.d) {
-            HIP_TRY(hipMalloc(&sl.d, kI8xSlotBytes));
-            HIP_TRY(hipHostMalloc(&sl.h, kI8xSlotBytes, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&sl.left, hipEventDisableTiming));
+            PDDC_HIP_TRY(hipMalloc(&sl.d, kI8xSlotBytes));
+            PDDC_HIP_TRY(hipHostMalloc(&sl.h, kI8xSlotBytes, hipHostMallocDefault));
+            PDDC_HIP_TRY(hipEventCreateWithFlags(&sl.left, hipEventDisableTiming));
         }
         if (sl.left_valid) {
-            HIP_TRY(hipEventSynchronize(sl.left));
+            PDDC_HIP_TRY(hipEventSynchronize(sl.left));
             sl.left_valid = false;
         }
         if (fir_i8x_table_bytes(s0.hist, mix) > kI8xTaps2Off)
@@ -1452,7 +1456,7 @@ static int i8x_prepare(pddc_pipeline *p, bool mix, bool fuse2, hipStream_t s, Fi
         /* (binary16-stored taps, no NCO: the matrix waves quantise the device's binary16 array themselves -- no table goes
          * to the device; the host's serves for scale and offset constant only) */
         if (!(s0.d_taps_f16 && !mix) || fuse2)
-            HIP_TRY(hipMemcpyAsync(sl.d, sl.h, kI8xSlotBytes, hipMemcpyHostToDevice, s));
+            PDDC_HIP_TRY(hipMemcpyAsync(sl.d, sl.h, kI8xSlotBytes, hipMemcpyHostToDevice, s));
         x.cur = nx;
         x.freg = word;
         x.mix = mix;
@@ -1489,11 +1493,11 @@ static int i8x_d10_prepare(pddc_pipeline *p, int delay, hipStream_t s, FirI8xArg
             /* a retune or new taps: the set in use stays where it is for the launches already queued -- an event behind them --
              * and the new one goes into the other buffer */
             if (e.stream == s) {
-                HIP_TRY(hipEventRecord(e.buf[e.cur].left, s));
+                PDDC_HIP_TRY(hipEventRecord(e.buf[e.cur].left, s));
                 e.buf[e.cur].left_valid = true;
             } else {
                 /* another stream (joining or leaving a gang): whatever reads the old tables there has to be through */
-                HIP_TRY(hipDeviceSynchronize());
+                PDDC_HIP_TRY(hipDeviceSynchronize());
                 for (auto &b : e.buf)
                     b.left_valid = false;
             }
@@ -1501,18 +1505,18 @@ static int i8x_d10_prepare(pddc_pipeline *p, int delay, hipStream_t s, FirI8xArg
         }
         pddc_pipeline::I8xSlot &b = e.buf[e.cur];
         if (!b.d) {
-            HIP_TRY(hipMalloc(&b.d, nb));
-            HIP_TRY(hipHostMalloc(&b.h, nb, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&b.left, hipEventDisableTiming));
+            PDDC_HIP_TRY(hipMalloc(&b.d, nb));
+            PDDC_HIP_TRY(hipHostMalloc(&b.h, nb, hipHostMallocDefault));
+            PDDC_HIP_TRY(hipEventCreateWithFlags(&b.left, hipEventDisableTiming));
         }
         if (b.left_valid) {
-            HIP_TRY(hipEventSynchronize(b.left));
+            PDDC_HIP_TRY(hipEventSynchronize(b.left));
             b.left_valid = false;
         }
         e.valid = false;
         if (!fir_i8x_d10_build_tables(s0.taps.data(), s0.ntaps, delay, p->freg, static_cast<int8_t *>(b.h), &e.scale, e.ct))
             return fail(PDDC_EINVAL, "k_fir_i8x: the taps cannot be quantised (all zero, or not finite)");
-        HIP_TRY(hipMemcpyAsync(b.d, b.h, nb, hipMemcpyHostToDevice, s));
+        PDDC_HIP_TRY(hipMemcpyAsync(b.d, b.h, nb, hipMemcpyHostToDevice, s));
         e.freg = p->freg;
         e.taps_ver = p->taps_ver;
         e.stream = s;
@@ -1551,18 +1555,18 @@ static int setup_stage3(pddc_pipeline *p)
     std::vector<float> seg((size_t)q.spl * q.seglen, 0.0f);
     std::copy(s2.taps.begin(), s2.taps.begin() + s2.ntaps, seg.begin());
     if (s2.d_taps_seg)
-        HIP_TRY(hipFree(s2.d_taps_seg));
+        PDDC_HIP_TRY(hipFree(s2.d_taps_seg));
     s2.d_taps_seg = nullptr;
-    HIP_TRY(hipMalloc(&s2.d_taps_seg, sizeof(float) * seg.size()));
-    HIP_TRY(hipMemcpy(s2.d_taps_seg, seg.data(), sizeof(float) * seg.size(), hipMemcpyHostToDevice));
+    PDDC_HIP_TRY(hipMalloc(&s2.d_taps_seg, sizeof(float) * seg.size()));
+    PDDC_HIP_TRY(hipMemcpy(s2.d_taps_seg, seg.data(), sizeof(float) * seg.size(), hipMemcpyHostToDevice));
     const size_t nch = (size_t)fir8_fused3_max_chunks();
     if (p->d_seam)
-        HIP_TRY(hipFree(p->d_seam));
+        PDDC_HIP_TRY(hipFree(p->d_seam));
     p->d_seam = nullptr;
-    HIP_TRY(hipMalloc(&p->d_seam, nch * (size_t)q.seam_stride));
+    PDDC_HIP_TRY(hipMalloc(&p->d_seam, nch * (size_t)q.seam_stride));
     if (!p->d_flags) {
-        HIP_TRY(hipMalloc((void **)&p->d_flags, sizeof(unsigned) * nch));
-        HIP_TRY(hipMemset(p->d_flags, 0, sizeof(unsigned) * nch));
+        PDDC_HIP_TRY(hipMalloc((void **)&p->d_flags, sizeof(unsigned) * nch));
+        PDDC_HIP_TRY(hipMemset(p->d_flags, 0, sizeof(unsigned) * nch));
     }
     p->s3 = q;
     p->s3_ok = true;
@@ -1575,10 +1579,10 @@ extern "C" int pddc_pipeline_check(pddc_pipeline *p, void *stream)
 {
     if (!p)
         return fail(PDDC_EINVAL, "null pipeline");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    PDDC_HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     unsigned w[4] = { 0, 0, 0, 0 };
-    HIP_TRY(hipMemcpy(w, p->d_sched, sizeof(w), hipMemcpyDeviceToHost));
+    PDDC_HIP_TRY(hipMemcpy(w, p->d_sched, sizeof(w), hipMemcpyDeviceToHost));
     if (w[2] != 0)
         return fail(PDDC_EHIP, "fused cascade: a block gave up waiting for the chunk in front of it (code %u)", w[2]);
     return PDDC_OK;
@@ -1595,12 +1599,12 @@ static int ensure_buf(Stage &s, size_t need, const void * = nullptr, size_t = 0)
         return fail(PDDC_ECAPACITY, "batch needs %zu samples of stage buffer, the workspace was sized for %zu", need,
                     s.buf_cap);
     const size_t cap = need + need / 4 + 64;
-    HIP_TRY(hipDeviceSynchronize());
+    PDDC_HIP_TRY(hipDeviceSynchronize());
     if (s.d_buf)
-        HIP_TRY(hipFree(s.d_buf));
+        PDDC_HIP_TRY(hipFree(s.d_buf));
     s.d_buf = nullptr;
     s.buf_cap = 0;
-    HIP_TRY(hipMalloc(&s.d_buf, sizeof(float) * 2 * cap));
+    PDDC_HIP_TRY(hipMalloc(&s.d_buf, sizeof(float) * 2 * cap));
     s.buf_cap = cap;
     if (tunables().debug.load())
         fprintf(stderr, "[pddc] stage buffer %p (%zu samples) hist %p %p\n", (void *)s.d_buf, cap, s.d_hist[0],
@@ -1638,15 +1642,15 @@ extern "C" int pddc_pipeline_set_workspace(pddc_pipeline *p, void *d_ws, size_t 
     if (d_ws && (((uintptr_t)d_ws & 255) || nbytes < pddc_pipeline_workspace_size(p, max_nsamples)))
         return fail(PDDC_EINVAL, "workspace must be 256-byte aligned and hold pddc_pipeline_workspace_size() = %zu bytes",
                     pddc_pipeline_workspace_size(p, max_nsamples));
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());                 /* nothing in flight may still use the old buffers */
+    PDDC_HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());                 /* nothing in flight may still use the old buffers */
     uint8_t *at = static_cast<uint8_t *>(d_ws);
     for (int i = 1; i < p->nstages; ++i) {
         Stage &s = p->st[i];
         if (s.d_buf && !s.buf_in_ws)
-            HIP_TRY(hipFree(s.d_buf));
+            PDDC_HIP_TRY(hipFree(s.d_buf));
         if (s.d_buf_alt && !s.buf_in_ws)
-            HIP_TRY(hipFree(s.d_buf_alt));
+            PDDC_HIP_TRY(hipFree(s.d_buf_alt));
         s.d_buf = s.d_buf_alt = nullptr;
         s.buf_cap = s.buf_alt_cap = 0;
         s.buf_in_ws = false;
@@ -1679,8 +1683,8 @@ int pddc_pipeline_place_buffers(pddc_pipeline *p, const void *d_packed, size_t m
         return fail(PDDC_EINVAL, "bad argument");
     if (p->carry_pending)
         return fail(PDDC_ESTATE, "overlap mode holds a tail back: pddc_pipeline_fence(p, stream) first");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
+    PDDC_HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());
     const void *src = d_packed;
     size_t src_bytes = max_nsamples * 6;
     for (int i = 1; i < p->nstages; ++i) {
@@ -1698,7 +1702,7 @@ int pddc_pipeline_place_buffers(pddc_pipeline *p, const void *d_packed, size_t m
             if (rc)
                 return rc;
             if (s.d_buf)
-                HIP_TRY(hipFree(s.d_buf));
+                PDDC_HIP_TRY(hipFree(s.d_buf));
             s.d_buf = static_cast<float *>(ptr);
             s.buf_cap = cap;
             if (tunables().debug.load())
@@ -1739,8 +1743,8 @@ int pddc_pipeline_fence(pddc_pipeline *p, void *stream)
     if (!p)
         return fail(PDDC_EINVAL, "null pipeline");
     if (p->carry_pending) {
-        HIP_TRY(hipSetDevice(p->device));
-        HIP_TRY(launch_gen_tail(p->carry_tail, (hipStream_t)stream));
+        PDDC_HIP_TRY(hipSetDevice(p->device));
+        PDDC_HIP_TRY(launch_gen_tail(p->carry_tail, (hipStream_t)stream));
         p->carry_pending = false;
     }
     return PDDC_OK;
@@ -1756,13 +1760,13 @@ static int stage0_event(pddc_pipeline *p, hipStream_t s, bool start)
             if (p->ev_pool.size() >= 8192)
                 return PDDC_OK;                       /* enough samples: stop recording */
             hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
+            PDDC_HIP_TRY(hipEventCreate(&a));
+            PDDC_HIP_TRY(hipEventCreate(&b));
             p->ev_pool.emplace_back(a, b);
         }
-        HIP_TRY(hipEventRecord(p->ev_pool[p->ev_used].first, s));
+        PDDC_HIP_TRY(hipEventRecord(p->ev_pool[p->ev_used].first, s));
     } else if (p->ev_used < p->ev_pool.size()) {
-        HIP_TRY(hipEventRecord(p->ev_pool[p->ev_used].second, s));
+        PDDC_HIP_TRY(hipEventRecord(p->ev_pool[p->ev_used].second, s));
         p->ev_used++;
     }
     return PDDC_OK;
@@ -1817,12 +1821,12 @@ static int stage_dst(pddc_pipeline *p, int i, const BatchPlan &b, void *d_out, h
     } else if (p->flags & PDDC_F_OUT_PACKED24) {
         const size_t n_final = b.n_in[p->nstages];
         if (p->d_fout_cap < n_final + 8) {
-            HIP_TRY(hipDeviceSynchronize());
+            PDDC_HIP_TRY(hipDeviceSynchronize());
             if (p->d_fout)
-                HIP_TRY(hipFree(p->d_fout));
+                PDDC_HIP_TRY(hipFree(p->d_fout));
             p->d_fout = nullptr;
             p->d_fout_cap = 0;
-            HIP_TRY(hipMalloc(&p->d_fout, (n_final + n_final / 4 + 64) * 8));
+            PDDC_HIP_TRY(hipMalloc(&p->d_fout, (n_final + n_final / 4 + 64) * 8));
             p->d_fout_cap = n_final + n_final / 4 + 64;
         }
         *dst = p->d_fout;
@@ -1857,12 +1861,12 @@ static int carry_setup(pddc_pipeline *p, int ti, const BatchPlan &b, void *d_out
                 if (rf)
                     return rf;
             }
-            HIP_TRY(hipDeviceSynchronize());
+            PDDC_HIP_TRY(hipDeviceSynchronize());
             if (sl.d_buf_alt)
-                HIP_TRY(hipFree(sl.d_buf_alt));
+                PDDC_HIP_TRY(hipFree(sl.d_buf_alt));
             sl.d_buf_alt = nullptr;
             sl.buf_alt_cap = 0;
-            HIP_TRY(hipMalloc(&sl.d_buf_alt, sizeof(float) * 2 * sl.buf_cap));
+            PDDC_HIP_TRY(hipMalloc(&sl.d_buf_alt, sizeof(float) * 2 * sl.buf_cap));
             sl.buf_alt_cap = sl.buf_cap;
         }
         *dst_first = sl.d_buf_alt;
@@ -2100,7 +2104,7 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
         if ((rc = ensure_buf(st, nsamples + 8)))
             return rc;
         if (!p->d_hist_f32)
-            HIP_TRY(hipMalloc(&p->d_hist_f32, (size_t)PDDC_MAX_TAPS * 8 + 256));
+            PDDC_HIP_TRY(hipMalloc(&p->d_hist_f32, (size_t)PDDC_MAX_TAPS * 8 + 256));
         const long long w0 = (long long)p->n0 - H;
         for (size_t k = 0; k < p->segs.size(); ++k) {
             const long long a0 = std::max(w0, k == 0 ? w0 : p->segs[k].n_begin);
@@ -2110,28 +2114,28 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
                 continue;
             float lc[8], ls[8];
             lo_steps(p->segs[k].freg, lc, ls);
-            HIP_TRY(launch_unpack24(static_cast<const uint8_t *>(h_in) + (a0 - w0) * PDDC_PACKED_BYTES, a1 - a0,
-                                    p->d_hist_f32 + 2 * (a0 - w0), false, true, (unsigned long long)a0,
-                                    p->segs[k].freg, p->segs[k].off, lc, ls, s));
+            PDDC_HIP_TRY(launch_unpack24(static_cast<const uint8_t *>(h_in) + (a0 - w0) * PDDC_PACKED_BYTES, a1 - a0,
+                                         p->d_hist_f32 + 2 * (a0 - w0), false, true, (unsigned long long)a0,
+                                         p->segs[k].freg, p->segs[k].off, lc, ls, s));
         }
-        HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, true, p->n0, p->freg, p->phase_off,
-                                p->lo_c, p->lo_s, s));
+        PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, true, p->n0, p->freg, p->phase_off,
+                                     p->lo_c, p->lo_s, s));
         if (n_in[1] > 0)
-            HIP_TRY(launch_fir_generic(st.d_buf, p->d_hist_f32, H, (long long)off[0], (long long)n_in[1], st.decim,
-                                       st.d_taps_dup, st.ntaps, dst, nullptr, (long long)nsamples, s));
+            PDDC_HIP_TRY(launch_fir_generic(st.d_buf, p->d_hist_f32, H, (long long)off[0], (long long)n_in[1], st.decim,
+                                            st.d_taps_dup, st.ntaps, dst, nullptr, (long long)nsamples, s));
         /* hist_done stays false: the packed history moves on below (x == d_packed) */
     } else if (i == 0 && route == Route::PackedGeneric) {
         if (n_in[1] > 0) {
             if (st.d_taps_firp)           /* register-blocked kernel for /4 /5 /8 /10 */
-                HIP_TRY(launch_firp_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1], st.decim,
-                                           st.d_taps_firp, st.ntaps, dst, h_out, (long long)nsamples, mix, p->n0,
-                                           p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s, p->lo_c_applied,
-                                           p->lo_s_applied, s));
+                PDDC_HIP_TRY(launch_firp_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1], st.decim,
+                                                st.d_taps_firp, st.ntaps, dst, h_out, (long long)nsamples, mix, p->n0,
+                                                p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s, p->lo_c_applied,
+                                                p->lo_s_applied, s));
             else
-                HIP_TRY(launch_fir_generic_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1],
-                                                  st.decim, st.d_taps_dup, st.ntaps, dst, h_out, (long long)nsamples,
-                                                  mix, p->n0, p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s,
-                                                  p->lo_c_applied, p->lo_s_applied, s));
+                PDDC_HIP_TRY(launch_fir_generic_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1],
+                                                       st.decim, st.d_taps_dup, st.ntaps, dst, h_out, (long long)nsamples,
+                                                       mix, p->n0, p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s,
+                                                       p->lo_c_applied, p->lo_s_applied, s));
             hist_done = true;             /* block 0 of the kernel wrote the new (packed) history */
         }
     } else {
@@ -2139,8 +2143,8 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
             /* generic first stage: unpack(+mix) to float2, then the generic FIR */
             if ((rc = ensure_buf(st, nsamples + 8)))
                 return rc;
-            HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, mix, p->n0, p->freg,
-                                    p->phase_off, p->lo_c, p->lo_s, s));
+            PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, mix, p->n0, p->freg,
+                                         p->phase_off, p->lo_c, p->lo_s, s));
         }
         x = st.d_buf;
         const bool fast = i > 0 && st.ntb != 0 && !(p->flags & PDDC_F_NO_FAST) &&
@@ -2155,34 +2159,34 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
             a.taps_blk = st.d_taps_blk;
             a.n_in = (long long)n_in[i];
             fill_fir8_args(p, a);
-            HIP_TRY(launch_fir8(st.ntb, p->R, IN_F32C, false, a, s));
+            PDDC_HIP_TRY(launch_fir8(st.ntb, p->R, IN_F32C, false, a, s));
             hist_done = a.hist_out != nullptr;
         } else if (st.interp > 1) {
             if (n_in[i + 1] > 0 && st.d_taps_poly && !(p->flags & PDDC_F_NO_FAST)) {
-                HIP_TRY(launch_resample_lds(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
-                                            st.consumed, b.m0[i], (long long)n_in[i + 1], st.interp, st.decim,
-                                            st.d_taps_poly, st.poly_k, st.poly_kp, dst, static_cast<float *>(h_out),
-                                            (long long)n_in[i], s));
+                PDDC_HIP_TRY(launch_resample_lds(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
+                                                 st.consumed, b.m0[i], (long long)n_in[i + 1], st.interp, st.decim,
+                                                 st.d_taps_poly, st.poly_k, st.poly_kp, dst, static_cast<float *>(h_out),
+                                                 (long long)n_in[i], s));
                 hist_done = true;
             } else if (n_in[i + 1] > 0) {
-                HIP_TRY(launch_resample(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
-                                        st.consumed, b.m0[i], (long long)n_in[i + 1], st.interp, st.decim,
-                                        st.d_taps, st.ntaps, dst, s));
+                PDDC_HIP_TRY(launch_resample(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
+                                             st.consumed, b.m0[i], (long long)n_in[i + 1], st.interp, st.decim,
+                                             st.d_taps, st.ntaps, dst, s));
             }
         } else if (n_in[i + 1] > 0) {
             if (st.d_taps_firp)
-                HIP_TRY(launch_firp(IN_F32C, false, x, h_in, st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
-                                    st.d_taps_firp, st.ntaps, dst, h_out, (long long)n_in[i], nullptr, s));
+                PDDC_HIP_TRY(launch_firp(IN_F32C, false, x, h_in, st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
+                                         st.d_taps_firp, st.ntaps, dst, h_out, (long long)n_in[i], nullptr, s));
             else
-                HIP_TRY(launch_fir_generic(static_cast<const float *>(x), static_cast<const float *>(h_in),
-                                           st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
-                                           st.d_taps_dup, st.ntaps, dst, static_cast<float *>(h_out),
-                                           (long long)n_in[i], s));
+                PDDC_HIP_TRY(launch_fir_generic(static_cast<const float *>(x), static_cast<const float *>(h_in),
+                                                st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
+                                                st.d_taps_dup, st.ntaps, dst, static_cast<float *>(h_out),
+                                                (long long)n_in[i], s));
             hist_done = true;             /* block 0 of the kernel wrote the new history */
         }
     }
     if (n_in[i] > 0 && !hist_done)
-        HIP_TRY(launch_hist_update(h_out, h_in, st.hist, x, (long long)n_in[i], st.hist_elem, s));
+        PDDC_HIP_TRY(launch_hist_update(h_out, h_in, st.hist, x, (long long)n_in[i], st.hist_elem, s));
     return PDDC_OK;
 }
 
@@ -2221,7 +2225,7 @@ static int process_batch(pddc_pipeline *p, const void *d_packed, size_t nsamples
         return fail(PDDC_EINVAL, "nsamples (%zu) must be a multiple of %d", nsamples, PDDC_INPUT_GRANULE);
     if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
         return fail(PDDC_EINVAL, "device pointers must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipSetDevice(p->device));
 
     BatchPlan b;
     plan_batch(p, nsamples, b);
@@ -2246,7 +2250,7 @@ static int process_batch(pddc_pipeline *p, const void *d_packed, size_t nsamples
         } else {
             if ((rc = stage0_event(p, s, true)))
                 return rc;
-            HIP_TRY(launch_first(r, s));
+            PDDC_HIP_TRY(launch_first(r, s));
             if (r.hold_tail)
                 p->carry_pending = false;   /* the previous tail went out with this launch (only once it was accepted) */
             if ((rc = stage0_event(p, s, false)))
@@ -2254,8 +2258,8 @@ static int process_batch(pddc_pipeline *p, const void *d_packed, size_t nsamples
         }
         Stage &s0 = p->st[0];
         if (nsamples < (size_t)s0.hist)     /* the kernel wrote no history (build_first): it moves on here */
-            HIP_TRY(launch_hist_update(s0.d_hist[s0.cur ^ 1], s0.d_hist[s0.cur], s0.hist, d_packed, (long long)nsamples,
-                                       s0.hist_elem, s));
+            PDDC_HIP_TRY(launch_hist_update(s0.d_hist[s0.cur ^ 1], s0.d_hist[s0.cur], s0.hist, d_packed, (long long)nsamples,
+                                            s0.hist_elem, s));
         next = r.stages;
     } else if ((rc = pddc_pipeline_fence(p, s))) {
         return rc;                          /* the stages run in line: what is held back goes first */
@@ -2264,7 +2268,7 @@ static int process_batch(pddc_pipeline *p, const void *d_packed, size_t nsamples
         if ((rc = run_stage(p, i, rt.route, b, d_packed, d_out, s)))
             return rc;
     if (p->flags & PDDC_F_OUT_PACKED24)
-        HIP_TRY(launch_pack24(p->d_fout, (long long)n_final, d_out, s));
+        PDDC_HIP_TRY(launch_pack24(p->d_fout, (long long)n_final, d_out, s));
 
     if (r.hold_tail) {                      /* this batch's last stage is held back for the next launch */
         p->carry_tail = r.tail;
@@ -2299,7 +2303,7 @@ int pddc_host_alloc(void **h_ptr, size_t nbytes)
 int pddc_host_free(void *h_ptr)
 {
     if (h_ptr)
-        HIP_TRY(hipHostFree(h_ptr));
+        PDDC_HIP_TRY(hipHostFree(h_ptr));
     return PDDC_OK;
 }
 
@@ -2307,29 +2311,29 @@ int pddc_host_free(void *h_ptr)
 static int prep_slot(pddc_pipeline *p, pddc_pipeline::HostSlot &sl, size_t nsamples)
 {
     if (!sl.ev_in) {
-        HIP_TRY(hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sl.ev_comp, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming));
+        PDDC_HIP_TRY(hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
+        PDDC_HIP_TRY(hipEventCreateWithFlags(&sl.ev_comp, hipEventDisableTiming));
+        PDDC_HIP_TRY(hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming));
     }
     const size_t max_out = pddc_pipeline_max_output(p, nsamples) + 1;
     if (sl.in_cap < nsamples || sl.out_cap < max_out) {
         if (sl.used)                          /* growing a slot: its last batch must be out first */
             if (sl.ev_wait)                     /* (nullptr: known complete) */
-                HIP_TRY(hipEventSynchronize(sl.ev_wait));
+                PDDC_HIP_TRY(hipEventSynchronize(sl.ev_wait));
         if (sl.in_cap < nsamples) {
             if (sl.d_in)
-                HIP_TRY(hipFree(sl.d_in));
+                PDDC_HIP_TRY(hipFree(sl.d_in));
             sl.d_in = nullptr;
             sl.in_cap = 0;
-            HIP_TRY(hipMalloc(&sl.d_in, nsamples * 6 + 64));
+            PDDC_HIP_TRY(hipMalloc(&sl.d_in, nsamples * 6 + 64));
             sl.in_cap = nsamples;
         }
         if (sl.out_cap < max_out) {
             if (sl.d_out)
-                HIP_TRY(hipFree(sl.d_out));
+                PDDC_HIP_TRY(hipFree(sl.d_out));
             sl.d_out = nullptr;
             sl.out_cap = 0;
-            HIP_TRY(hipMalloc(&sl.d_out, max_out * 8 + 64));
+            PDDC_HIP_TRY(hipMalloc(&sl.d_out, max_out * 8 + 64));
             sl.out_cap = max_out;
         }
     }
@@ -2355,7 +2359,7 @@ static int leave_gang(pddc_pipeline *p)
     if (!g)
         return PDDC_OK;
     std::lock_guard<std::mutex> lk(g->lock);
-    HIP_TRY(hipStreamSynchronize(g->stream));
+    PDDC_HIP_TRY(hipStreamSynchronize(g->stream));
     g->members.erase(std::remove(g->members.begin(), g->members.end(), p), g->members.end());
     p->gang = nullptr;
     forget_gang_events(p, g);
@@ -2386,13 +2390,13 @@ static int push_async(pddc_pipeline *p, const void *h_packed, bool synth, uint32
         if (need > out_capacity)
             return fail(PDDC_ECAPACITY, "output capacity %zu < %zu", out_capacity, need);
     }
-    HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipSetDevice(p->device));
     int rc0 = leave_gang(p);                  /* the batch before may have gone out with a gang, on the gang's stream */
     if (rc0)
         return rc0;
     if (!p->s_in) {
-        HIP_TRY(hipStreamCreateWithFlags(&p->s_in, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&p->s_out, hipStreamNonBlocking));
+        PDDC_HIP_TRY(hipStreamCreateWithFlags(&p->s_in, hipStreamNonBlocking));
+        PDDC_HIP_TRY(hipStreamCreateWithFlags(&p->s_out, hipStreamNonBlocking));
     }
     const int si = p->next_slot;
     pddc_pipeline::HostSlot &sl = p->slot[si];
@@ -2411,17 +2415,17 @@ static int push_async(pddc_pipeline *p, const void *h_packed, bool synth, uint32
     hipStream_t st_out = one_stream ? p->own_stream : p->s_out;
     /* H2D (or the generator): the slot's input buffer is free once the kernels of its previous batch are done */
     if (sl.used && (!one_stream || gen_aside))
-        HIP_TRY(hipStreamWaitEvent(st_in, sl.ev_comp, 0));
+        PDDC_HIP_TRY(hipStreamWaitEvent(st_in, sl.ev_comp, 0));
     if (synth)
-        HIP_TRY(launch_synth_lcg(sl.d_in, nsamples * 6, seed, byte_offset, st_in));
+        PDDC_HIP_TRY(launch_synth_lcg(sl.d_in, nsamples * 6, seed, byte_offset, st_in));
     else
-        HIP_TRY(hipMemcpyAsync(sl.d_in, h_packed, nsamples * 6, hipMemcpyHostToDevice, st_in));
+        PDDC_HIP_TRY(hipMemcpyAsync(sl.d_in, h_packed, nsamples * 6, hipMemcpyHostToDevice, st_in));
     if (!one_stream || gen_aside) {
-        HIP_TRY(hipEventRecord(sl.ev_in, st_in));
+        PDDC_HIP_TRY(hipEventRecord(sl.ev_in, st_in));
         /* kernels: after this batch has arrived and the slot's previous output has left */
-        HIP_TRY(hipStreamWaitEvent(p->own_stream, sl.ev_in, 0));
+        PDDC_HIP_TRY(hipStreamWaitEvent(p->own_stream, sl.ev_in, 0));
         if (sl.used && !one_stream)
-            HIP_TRY(hipStreamWaitEvent(p->own_stream, sl.ev_out, 0));
+            PDDC_HIP_TRY(hipStreamWaitEvent(p->own_stream, sl.ev_out, 0));
     }
     size_t n_out = 0;
     /* (one stream: the last stage writes into the caller's buffer itself where that is pinned memory, see direct_out) */
@@ -2434,15 +2438,15 @@ static int push_async(pddc_pipeline *p, const void *h_packed, bool synth, uint32
         return rc;
     if ((rc = pddc_pipeline_fence(p, p->own_stream)))     /* overlap mode: the D2H copy needs the tail's output */
         return rc;
-    HIP_TRY(hipEventRecord(sl.ev_comp, p->own_stream));
+    PDDC_HIP_TRY(hipEventRecord(sl.ev_comp, p->own_stream));
     sl.used = true;
     p->next_slot = si ^ 1;
     if (!one_stream)
-        HIP_TRY(hipStreamWaitEvent(st_out, sl.ev_comp, 0));
+        PDDC_HIP_TRY(hipStreamWaitEvent(st_out, sl.ev_comp, 0));
     if (n_out && !direct)
-        HIP_TRY(hipMemcpyAsync(h_out, sl.d_out, n_out * ((p->flags & PDDC_F_OUT_PACKED24) ? 6 : 8),
-                               hipMemcpyDeviceToHost, st_out));
-    HIP_TRY(hipEventRecord(sl.ev_out, st_out));
+        PDDC_HIP_TRY(hipMemcpyAsync(h_out, sl.d_out, n_out * ((p->flags & PDDC_F_OUT_PACKED24) ? 6 : 8),
+                                    hipMemcpyDeviceToHost, st_out));
+    PDDC_HIP_TRY(hipEventRecord(sl.ev_out, st_out));
     sl.ev_wait = sl.ev_out;
     if (n_out_ret)
         *n_out_ret = n_out;
@@ -2469,7 +2473,7 @@ int pddc_pipeline_ticket_done(pddc_pipeline *p, int ticket)
         return fail(PDDC_EINVAL, "bad ticket");
     if (!p->slot[ticket].used)
         return fail(PDDC_ESTATE, "nothing was pushed on ticket %d", ticket);
-    HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipSetDevice(p->device));
     if (!p->slot[ticket].ev_wait)
         return 1;                             /* complete (it went out with a gang this pipeline has left since) */
     hipError_t e = hipEventQuery(p->slot[ticket].ev_wait);
@@ -2486,9 +2490,9 @@ int pddc_pipeline_wait_ticket(pddc_pipeline *p, int ticket)
         return fail(PDDC_EINVAL, "bad ticket");
     if (!p->slot[ticket].used)
         return fail(PDDC_ESTATE, "nothing was pushed on ticket %d", ticket);
-    HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipSetDevice(p->device));
     if (p->slot[ticket].ev_wait)
-        HIP_TRY(hipEventSynchronize(p->slot[ticket].ev_wait));
+        PDDC_HIP_TRY(hipEventSynchronize(p->slot[ticket].ev_wait));
     return PDDC_OK;
 }
 
@@ -2504,15 +2508,15 @@ int pddc_pipeline_wait(pddc_pipeline *p)
 {
     if (!p)
         return fail(PDDC_EINVAL, "null pipeline");
-    HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipSetDevice(p->device));
     if (p->s_in)
-        HIP_TRY(hipStreamSynchronize(p->s_in));
-    HIP_TRY(hipStreamSynchronize(p->own_stream));
+        PDDC_HIP_TRY(hipStreamSynchronize(p->s_in));
+    PDDC_HIP_TRY(hipStreamSynchronize(p->own_stream));
     if (p->s_out)
-        HIP_TRY(hipStreamSynchronize(p->s_out));
+        PDDC_HIP_TRY(hipStreamSynchronize(p->s_out));
     if (p->gang) {
         std::lock_guard<std::mutex> lk(p->gang->lock);
-        HIP_TRY(hipStreamSynchronize(p->gang->stream));
+        PDDC_HIP_TRY(hipStreamSynchronize(p->gang->stream));
     }
     return PDDC_OK;
 }
@@ -2552,7 +2556,7 @@ int pddc_gang_create(pddc_gang **out, int device)
     int rc = require_device();
     if (rc)
         return rc;
-    HIP_TRY(hipSetDevice(device));
+    PDDC_HIP_TRY(hipSetDevice(device));
     pddc_gang *g = new (std::nothrow) pddc_gang;
     if (!g)
         return fail(PDDC_ENOMEM, "out of memory");
@@ -2634,7 +2638,7 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
             return fail(PDDC_ECAPACITY, "gang item %d: output capacity %zu < %zu", i, it.out_capacity, need);
         all_synth = all_synth && it.h_packed == nullptr;
     }
-    HIP_TRY(hipSetDevice(g->device));
+    PDDC_HIP_TRY(hipSetDevice(g->device));
     std::lock_guard<std::mutex> lk(g->lock);
     hipStream_t s = g->stream;
     int si[PDDC_GANG_MAX];
@@ -2674,21 +2678,21 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
                 if (!sl.used || !sl.ev_wait || std::find(seen, seen + nseen, sl.ev_wait) != seen + nseen)
                     continue;
                 seen[nseen++] = sl.ev_wait;
-                HIP_TRY(hipStreamWaitEvent(g->s_gen, sl.ev_wait, 0));
+                PDDC_HIP_TRY(hipStreamWaitEvent(g->s_gen, sl.ev_wait, 0));
             }
-            HIP_TRY(launch_synth_lcg_many(sm, n, nsamples * 6, g->s_gen));
-            HIP_TRY(hipEventRecord(g->ev_gen[g->next_ev], g->s_gen));
-            HIP_TRY(hipStreamWaitEvent(s, g->ev_gen[g->next_ev], 0));
+            PDDC_HIP_TRY(launch_synth_lcg_many(sm, n, nsamples * 6, g->s_gen));
+            PDDC_HIP_TRY(hipEventRecord(g->ev_gen[g->next_ev], g->s_gen));
+            PDDC_HIP_TRY(hipStreamWaitEvent(s, g->ev_gen[g->next_ev], 0));
         } else {
-            HIP_TRY(launch_synth_lcg_many(sm, n, nsamples * 6, s));
+            PDDC_HIP_TRY(launch_synth_lcg_many(sm, n, nsamples * 6, s));
         }
     } else {
         for (int i = 0; i < n; ++i) {
             pddc_pipeline::HostSlot &sl = items[i].pipe->slot[si[i]];
             if (items[i].h_packed)
-                HIP_TRY(hipMemcpyAsync(sl.d_in, items[i].h_packed, nsamples * 6, hipMemcpyHostToDevice, s));
+                PDDC_HIP_TRY(hipMemcpyAsync(sl.d_in, items[i].h_packed, nsamples * 6, hipMemcpyHostToDevice, s));
             else
-                HIP_TRY(launch_synth_lcg(sl.d_in, nsamples * 6, items[i].seed, items[i].byte_offset, s));
+                PDDC_HIP_TRY(launch_synth_lcg(sl.d_in, nsamples * 6, items[i].seed, items[i].byte_offset, s));
         }
     }
     /* every member plans its batch: the ones whose plan is "first-stage kernel [+ one plain decimator]" leave a record,
@@ -2741,12 +2745,12 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
             ++k;
         }
         if (x)
-            HIP_TRY(launch_fir_i8x_many(xm, k, rec[i].hist, rec[i].mix, rec[i].route == Route::I8xPair, s, rec[i].blocks,
-                                        rec[i].chunk, rec[i].layout));
+            PDDC_HIP_TRY(launch_fir_i8x_many(xm, k, rec[i].hist, rec[i].mix, rec[i].route == Route::I8xPair, s, rec[i].blocks,
+                                             rec[i].chunk, rec[i].layout));
         else
-            HIP_TRY(launch_fir8_many(rec[i].route == Route::Fir8Pair ? 2 : 1, rec[i].ntb, rec[i].R, rec[i].mix, fm, k, s));
+            PDDC_HIP_TRY(launch_fir8_many(rec[i].route == Route::Fir8Pair ? 2 : 1, rec[i].ntb, rec[i].R, rec[i].mix, fm, k, s));
         if (any_tail)
-            HIP_TRY(launch_gen_tail_many(tm, k, s));
+            PDDC_HIP_TRY(launch_gen_tail_many(tm, k, s));
         if (n_ganged)
             *n_ganged += k;
     }
@@ -2764,10 +2768,10 @@ int pddc_gang_push_async(pddc_gang *g, pddc_gang_item *items, int n, size_t nsam
         pddc_pipeline *p = items[i].pipe;
         pddc_pipeline::HostSlot &sl = p->slot[si[i]];
         if (items[i].n_out && !direct[i])
-            HIP_TRY(hipMemcpyAsync(items[i].h_out, sl.d_out, items[i].n_out * ((p->flags & PDDC_F_OUT_PACKED24) ? 6 : 8),
-                                   hipMemcpyDeviceToHost, s));
+            PDDC_HIP_TRY(hipMemcpyAsync(items[i].h_out, sl.d_out, items[i].n_out * ((p->flags & PDDC_F_OUT_PACKED24) ? 6 : 8),
+                                        hipMemcpyDeviceToHost, s));
     }
-    HIP_TRY(hipEventRecord(ev, s));
+    PDDC_HIP_TRY(hipEventRecord(ev, s));
     for (int i = 0; i < n; ++i) {
         pddc_pipeline *p = items[i].pipe;
         pddc_pipeline::HostSlot &sl = p->slot[si[i]];
@@ -2982,7 +2986,7 @@ int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void 
     }
     if (nsamples == 0)
         return PDDC_OK;
-    HIP_TRY(hipSetDevice(b->device));
+    PDDC_HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = (hipStream_t)stream_v;
     int groups[PDDC_BANK_MAX][kFirI8xBankMax], gsize[PDDC_BANK_MAX];
     unsigned mask = 0, was_al = 0;
@@ -3017,7 +3021,7 @@ int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void 
             const FirI8xArgs &q = rec[groups[g][c]].ax;
             fb.ch[c] = FirI8xBankCh{ q.atab, q.out, q.hist_out, q.scale, { q.ct[0], q.ct[1] }, q.hist_len, q.n0, q.freg, q.phase_off };
         }
-        HIP_TRY(r0.route == Route::I8xD10 ? launch_fir_i8x_bank_d10(fb, gsize[g], s) : launch_fir_i8x_bank(fb, gsize[g], r0.hist, s));
+        PDDC_HIP_TRY(r0.route == Route::I8xD10 ? launch_fir_i8x_bank_d10(fb, gsize[g], s) : launch_fir_i8x_bank(fb, gsize[g], r0.hist, s));
     }
     /* behind it, per member: the stages after the first, the commit -- process_batch's.  (A failure from here on -- a HIP
      * error, or one an unbanked member's own process_batch reports, such as its overlap workspace -- leaves the members
@@ -3027,8 +3031,8 @@ int pddc_bank_process(pddc_bank *b, const void *d_packed, size_t nsamples, void 
         if (mask >> i & 1) {
             Stage &s0 = p->st[0];
             if (nsamples < (size_t)s0.hist)         /* (decimate by 10: the kernel wrote no history -- build_first) */
-                HIP_TRY(launch_hist_update(s0.d_hist[s0.cur ^ 1], s0.d_hist[s0.cur], s0.hist, d_packed, (long long)nsamples,
-                                           s0.hist_elem, s));
+                PDDC_HIP_TRY(launch_hist_update(s0.d_hist[s0.cur ^ 1], s0.d_hist[s0.cur], s0.hist, d_packed, (long long)nsamples,
+                                                s0.hist_elem, s));
             for (int k = 1; k < p->nstages; ++k)
                 if ((rc = run_stage(p, k, rec[i].route, bp[i], d_packed, d_out[i], s)))
                     return rc;                      /* (members before this one have moved on: the stream is broken) */
@@ -3101,8 +3105,8 @@ int pddc_pipeline_save_state(pddc_pipeline *p, void *h_buf, size_t capacity, siz
         return fail(PDDC_ECAPACITY, "state needs %zu bytes, buffer has %zu", need, capacity);
     if (p->carry_pending)
         return fail(PDDC_ESTATE, "overlap mode holds a tail back: pddc_pipeline_fence(p, stream) first");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());                  /* every batch pushed so far is part of the state */
+    PDDC_HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());                  /* every batch pushed so far is part of the state */
     StateHeader h = {};
     h.magic = kStateMagic;
     h.version = 1;
@@ -3137,7 +3141,7 @@ int pddc_pipeline_save_state(pddc_pipeline *p, void *h_buf, size_t capacity, siz
     for (int i = 0; i < p->nstages; ++i) {
         const Stage &s = p->st[i];
         const size_t nb = (size_t)s.hist * (size_t)s.hist_elem;
-        HIP_TRY(hipMemcpy(w, s.d_hist[s.cur], nb, hipMemcpyDeviceToHost));
+        PDDC_HIP_TRY(hipMemcpy(w, s.d_hist[s.cur], nb, hipMemcpyDeviceToHost));
         w += nb;
     }
     return PDDC_OK;
@@ -3164,8 +3168,8 @@ int pddc_pipeline_restore_state(pddc_pipeline *p, const void *h_buf, size_t nbyt
     }
     if (nbytes < need || h.nsegs < 1 || h.nsegs > 4096)
         return fail(PDDC_EINVAL, "state buffer truncated (%zu of %zu bytes)", nbytes, need);
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipDeviceSynchronize());
+    PDDC_HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());
     const uint8_t *r = static_cast<const uint8_t *>(h_buf) + sizeof(StateHeader);
     p->segs.clear();
     for (uint32_t k = 0; k < h.nsegs; ++k) {
@@ -3179,7 +3183,7 @@ int pddc_pipeline_restore_state(pddc_pipeline *p, const void *h_buf, size_t nbyt
     for (int i = 0; i < p->nstages; ++i) {
         Stage &s = p->st[i];
         const size_t nb = (size_t)s.hist * (size_t)s.hist_elem;
-        HIP_TRY(hipMemcpy(s.d_hist[s.cur], r, nb, hipMemcpyHostToDevice));
+        PDDC_HIP_TRY(hipMemcpy(s.d_hist[s.cur], r, nb, hipMemcpyHostToDevice));
         s.consumed = h.st[i].consumed;
         r += nb;
     }
@@ -3206,12 +3210,12 @@ int pddc_pipeline_stage0_time(pddc_pipeline *p, float *avg_ms, int *nlaunches)
 {
     if (!p || !avg_ms)
         return fail(PDDC_EINVAL, "null argument");
-    HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipSetDevice(p->device));
     double sum = 0.0;
     for (size_t k = 0; k < p->ev_used; ++k) {
-        HIP_TRY(hipEventSynchronize(p->ev_pool[k].second));
+        PDDC_HIP_TRY(hipEventSynchronize(p->ev_pool[k].second));
         float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, p->ev_pool[k].first, p->ev_pool[k].second));
+        PDDC_HIP_TRY(hipEventElapsedTime(&ms, p->ev_pool[k].first, p->ev_pool[k].second));
         sum += ms;
     }
     *avg_ms = p->ev_used ? (float)(sum / (double)p->ev_used) : 0.0f;
@@ -3256,17 +3260,17 @@ int pddc_measure_copy(void *d_dst, const void *d_src, size_t nbytes, int iters, 
     if (((uintptr_t)d_dst | (uintptr_t)d_src | nbytes) & 15)
         return fail(PDDC_EINVAL, "copy measurement wants 16-byte aligned pointers and size");
     hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    PDDC_HIP_TRY(hipEventCreate(&e0));
+    PDDC_HIP_TRY(hipEventCreate(&e1));
     for (int i = 0; i < iters; ++i)                             /* as many untimed ones first: sustained clocks */
-        HIP_TRY(launch_stream_copy(d_src, d_dst, nbytes, s));
-    HIP_TRY(hipEventRecord(e0, s));
+        PDDC_HIP_TRY(launch_stream_copy(d_src, d_dst, nbytes, s));
+    PDDC_HIP_TRY(hipEventRecord(e0, s));
     for (int i = 0; i < iters; ++i)
-        HIP_TRY(launch_stream_copy(d_src, d_dst, nbytes, s));
-    HIP_TRY(hipEventRecord(e1, s));
-    HIP_TRY(hipEventSynchronize(e1));
+        PDDC_HIP_TRY(launch_stream_copy(d_src, d_dst, nbytes, s));
+    PDDC_HIP_TRY(hipEventRecord(e1, s));
+    PDDC_HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    PDDC_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     hipEventDestroy(e0);
     hipEventDestroy(e1);
     *avg_ms = ms / (float)iters;
@@ -3283,7 +3287,7 @@ int pddc_pipeline_time_stage0(pddc_pipeline *p, const void *d_packed, size_t nsa
     if (nsamples % PDDC_INPUT_GRANULE || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
         return fail(PDDC_EINVAL, "bad size/alignment");
     hipStream_t s = (hipStream_t)stream_v;
-    HIP_TRY(hipSetDevice(p->device));
+    PDDC_HIP_TRY(hipSetDevice(p->device));
     float *dst = static_cast<float *>(d_out);
     if (p->nstages > 1) {                  /* stage 0 (or the fused pair) of a cascade writes an internal buffer */
         int rc = ensure_buf(p->st[1], nsamples / (size_t)p->st[0].decim + 8);
@@ -3298,15 +3302,15 @@ int pddc_pipeline_time_stage0(pddc_pipeline *p, const void *d_packed, size_t nsa
     if (rc)
         return rc;
     hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, s));
+    PDDC_HIP_TRY(hipEventCreate(&e0));
+    PDDC_HIP_TRY(hipEventCreate(&e1));
+    PDDC_HIP_TRY(hipEventRecord(e0, s));
     for (int i = 0; i < iters; ++i)
-        HIP_TRY(launch_first(r, s));
-    HIP_TRY(hipEventRecord(e1, s));
-    HIP_TRY(hipEventSynchronize(e1));
+        PDDC_HIP_TRY(launch_first(r, s));
+    PDDC_HIP_TRY(hipEventRecord(e1, s));
+    PDDC_HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    PDDC_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     hipEventDestroy(e0);
     hipEventDestroy(e1);
     *avg_ms = ms / (float)iters;

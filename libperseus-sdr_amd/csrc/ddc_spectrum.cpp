@@ -1,8 +1,7 @@
 /*
- * ddc_spectrum.cpp -- host side of the panorama (include/perseus_ddc.h, pddc_spectrum_*): the object, its carried tail
- * and counters, and the two launches of a batch.  The kernels are in ddc_spectrum.hip.
+ * ddc_spectrum.cpp -- host side of the panorama (include/perseus_ddc.h, pddc_spectrum_*): the object, its counters, and
+ * the two launches of a batch.  The carried tail is a PackedCarry (ddc_packed.h); the kernels are in ddc_spectrum.hip.
  */
-#include "../../include/perseus_ddc.h"
 #include "ddc_spectrum.h"
 
 #include <new>
@@ -10,28 +9,13 @@
 
 using namespace pddc;
 
-extern "C" int pddc_set_error_(int code, const char *fmt, ...);
-
-#define SPEC_TRY(expr)                                                                                          \
-    do {                                                                                                        \
-        hipError_t e__ = (expr);                                                                                \
-        if (e__ != hipSuccess)                                                                                  \
-            return pddc_set_error_(e__ == hipErrorOutOfMemory ? PDDC_ENOMEM                                     \
-                                   : (e__ == hipErrorNoDevice || e__ == hipErrorInvalidDevice) ? PDDC_ENODEV    \
-                                                                                               : PDDC_EHIP,     \
-                                   "%s: %s", #expr, hipGetErrorString(e__));                                    \
-    } while (0)
-
 struct pddc_spectrum {
     int device = 0;
     int nfft = 0, hop = 0;
     uint32_t flags = 0;
     int max_blocks = 0;
     float *d_window = nullptr, *d_tw = nullptr;
-    uint8_t *d_tail[2] = { nullptr, nullptr };      /* nfft * 6 bytes each; process() reads [cur] and writes [cur ^ 1] */
-    int cur = 0;
-    uint64_t tail_len = 0;                          /* samples in d_tail[cur]                  */
-    uint64_t samples = 0;                           /* stream length since create / reset      */
+    PackedCarry in;                                 /* the carried tail (a window of nfft) and the stream length */
     uint64_t segments = 0;                          /* accumulated since the last clear        */
     float *d_part_sum = nullptr, *d_part_peak = nullptr;
     double *d_acc_sum = nullptr;
@@ -45,17 +29,11 @@ static bool spec_sizes_ok(int nfft, int hop)
     return hop == nfft || hop == nfft / 2;
 }
 
-static uint64_t spec_complete(int nfft, int hop, uint64_t len)
-{
-    return len >= (uint64_t)nfft ? (len - (uint64_t)nfft) / (uint64_t)hop + 1 : 0;
-}
-
 static void spec_free(pddc_spectrum *s)
 {
     hipFree(s->d_window);
     hipFree(s->d_tw);
-    hipFree(s->d_tail[0]);
-    hipFree(s->d_tail[1]);
+    s->in.free();
     hipFree(s->d_part_sum);
     hipFree(s->d_part_peak);
     hipFree(s->d_acc_sum);
@@ -66,26 +44,25 @@ static void spec_free(pddc_spectrum *s)
 static int spec_create(pddc_spectrum *s, const float *window)
 {
     const size_t n = (size_t)s->nfft;
-    SPEC_TRY(hipSetDevice(s->device));
+    PDDC_HIP_TRY(hipSetDevice(s->device));
     int ncu = 0;
-    SPEC_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, s->device));
+    PDDC_HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, s->device));
     s->max_blocks = spectrum_max_blocks(s->nfft, ncu > 0 ? ncu : 256);
     std::vector<float> tw((size_t)spectrum_twiddle_len(s->nfft));
     spectrum_build_twiddles(s->nfft, tw.data());
-    SPEC_TRY(hipMalloc(&s->d_window, n * sizeof(float)));
-    SPEC_TRY(hipMalloc(&s->d_tw, tw.size() * sizeof(float)));
-    SPEC_TRY(hipMalloc(&s->d_tail[0], n * 6));
-    SPEC_TRY(hipMalloc(&s->d_tail[1], n * 6));
-    SPEC_TRY(hipMalloc(&s->d_part_sum, (size_t)s->max_blocks * n * sizeof(float)));
-    SPEC_TRY(hipMalloc(&s->d_acc_sum, n * sizeof(double)));
+    PDDC_HIP_TRY(hipMalloc(&s->d_window, n * sizeof(float)));
+    PDDC_HIP_TRY(hipMalloc(&s->d_tw, tw.size() * sizeof(float)));
+    PDDC_HIP_TRY(s->in.alloc(n));
+    PDDC_HIP_TRY(hipMalloc(&s->d_part_sum, (size_t)s->max_blocks * n * sizeof(float)));
+    PDDC_HIP_TRY(hipMalloc(&s->d_acc_sum, n * sizeof(double)));
     if (s->flags & PDDC_SPEC_PEAK) {
-        SPEC_TRY(hipMalloc(&s->d_part_peak, (size_t)s->max_blocks * n * sizeof(float)));
-        SPEC_TRY(hipMalloc(&s->d_acc_peak, n * sizeof(float)));
-        SPEC_TRY(hipMemset(s->d_acc_peak, 0, n * sizeof(float)));
+        PDDC_HIP_TRY(hipMalloc(&s->d_part_peak, (size_t)s->max_blocks * n * sizeof(float)));
+        PDDC_HIP_TRY(hipMalloc(&s->d_acc_peak, n * sizeof(float)));
+        PDDC_HIP_TRY(hipMemset(s->d_acc_peak, 0, n * sizeof(float)));
     }
-    SPEC_TRY(hipMemcpy(s->d_window, window, n * sizeof(float), hipMemcpyHostToDevice));
-    SPEC_TRY(hipMemcpy(s->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
-    SPEC_TRY(hipMemset(s->d_acc_sum, 0, n * sizeof(double)));
+    PDDC_HIP_TRY(hipMemcpy(s->d_window, window, n * sizeof(float), hipMemcpyHostToDevice));
+    PDDC_HIP_TRY(hipMemcpy(s->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
+    PDDC_HIP_TRY(hipMemset(s->d_acc_sum, 0, n * sizeof(double)));
     return PDDC_OK;
 }
 
@@ -95,12 +72,12 @@ uint64_t pddc_spectrum_segments(int nfft, int hop, uint64_t samples_before, size
 {
     if (!spec_sizes_ok(nfft, hop))
         return 0;
-    return spec_complete(nfft, hop, samples_before + nsamples) - spec_complete(nfft, hop, samples_before);
+    return windows_complete(nfft, hop, samples_before + nsamples) - windows_complete(nfft, hop, samples_before);
 }
 
 uint64_t pddc_spectrum_next_segments(const pddc_spectrum *s, size_t nsamples)
 {
-    return s ? pddc_spectrum_segments(s->nfft, s->hop, s->samples, nsamples) : 0;
+    return s ? pddc_spectrum_segments(s->nfft, s->hop, s->in.samples, nsamples) : 0;
 }
 
 int pddc_spectrum_create(pddc_spectrum **out, int device, int nfft, int hop, const float *window, uint32_t flags)
@@ -115,13 +92,8 @@ int pddc_spectrum_create(pddc_spectrum **out, int device, int nfft, int hop, con
         return pddc_set_error_(PDDC_EINVAL, "spectrum: null window");
     if (flags & ~PDDC_SPEC_PEAK)
         return pddc_set_error_(PDDC_EINVAL, "spectrum: unknown flags 0x%x", flags);
-    const int ndev = pddc_device_count();
-    if (ndev < 0)
-        return ndev;
-    if (ndev == 0)
-        return pddc_set_error_(PDDC_ENODEV, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev)
-        return pddc_set_error_(PDDC_ENODEV, "device %d out of range (%d visible)", device, ndev);
+    if (const int rc = pddc_check_device_(device))
+        return rc;
     pddc_spectrum *s = new (std::nothrow) pddc_spectrum;
     if (!s)
         return pddc_set_error_(PDDC_ENOMEM, "out of memory");
@@ -152,13 +124,12 @@ int pddc_spectrum_reset(pddc_spectrum *s)
 {
     if (!s)
         return pddc_set_error_(PDDC_EINVAL, "null argument");
-    SPEC_TRY(hipSetDevice(s->device));
-    SPEC_TRY(hipDeviceSynchronize());
-    SPEC_TRY(hipMemset(s->d_acc_sum, 0, (size_t)s->nfft * sizeof(double)));
+    PDDC_HIP_TRY(hipSetDevice(s->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());
+    PDDC_HIP_TRY(hipMemset(s->d_acc_sum, 0, (size_t)s->nfft * sizeof(double)));
     if (s->d_acc_peak)
-        SPEC_TRY(hipMemset(s->d_acc_peak, 0, (size_t)s->nfft * sizeof(float)));
-    s->tail_len = 0;
-    s->samples = 0;
+        PDDC_HIP_TRY(hipMemset(s->d_acc_peak, 0, (size_t)s->nfft * sizeof(float)));
+    s->in.reset();
     s->segments = 0;
     return PDDC_OK;
 }
@@ -167,30 +138,25 @@ int pddc_spectrum_process(pddc_spectrum *s, const void *d_packed, size_t nsample
 {
     if (!s)
         return pddc_set_error_(PDDC_EINVAL, "null argument");
-    if (nsamples % 8)
-        return pddc_set_error_(PDDC_EINVAL, "nsamples (%zu) must be a multiple of 8", nsamples);
-    if (nsamples && (!d_packed || ((uintptr_t)d_packed & 15)))
-        return pddc_set_error_(PDDC_EINVAL, "d_packed must be a 16-byte aligned device pointer");
+    if (const int rc = PackedCarry::check(d_packed, nsamples))
+        return rc;
     if (!nsamples)
         return PDDC_OK;
-    SPEC_TRY(hipSetDevice(s->device));
-    const uint64_t len = s->tail_len + nsamples;           /* tail-then-batch */
-    const uint64_t nseg = spec_complete(s->nfft, s->hop, len);
-    const uint64_t keep_from = nseg * (uint64_t)s->hop;
+    PDDC_HIP_TRY(hipSetDevice(s->device));
+    const PackedCarry::Plan plan = s->in.plan(nsamples, s->nfft, s->hop);
+    const uint64_t nseg = plan.n_complete;
     const int blocks = (int)(nseg < (uint64_t)s->max_blocks ? nseg : (uint64_t)s->max_blocks);
     hipStream_t st = (hipStream_t)stream;
     if (nseg) {
         SpectrumArgs a{};
-        a.tail = s->d_tail[s->cur];
-        a.batch = static_cast<const uint8_t *>(d_packed);
-        a.tail_len = (long long)s->tail_len;
+        a.in = s->in.stream(d_packed);
         a.nseg = (long long)nseg;
         a.hop = s->hop;
         a.window = s->d_window;
         a.twiddles = s->d_tw;
         a.part_sum = s->d_part_sum;
         a.part_peak = s->d_part_peak;
-        SPEC_TRY(launch_spectrum(s->nfft, a, blocks, st));
+        PDDC_HIP_TRY(launch_spectrum(s->nfft, a, blocks, st));
     }
     SpectrumFoldArgs f{};
     f.part_sum = s->d_part_sum;
@@ -199,17 +165,10 @@ int pddc_spectrum_process(pddc_spectrum *s, const void *d_packed, size_t nsample
     f.nfft = s->nfft;
     f.acc_sum = s->d_acc_sum;
     f.acc_peak = s->d_acc_peak;
-    f.tail = s->d_tail[s->cur];
-    f.batch = static_cast<const uint8_t *>(d_packed);
-    f.new_tail = s->d_tail[s->cur ^ 1];
-    f.tail_len = (long long)s->tail_len;
-    f.keep_from = (long long)keep_from;
-    f.new_len = (long long)(len - keep_from);
-    SPEC_TRY(launch_spectrum_fold(f, st));
+    f.carry = s->in.carry(plan, d_packed);
+    PDDC_HIP_TRY(launch_spectrum_fold(f, st));
     /* both launches were accepted: only now do the host-side counters move */
-    s->cur ^= 1;
-    s->tail_len = len - keep_from;
-    s->samples += nsamples;
+    s->in.commit(plan, nsamples);
     s->segments += nseg;
     return PDDC_OK;
 }
@@ -220,10 +179,10 @@ int pddc_spectrum_read(pddc_spectrum *s, void *d_sum, void *d_peak, uint64_t *ns
         return pddc_set_error_(PDDC_EINVAL, "null argument");
     if (d_peak && !(s->flags & PDDC_SPEC_PEAK))
         return pddc_set_error_(PDDC_EINVAL, "spectrum: created without PDDC_SPEC_PEAK");
-    SPEC_TRY(hipSetDevice(s->device));
+    PDDC_HIP_TRY(hipSetDevice(s->device));
     if (d_sum || d_peak || clear)
-        SPEC_TRY(launch_spectrum_read(s->nfft, s->d_acc_sum, s->d_acc_peak, static_cast<float *>(d_sum),
-                                      static_cast<float *>(d_peak), clear, (hipStream_t)stream));
+        PDDC_HIP_TRY(launch_spectrum_read(s->nfft, s->d_acc_sum, s->d_acc_peak, static_cast<float *>(d_sum),
+                                          static_cast<float *>(d_peak), clear, (hipStream_t)stream));
     if (nsegments)
         *nsegments = s->segments;
     if (clear)

@@ -5,8 +5,7 @@
 #ifndef PDDC_DDC_SPECTRUM_H
 #define PDDC_DDC_SPECTRUM_H
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "ddc_packed.h"
 
 namespace pddc {
 
@@ -21,9 +20,7 @@ void spectrum_build_twiddles(int nfft, float *tw);
 int spectrum_max_blocks(int nfft, int ncu);
 
 struct SpectrumArgs {
-    const uint8_t *tail;      /* the packed samples carried from the batches before: tail_len of them   */
-    const uint8_t *batch;     /* this batch                                                             */
-    long long tail_len;       /* samples, a multiple of 8, < nfft                                       */
+    PackedStream in;          /* tail-then-batch (ddc_packed.h); the tail is shorter than nfft          */
     long long nseg;           /* segments this launch completes; segment j starts at sample j*hop of tail-then-batch */
     int hop;
     const float *window;      /* [nfft]                                                                 */
@@ -40,10 +37,7 @@ struct SpectrumFoldArgs {
     int nparts, nfft;
     double *acc_sum;                     /* [nfft] running sums                                          */
     float *acc_peak;                     /* [nfft] or nullptr                                            */
-    /* the carried tail for the NEXT batch: new_tail[0 .. new_len) = (tail-then-batch)[keep_from .. keep_from + new_len) */
-    const uint8_t *tail, *batch;
-    uint8_t *new_tail;
-    long long tail_len, keep_from, new_len;
+    PackedCarryArgs carry;               /* the carried tail for the NEXT batch (ddc_packed.h)           */
 };
 /* k_spectrum_fold: the second pass -- partial sums into the running sums (double, partials in ascending order), and the
  * tail carried on.  One launch.                                                                                */

@@ -6,7 +6,7 @@
  *                the workgroup (LDS + registers), |X|^2 added to per-thread per-bin sums.  No float copy of the input
  *                ever reaches HBM: 6 B read per sample, 4*N (8*N with the peak hold) written per BLOCK.
  *   k_spectrum_fold       second pass: the blocks' partial sums into the running sums (double, ascending block order),
- *                the peak partials into the running peak, and the packed tail carried to the next batch.
+ *                the peak partials into the running peak, and the packed tail carried to the next batch (ddc_packed.h).
  *   k_spectrum_read       running sums -> float32 (and the optional clear).
  *
  * Transform, twiddles and LDS images: ddc_fft_dev.h (shared with the channelizer).  The twiddle table lives in LDS beside
@@ -111,14 +111,8 @@ __global__ __launch_bounds__(N / 16 < 256 ? N / 16 : 256) void k_spectrum(Spectr
     auto load_seg = [&](long long seg) {
         const long long v0 = seg * p.hop;
 #pragma unroll
-        for (int u = 0; u < NG; ++u) {
-            const long long v = v0 + 8LL * (tid + u * NT);      /* tail_len is a multiple of 8: a group lies on one side */
-            const uint8_t *src = v < p.tail_len ? p.tail + v * 6 : p.batch + (v - p.tail_len) * 6;
-            const u32x4 *s = reinterpret_cast<const u32x4 *>(src);
-            raw[u][0] = __builtin_nontemporal_load(s);
-            raw[u][1] = __builtin_nontemporal_load(s + 1);
-            raw[u][2] = __builtin_nontemporal_load(s + 2);
-        }
+        for (int u = 0; u < NG; ++u)
+            p.in.load_group(v0 + 8LL * (tid + u * NT), raw[u]);
     };
 
     long long seg = blockIdx.x;
@@ -132,15 +126,11 @@ __global__ __launch_bounds__(N / 16 < 256 ? N / 16 : 256) void k_spectrum(Spectr
             f32x4 o[4];
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-                /* 12 bytes = 2 samples: I0 Q0 I1 Q1, MSB-aligned (value * 256) as k_unpack24 places them */
-                const uint32_t a = raw[u][(3 * h) >> 2][(3 * h) & 3], b = raw[u][(3 * h + 1) >> 2][(3 * h + 1) & 3],
-                               c = raw[u][(3 * h + 2) >> 2][(3 * h + 2) & 3];
-                int32_t i0, q0, i1, q1;
-                unpack2_msb(a, b, c, i0, q0, i1, q1);
-                o[h].x = ((float)i0 * kSpecUnpackScale) * win[u][2 * h];
-                o[h].y = ((float)q0 * kSpecUnpackScale) * win[u][2 * h];
-                o[h].z = ((float)i1 * kSpecUnpackScale) * win[u][2 * h + 1];
-                o[h].w = ((float)q1 * kSpecUnpackScale) * win[u][2 * h + 1];
+                PDDC_UNPACK_GROUP_MSB(raw[u], h, i0, q0, i1, q1);
+                o[h].x = ((float)i0 * kPackedUnpackScale) * win[u][2 * h];
+                o[h].y = ((float)q0 * kPackedUnpackScale) * win[u][2 * h];
+                o[h].z = ((float)i1 * kPackedUnpackScale) * win[u][2 * h + 1];
+                o[h].w = ((float)q1 * kPackedUnpackScale) * win[u][2 * h + 1];
             }
             f32x4 *dst = reinterpret_cast<f32x4 *>(buf);
 #pragma unroll
@@ -210,16 +200,7 @@ __global__ __launch_bounds__(256) void k_spectrum_fold(SpectrumFoldArgs p)
         }
         return;
     }
-    /* new_tail[c] = (tail-then-batch)[keep_from*6/16 + c], 16-byte chunks: every length is a multiple of 8 samples = 48 B */
-    const long long nchunks = p.new_len * 6 / 16;
-    const long long tail_chunks = p.tail_len * 6 / 16, from = p.keep_from * 6 / 16;
-    const long long stride = (long long)(gridDim.x - nbin_blocks) * 256;
-    for (long long c = (long long)(blockIdx.x - nbin_blocks) * 256 + threadIdx.x; c < nchunks; c += stride) {
-        const long long v = from + c;
-        const u32x4 *src = v < tail_chunks ? reinterpret_cast<const u32x4 *>(p.tail) + v
-                                           : reinterpret_cast<const u32x4 *>(p.batch) + (v - tail_chunks);
-        reinterpret_cast<u32x4 *>(p.new_tail)[c] = *src;
-    }
+    PDDC_CARRY_TAIL(p.carry, nbin_blocks)
 }
 
 __global__ __launch_bounds__(256) void k_spectrum_read(int nfft, double *acc_sum, float *acc_peak, float *d_sum,
@@ -244,20 +225,7 @@ template <int N, bool PEAK> static hipError_t launch_spectrum_t(const SpectrumAr
 {
     constexpr int NT = N / 16 < 256 ? N / 16 : 256;
     const size_t lds = sizeof(float) * ((size_t)2 * N + (size_t)spectrum_twiddle_len(N));
-    static bool raised[64] = {};      /* (two threads may both set the attribute: the same value, harmless) */
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess)
-        return e;
-    if (!raised[dev & 63]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spectrum<N, PEAK>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess)
-            return e;
-        raised[dev & 63] = true;
-    }
-    hipLaunchKernelGGL((k_spectrum<N, PEAK>), dim3((unsigned)blocks), dim3(NT), lds, s, a);
-    return hipGetLastError();
+    return launch_dynamic_lds<&k_spectrum<N, PEAK>>(lds, dim3((unsigned)blocks), dim3(NT), lds, s, a);
 }
 
 hipError_t launch_spectrum(int nfft, const SpectrumArgs &a, int blocks, hipStream_t s)
@@ -275,9 +243,8 @@ hipError_t launch_spectrum(int nfft, const SpectrumArgs &a, int blocks, hipStrea
 hipError_t launch_spectrum_fold(const SpectrumFoldArgs &a, hipStream_t s)
 {
     const int nbin_blocks = a.nfft / 32;
-    const long long nchunks = a.new_len * 6 / 16;
-    const int copy_blocks = (int)((nchunks + 255) / 256 < 32 ? (nchunks + 255) / 256 : 32);
-    hipLaunchKernelGGL(k_spectrum_fold, dim3((unsigned)(nbin_blocks + copy_blocks)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_spectrum_fold, dim3((unsigned)(nbin_blocks + carry_tail_blocks(a.carry.new_len))), dim3(256), 0, s,
+                       a);
     return hipGetLastError();
 }
 

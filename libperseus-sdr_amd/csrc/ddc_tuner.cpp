@@ -2,7 +2,7 @@
  * ddc_tuner.cpp -- host side of the tuner (include/perseus_ddc.h, pddc_tuner_*): the object, its receiver table, the
  * carried z values and counters, and the launches of a batch.  The kernels are in ddc_tuner.hip.
  */
-#include "../../include/perseus_ddc.h"
+#include "ddc_host.h"
 #include "ddc_tuner.h"
 
 #include <algorithm>
@@ -10,18 +10,6 @@
 #include <vector>
 
 using namespace pddc;
-
-extern "C" int pddc_set_error_(int code, const char *fmt, ...);
-
-#define TUNE_TRY(expr)                                                                                          \
-    do {                                                                                                        \
-        hipError_t e__ = (expr);                                                                                \
-        if (e__ != hipSuccess)                                                                                  \
-            return pddc_set_error_(e__ == hipErrorOutOfMemory ? PDDC_ENOMEM                                     \
-                                   : (e__ == hipErrorNoDevice || e__ == hipErrorInvalidDevice) ? PDDC_ENODEV    \
-                                                                                               : PDDC_EHIP,     \
-                                   "%s: %s", #expr, hipGetErrorString(e__));                                    \
-    } while (0)
 
 struct pddc_tuner {
     int device = 0;
@@ -50,21 +38,11 @@ static void tune_split(int b, uint32_t freg, int *channel, int32_t *residue)
         *residue = (int32_t)(freg - (k << (32 - b)));
 }
 
-static bool tune_range_ok(int nchan, int first, int count)
-{
-    return first >= 0 && first < nchan && count >= 1 && count <= nchan;
-}
-
 static bool tune_in_range(int nchan, int first, int count, uint32_t freg)
 {
     int k;
     tune_split(tune_log2(nchan), freg, &k, nullptr);
     return ((k - first) & (nchan - 1)) < count;
-}
-
-static uint64_t tune_complete(int ntaps, int decim, uint64_t rows)
-{
-    return rows >= (uint64_t)ntaps ? (rows - (uint64_t)ntaps) / (uint64_t)decim + 1 : 0;
 }
 
 static void tune_build_table(pddc_tuner *t)
@@ -91,16 +69,16 @@ static void tune_free(pddc_tuner *t)
 
 static int tune_alloc(pddc_tuner *t, const float *taps)
 {
-    TUNE_TRY(hipSetDevice(t->device));
+    PDDC_HIP_TRY(hipSetDevice(t->device));
     int ncu = 0;
-    TUNE_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device));
+    PDDC_HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, t->device));
     t->target_blocks = 4 * (ncu > 0 ? ncu : 256);
     const size_t carry = sizeof(float2) * (size_t)t->nrx * (size_t)t->carry_cap;
-    TUNE_TRY(hipMalloc(&t->d_table, sizeof(TuneRx) * (size_t)t->nrx));
-    TUNE_TRY(hipMalloc(&t->d_taps, sizeof(float) * (size_t)t->ntaps));
-    TUNE_TRY(hipMalloc(&t->d_carry[0], carry));
-    TUNE_TRY(hipMalloc(&t->d_carry[1], carry));
-    TUNE_TRY(hipMemcpy(t->d_taps, taps, sizeof(float) * (size_t)t->ntaps, hipMemcpyHostToDevice));
+    PDDC_HIP_TRY(hipMalloc(&t->d_table, sizeof(TuneRx) * (size_t)t->nrx));
+    PDDC_HIP_TRY(hipMalloc(&t->d_taps, sizeof(float) * (size_t)t->ntaps));
+    PDDC_HIP_TRY(hipMalloc(&t->d_carry[0], carry));
+    PDDC_HIP_TRY(hipMalloc(&t->d_carry[1], carry));
+    PDDC_HIP_TRY(hipMemcpy(t->d_taps, taps, sizeof(float) * (size_t)t->ntaps, hipMemcpyHostToDevice));
     return PDDC_OK;
 }
 
@@ -119,7 +97,7 @@ uint64_t pddc_tuner_outputs(int ntaps, int decim, uint64_t rows_before, size_t n
 {
     if (ntaps < 1 || ntaps > kTuneMaxTaps || decim < 1 || decim > kTuneMaxDecim)
         return 0;
-    return tune_complete(ntaps, decim, rows_before + nrows) - tune_complete(ntaps, decim, rows_before);
+    return windows_complete(ntaps, decim, rows_before + nrows) - windows_complete(ntaps, decim, rows_before);
 }
 
 uint64_t pddc_tuner_next_outputs(const pddc_tuner *t, size_t nrows)
@@ -135,7 +113,7 @@ int pddc_tuner_create(pddc_tuner **out, int device, int nchan, int hop, int firs
     *out = nullptr;
     if (!tune_log2(nchan) || (hop != nchan && hop != nchan / 2))
         return pddc_set_error_(PDDC_EINVAL, "tuner: nchan %d (1024, 2048 or 4096), hop %d (nchan or nchan/2)", nchan, hop);
-    if (!tune_range_ok(nchan, first, count))
+    if (!channel_range_ok(nchan, first, count))
         return pddc_set_error_(PDDC_EINVAL, "tuner: first %d (0 .. nchan-1), count %d (1 .. nchan)", first, count);
     if (nrx < 1 || nrx > kTuneMaxRx || !freg)
         return pddc_set_error_(PDDC_EINVAL, "tuner: %d receivers (1 .. %d) and their words", nrx, kTuneMaxRx);
@@ -147,13 +125,8 @@ int pddc_tuner_create(pddc_tuner **out, int device, int nchan, int hop, int firs
     for (int j = 0; j < nrx; ++j)
         if (!tune_in_range(nchan, first, count, freg[j]))
             return pddc_set_error_(PDDC_EINVAL, "tuner: receiver %d (word 0x%08x) lies outside the channel range", j, freg[j]);
-    const int ndev = pddc_device_count();
-    if (ndev < 0)
-        return ndev;
-    if (ndev == 0)
-        return pddc_set_error_(PDDC_ENODEV, "no HIP device visible (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev)
-        return pddc_set_error_(PDDC_ENODEV, "device %d out of range (%d visible)", device, ndev);
+    if (const int rc = pddc_check_device_(device))
+        return rc;
     pddc_tuner *t = new (std::nothrow) pddc_tuner;
     if (!t)
         return pddc_set_error_(PDDC_ENOMEM, "out of memory");
@@ -191,8 +164,8 @@ int pddc_tuner_reset(pddc_tuner *t)
 {
     if (!t)
         return pddc_set_error_(PDDC_EINVAL, "null argument");
-    TUNE_TRY(hipSetDevice(t->device));
-    TUNE_TRY(hipDeviceSynchronize());
+    PDDC_HIP_TRY(hipSetDevice(t->device));
+    PDDC_HIP_TRY(hipDeviceSynchronize());
     t->rows = 0;
     std::fill(t->phi.begin(), t->phi.end(), 0u);
     t->dirty = true;
@@ -219,7 +192,7 @@ int pddc_tuner_set_range(pddc_tuner *t, int first, int count)
 {
     if (!t)
         return pddc_set_error_(PDDC_EINVAL, "null argument");
-    if (!tune_range_ok(t->nchan, first, count))
+    if (!channel_range_ok(t->nchan, first, count))
         return pddc_set_error_(PDDC_EINVAL, "tuner: first %d (0 .. nchan-1), count %d (1 .. nchan)", first, count);
     for (int j = 0; j < t->nrx; ++j)
         if (!tune_in_range(t->nchan, first, count, t->freg[(size_t)j]))
@@ -239,8 +212,8 @@ int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_
     if (nrows && (!d_rows || ((uintptr_t)d_rows & 7)))
         return pddc_set_error_(PDDC_EINVAL, "d_rows must be an 8-byte aligned device pointer");
     const uint64_t R = (uint64_t)t->decim;
-    const uint64_t m0 = tune_complete(t->ntaps, t->decim, t->rows);
-    const uint64_t m1 = tune_complete(t->ntaps, t->decim, t->rows + nrows);
+    const uint64_t m0 = windows_complete(t->ntaps, t->decim, t->rows);
+    const uint64_t m1 = windows_complete(t->ntaps, t->decim, t->rows + nrows);
     const uint64_t nout = m1 - m0;
     if (nout && (!d_out || ((uintptr_t)d_out & 7)))
         return pddc_set_error_(PDDC_EINVAL, "d_out must be an 8-byte aligned device pointer");
@@ -251,11 +224,11 @@ int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_
         *n_out = 0;
     if (!nrows)
         return PDDC_OK;
-    TUNE_TRY(hipSetDevice(t->device));
+    PDDC_HIP_TRY(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream;
     if (t->dirty) {
         tune_build_table(t);
-        TUNE_TRY(hipMemcpyAsync(t->d_table, t->table.data(), sizeof(TuneRx) * (size_t)t->nrx, hipMemcpyHostToDevice, st));
+        PDDC_HIP_TRY(hipMemcpyAsync(t->d_table, t->table.data(), sizeof(TuneRx) * (size_t)t->nrx, hipMemcpyHostToDevice, st));
     }
     const uint64_t total = t->rows + nrows;
     TuneArgs a{};
@@ -285,7 +258,7 @@ int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_
         long long run = ((long long)nout + runs - 1) / runs;
         run = std::max(run, (4LL * (t->ntaps - 1) + t->decim - 1) / t->decim);
         a.run = (std::max(run, 1LL) + a.co - 1) / a.co * a.co;
-        TUNE_TRY(launch_tune(a, st));
+        PDDC_HIP_TRY(launch_tune(a, st));
     }
     const uint64_t keep_from = m1 * R;              /* the first row the next output needs */
     const bool carries = total > keep_from;
@@ -295,7 +268,7 @@ int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_
         c.new_carry = t->d_carry[t->cur ^ 1];
         c.keep_u = (long long)(nout * R);
         c.new_len = (int)(total - keep_from);
-        TUNE_TRY(launch_tune_carry(c, st));
+        PDDC_HIP_TRY(launch_tune_carry(c, st));
     }
     /* every launch was accepted: only now do the host-side counters move */
     if (carries)
