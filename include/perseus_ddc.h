@@ -468,6 +468,12 @@ uint64_t pddc_spectrum_segments(int nfft, int hop, uint64_t samples_before, size
  * output s + L/D of a stream with zero history.
  * Channel range: only channels (first + i) mod M, i < count, are written; a row is `count`
  * complex float32, interleaved (re, im), rows consecutive: out[s count + i].
+ * Channel list (set_channels): instead of a range, channels[0 .. n), 1 <= n <= 1024, each in
+ * [0, M), pairwise distinct, in any order; a row then is n values, out[s n + i] = y[s][channels[i]],
+ * and `count` is n wherever it means values per row (capacity, next_rows).  A value's bits are those
+ * the range mode gives for the same (M, D, P, w, samples, channel): they do not depend on the list,
+ * its order or the mode.  set_range returns to range mode; either takes effect from the next
+ * process(), the rows go on without a gap.
  * Stream semantics are the panorama's: the row grid belongs to the stream, the object carries the
  * last (fewer than L) packed samples across process() calls, a batch may be shorter than L, and
  * batches cut anywhere on a multiple of 8 samples give the same rows -- here the same BITS: a
@@ -490,6 +496,9 @@ int pddc_channelizer_process(pddc_channelizer *c, const void *d_packed, size_t n
                              size_t out_capacity_rows, size_t *n_rows, void *stream);
 /* another channel range, from the next process() on (the rows go on without a gap) */
 int pddc_channelizer_set_range(pddc_channelizer *c, int first, int count);
+/* list mode from the next process() on: rows of n values, out[s n + i] = y[s][channels[i]].  The list is copied.
+ * PDDC_EINVAL, nothing changed: NULL, n outside 1 .. 1024, an entry outside [0, nchan), a duplicate. */
+int pddc_channelizer_set_channels(pddc_channelizer *c, const int *channels, int n);
 /* rows the NEXT process() of nsamples writes */
 uint64_t pddc_channelizer_next_rows(const pddc_channelizer *c, size_t nsamples);
 /* the same without an object (host arithmetic, no device): rows completed by nsamples more samples of a stream that
@@ -517,6 +526,14 @@ uint64_t pddc_channelizer_rows(int nchan, int hop, int proto_len, uint64_t sampl
  * is continuous (the increment changes, never the phase): phi_j' = phi_j + (F_j - F') (s0 D) mod 2^32.
  * Rows before s0 keep the z they had, so the first T - 1 outputs after a retune mix old and new
  * tuning.  A word whose channel lies outside the channel range: PDDC_EINVAL, nothing changed.
+ * Channel list (set_channels, after pddc_channelizer_set_channels with the same list, between two
+ * batches): rows are [nrows][n] in the list's order, receiver j reads the column at which k_j stands
+ * in the list; several receivers may share a listed channel.  A list that misses a current
+ * receiver's channel, and in list mode a set_freq to a word whose channel is not listed:
+ * PDDC_EINVAL, nothing changed.  To retune to an unlisted channel, between two batches: set the
+ * union list on both objects, set_freq, then (optionally) the shrunk list on both.  The carried z is
+ * indexed by the caller's receiver index, so a list change leaves it as it is, like a range change.
+ * set_range returns to range mode.
  * Stream semantics are the channelizer's: the tuner counts rows itself and must be given every row
  * since create / reset, in order, as [nrows][count] complex float32 of the CURRENT range
  * (set_range follows pddc_channelizer_set_range, between two batches); it carries what the next
@@ -540,6 +557,8 @@ int pddc_tuner_destroy(pddc_tuner *t);
 int pddc_tuner_reset(pddc_tuner *t);                  /* row counter, carried rows, phase offsets; synchronises the device */
 int pddc_tuner_set_freq(pddc_tuner *t, int rx, uint32_t freg);
 int pddc_tuner_set_range(pddc_tuner *t, int first, int count);        /* every receiver must lie inside it */
+/* the channelizer's list (pddc_channelizer_set_channels), from the next process() on; every receiver's channel must be in it */
+int pddc_tuner_set_channels(pddc_tuner *t, const int *channels, int n);
 /* one batch of rows; *n_out (host, may be NULL) = outputs written per receiver */
 int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_out, size_t out_stride,
                        size_t *n_out, void *stream);
@@ -549,6 +568,9 @@ uint64_t pddc_tuner_next_outputs(const pddc_tuner *t, size_t nrows);
 uint64_t pddc_tuner_outputs(int ntaps, int decim, uint64_t rows_before, size_t nrows);
 /* channel and residue of a word (host arithmetic, no device); either pointer may be NULL */
 int pddc_tuner_channel(int nchan, uint32_t freg, int *channel, int32_t *residue);
+/* the distinct channels of nrx words (pddc_tuner_channel's rule), ascending, into channels[nrx]: the list for the two
+ * set_channels calls (host arithmetic, no device).  -> how many, or a negative PDDC_E* (NULL, nrx <= 0, unsupported nchan) */
+int pddc_tuner_channel_list(int nchan, const uint32_t *freg, int nrx, int *channels /* [nrx] */);
 
 /* pinned host memory for the two calls above */
 int pddc_host_alloc(void **h_ptr, size_t nbytes);

@@ -198,8 +198,9 @@ def ddc_lib() -> C.CDLL:
     L.pddc_channelizer_reset.argtypes = [vp]
     L.pddc_channelizer_process.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), vp]
     L.pddc_channelizer_set_range.argtypes = [vp, C.c_int, C.c_int]
+    L.pddc_channelizer_set_channels.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
     for f in (L.pddc_channelizer_create, L.pddc_channelizer_destroy, L.pddc_channelizer_reset,
-              L.pddc_channelizer_process, L.pddc_channelizer_set_range):
+              L.pddc_channelizer_process, L.pddc_channelizer_set_range, L.pddc_channelizer_set_channels):
         f.restype = C.c_int
     L.pddc_channelizer_next_rows.argtypes = [vp, sz]
     L.pddc_channelizer_next_rows.restype = C.c_uint64
@@ -213,8 +214,11 @@ def ddc_lib() -> C.CDLL:
     L.pddc_tuner_set_range.argtypes = [vp, C.c_int, C.c_int]
     L.pddc_tuner_process.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), vp]
     L.pddc_tuner_channel.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int32)]
+    L.pddc_tuner_set_channels.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
+    L.pddc_tuner_channel_list.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int)]
     for f in (L.pddc_tuner_create, L.pddc_tuner_destroy, L.pddc_tuner_reset, L.pddc_tuner_set_freq,
-              L.pddc_tuner_set_range, L.pddc_tuner_process, L.pddc_tuner_channel):
+              L.pddc_tuner_set_range, L.pddc_tuner_process, L.pddc_tuner_channel, L.pddc_tuner_set_channels,
+              L.pddc_tuner_channel_list):
         f.restype = C.c_int
     L.pddc_tuner_next_outputs.argtypes = [vp, sz]
     L.pddc_tuner_next_outputs.restype = C.c_uint64
@@ -712,6 +716,13 @@ def spectrum_dbfs(sum_, nsegments: int, window):
         return 10.0 * np.log10(p.astype(np.float64) / ref)
 
 
+def _channel_list(channels):
+    """a channel list as the C ABI takes it -> (numpy int32 array, its int pointer)"""
+    import numpy as np
+    ch = np.ascontiguousarray(np.asarray(channels, dtype=np.int64).reshape(-1), dtype=np.int32)
+    return ch, ch.ctypes.data_as(C.POINTER(C.c_int))
+
+
 def _packed_arg(kind, packed, nsamples):
     """a torch uint8 CUDA tensor of packed samples, or a device address with nsamples -> (address, nsamples)"""
     if hasattr(packed, "data_ptr"):
@@ -808,13 +819,17 @@ class Channelizer(_StreamObject):
     time series, from one read of the batch (include/perseus_ddc.h).  proto: the real prototype low-pass, float32 of 1, 2,
     4 or 8 times nchan taps, at most 16384 (channelizer_prototype gives a usable one); hop nchan (default) or nchan/2;
     first / count: the channels (first + i) mod nchan, i < count, that are written (default: all).  The row grid belongs
-    to the stream: batches may be cut anywhere on a multiple of 8 samples, and give the same bits."""
+    to the stream: batches may be cut anywhere on a multiple of 8 samples, and give the same bits.
+    set_channels(list) switches to list mode: only the listed channels (1 .. 1024 of them, distinct, any order) are
+    written, a row is len(list) values in the list's order, with the bits range mode gives; `channels` holds the list
+    (None in range mode) and `count` its length."""
     _kind = "channelizer"
 
     def __init__(self, nchan: int, proto, hop=None, first: int = 0, count=None, device: int = 0):
         import numpy as np
         self.nchan, self.hop, self.device = int(nchan), int(nchan if hop is None else hop), device
         self.first, self.count = int(first), int(self.nchan if count is None else count)
+        self.channels = None
         w = np.ascontiguousarray(np.asarray(proto, dtype=np.float32).reshape(-1))
         self.proto = w
         h = C.c_void_p()
@@ -849,9 +864,19 @@ class Channelizer(_StreamObject):
         return out.view(-1)[:n.value * self.count].view(n.value, self.count)
 
     def set_range(self, first: int, count: int):
-        """another channel range, from the next process() on"""
+        """another channel range (and range mode), from the next process() on"""
         check(ddc_lib().pddc_channelizer_set_range(self._h, first, count))
         self.first, self.count = int(first), int(count)
+        self.channels = None
+
+    def set_channels(self, channels):
+        """list mode from the next process() on: rows of len(channels) values, out[s, i] = y[s][channels[i]].  A Tuner
+        behind this object needs the same list (Tuner.set_channels) before its next batch.  To retune a receiver to a
+        channel that is not listed, between two batches: set the union list here and on the Tuner, Tuner.set_freq, then
+        (optionally) the shrunk list on both."""
+        ch, ptr = _channel_list(channels)
+        check(ddc_lib().pddc_channelizer_set_channels(self._h, ptr, ch.size))
+        self.channels, self.count = ch, int(ch.size)
 
 
 def channelizer_rows(nchan: int, hop: int, proto_len: int, samples_before: int, nsamples: int) -> int:
@@ -901,6 +926,17 @@ def tuner_outputs(ntaps: int, decim: int, rows_before: int, nrows: int) -> int:
     return int(ddc_lib().pddc_tuner_outputs(ntaps, decim, rows_before, nrows))
 
 
+def tuner_channel_list(nchan: int, freqs):
+    """pddc_tuner_channel_list: the distinct channels of the words, ascending -- the list for Channelizer.set_channels
+    and Tuner.set_channels; host arithmetic, no device.  -> numpy int32 array"""
+    import numpy as np
+    f = np.ascontiguousarray(np.asarray(freqs, dtype=np.uint64).reshape(-1) & 0xFFFFFFFF, dtype=np.uint32)
+    out = np.empty(max(f.size, 1), dtype=np.int32)
+    n = check(ddc_lib().pddc_tuner_channel_list(nchan, f.ctypes.data_as(C.POINTER(C.c_uint32)), f.size,
+                                                out.ctypes.data_as(C.POINTER(C.c_int))))
+    return out[:n].copy()
+
+
 def tuner_channel(nchan: int, freg: int):
     """pddc_tuner_channel: (channel, residue) of a 32-bit NCO word; host arithmetic, no device"""
     k, r = C.c_int(), C.c_int32()
@@ -912,15 +948,20 @@ class Tuner(_StreamObject):
     """pddc_tuner: len(freqs) narrowband receivers behind `channelizer` (its nchan, hop and channel range), each tuned
     with its own 32-bit NCO word (pddc_nco_freg's convention), all filtered by the real low-pass `taps` on rows and
     decimated by `decim`: output rate fs / (hop * decim) (include/perseus_ddc.h).  Feed it every batch of rows the
-    Channelizer returns, in order, on the same stream; after Channelizer.set_range call set_range here too.  Outputs
-    are bit-identical however the rows are cut into batches."""
+    Channelizer returns, in order, on the same stream; after Channelizer.set_range call set_range here too, after
+    Channelizer.set_channels call set_channels with the same list.  A channelizer in list mode hands its list over at
+    construction.  Outputs are bit-identical however the rows are cut into batches, and in either mode.
+    Retune to a channel that is not listed, between two batches: set the union list on the Channelizer and here,
+    set_freq, then (optionally) the shrunk list on both."""
     _kind = "tuner"
 
     def __init__(self, channelizer, freqs, taps, decim: int):
         import numpy as np
         ch = channelizer
         self.nchan, self.hop, self.device = ch.nchan, ch.hop, ch.device
-        self.first, self.count = ch.first, ch.count
+        listed = getattr(ch, "channels", None)
+        self.first, self.count = (0, ch.nchan) if listed is not None else (ch.first, ch.count)
+        self.channels = None
         f = np.ascontiguousarray(np.asarray(freqs, dtype=np.uint64).reshape(-1) & 0xFFFFFFFF, dtype=np.uint32)
         h = np.ascontiguousarray(np.asarray(taps, dtype=np.float32).reshape(-1))
         self.nrx, self.taps, self.decim = int(f.size), h, int(decim)
@@ -929,6 +970,8 @@ class Tuner(_StreamObject):
                                           f.ctypes.data_as(C.POINTER(C.c_uint32)), f.size,
                                           h.ctypes.data_as(C.POINTER(C.c_float)), h.size, self.decim, 0))
         self._h = hd
+        if listed is not None:                       # created over the full range, then given the list
+            self.set_channels(listed)
 
     def next_outputs(self, nrows: int) -> int:
         """outputs per receiver the next process() of nrows rows writes (known from sizes alone)"""
@@ -967,6 +1010,15 @@ class Tuner(_StreamObject):
         """the Channelizer's new range (Channelizer.set_range), from the next process() on"""
         check(ddc_lib().pddc_tuner_set_range(self._h, first, count))
         self.first, self.count = int(first), int(count)
+        self.channels = None
+
+    def set_channels(self, channels):
+        """the Channelizer's list (Channelizer.set_channels), from the next process() on: rows of len(channels) values in
+        this order.  Every receiver's channel must be listed; in list mode set_freq to an unlisted channel is refused
+        (the retune sequence: the class docstring)."""
+        ch, ptr = _channel_list(channels)
+        check(ddc_lib().pddc_tuner_set_channels(self._h, ptr, ch.size))
+        self.channels, self.first, self.count = ch, 0, int(ch.size)
 
 
 class PinnedBuffer:

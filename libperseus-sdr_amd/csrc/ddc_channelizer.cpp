@@ -2,6 +2,9 @@
  * ddc_channelizer.cpp -- host side of the channelizer (include/perseus_ddc.h, pddc_channelizer_*): the object, its
  * counters, and the two launches of a batch.  The carried tail is a PackedCarry (ddc_packed.h); the kernels are in
  * ddc_channelizer.hip.
+ * List mode: the list lives on the host; the kernel reads slot[bin] (the column of bin k, -1: not listed).  A new list's
+ * table is uploaded by the next process() that has rows, on its stream -- ordered behind the launch before it, which
+ * therefore never sees it (one stream per object) -- as the tuner uploads its receiver table.
  */
 #include "ddc_channelizer.h"
 #include "ddc_kernels.h"
@@ -15,8 +18,12 @@ using namespace pddc;
 struct pddc_channelizer {
     int device = 0;
     int nchan = 0, hop = 0, proto_len = 0;
-    int first = 0, count = 0;
-    int target_blocks = 0;
+    int first = 0, count = 0;                       /* list mode: count = channels.size()                         */
+    std::vector<int> channels;                      /* list mode: the list; empty: range mode                     */
+    std::vector<short> h_slot;                      /* the slot table; rebuilt and uploaded when `slot_dirty`     */
+    short *d_slot = nullptr;
+    bool slot_dirty = false;
+    int target_blocks = 0, target_blocks_list = 0;
     float *d_proto = nullptr, *d_tw = nullptr;
     PackedCarry in;                                 /* the carried tail (a window of proto_len) and the stream length */
     uint64_t rows = 0;                              /* rows delivered since create / reset     */
@@ -38,6 +45,7 @@ static void chan_free(pddc_channelizer *c)
 {
     hipFree(c->d_proto);
     hipFree(c->d_tw);
+    hipFree(c->d_slot);
     c->in.free();
     delete c;
 }
@@ -48,11 +56,13 @@ static int chan_create(pddc_channelizer *c, const float *proto)
     int ncu = 0;
     PDDC_HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device));
     c->target_blocks = channelize_target_blocks(c->nchan, c->proto_len / c->nchan, c->hop, ncu > 0 ? ncu : 256);
+    c->target_blocks_list = channelize_target_blocks(c->nchan, c->proto_len / c->nchan, c->hop, ncu > 0 ? ncu : 256, true);
     std::vector<float> tw((size_t)spectrum_twiddle_len(c->nchan));
     spectrum_build_twiddles(c->nchan, tw.data());
     PDDC_HIP_TRY(hipMalloc(&c->d_proto, (size_t)c->proto_len * sizeof(float)));
     PDDC_HIP_TRY(hipMalloc(&c->d_tw, tw.size() * sizeof(float)));
     PDDC_HIP_TRY(c->in.alloc((size_t)c->proto_len));
+    PDDC_HIP_TRY(hipMalloc(&c->d_slot, (size_t)c->nchan * sizeof(short)));
     PDDC_HIP_TRY(hipMemcpy(c->d_proto, proto, (size_t)c->proto_len * sizeof(float), hipMemcpyHostToDevice));
     PDDC_HIP_TRY(hipMemcpy(c->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
     return PDDC_OK;
@@ -138,6 +148,20 @@ int pddc_channelizer_set_range(pddc_channelizer *c, int first, int count)
         return pddc_set_error_(PDDC_EINVAL, "channelizer: first %d (0 .. nchan-1), count %d (1 .. nchan)", first, count);
     c->first = first;
     c->count = count;
+    c->channels.clear();        /* range mode; the device table is of no use to a later list: set_channels marks it stale */
+    return PDDC_OK;
+}
+
+int pddc_channelizer_set_channels(pddc_channelizer *c, const int *channels, int n)
+{
+    if (!c)
+        return pddc_set_error_(PDDC_EINVAL, "null argument");
+    if (!channel_list_ok(c->nchan, channels, n))
+        return pddc_set_error_(PDDC_EINVAL, "channelizer: a list of %d channels (1 .. %d, each 0 .. nchan-1, no duplicates)",
+                               n, kChannelListMax);
+    c->channels.assign(channels, channels + n);
+    c->count = n;
+    c->slot_dirty = true;
     return PDDC_OK;
 }
 
@@ -161,13 +185,21 @@ int pddc_channelizer_process(pddc_channelizer *c, const void *d_packed, size_t n
         return PDDC_OK;
     PDDC_HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
+    const bool list = !c->channels.empty();
     if (nrows) {
         const int taps = c->proto_len / c->nchan, units = taps * (c->nchan / c->hop);
+        const int target = list ? c->target_blocks_list : c->target_blocks;
+        if (list && c->slot_dirty) {
+            c->h_slot.assign((size_t)c->nchan, (short)-1);
+            for (size_t i = 0; i < c->channels.size(); ++i)
+                c->h_slot[(size_t)c->channels[i]] = (short)i;
+            PDDC_HIP_TRY(hipMemcpyAsync(c->d_slot, c->h_slot.data(), c->h_slot.size() * sizeof(short), hipMemcpyHostToDevice, st));
+        }
         /* rows per block: the stream spread over the blocks that fit side by side, but never runs so short that the
          * porch (units - 1 re-read units per run) outweighs them -- at least 4 rows per re-read unit (porch <= 25 %) */
         long long run = tunables().chan_run.load();
         if (run <= 0) {
-            run = (long long)((nrows + (uint64_t)c->target_blocks - 1) / (uint64_t)c->target_blocks);
+            run = (long long)((nrows + (uint64_t)target - 1) / (uint64_t)target);
             const long long floor_rows = 4LL * (units - 1);
             run = run < floor_rows ? floor_rows : run;
         }
@@ -181,11 +213,14 @@ int pddc_channelizer_process(pddc_channelizer *c, const void *d_packed, size_t n
         a.proto = c->d_proto;
         a.twiddles = c->d_tw;
         a.out = static_cast<float *>(d_out);
+        a.slot = list ? c->d_slot : nullptr;
         PDDC_HIP_TRY(launch_channelize(c->nchan, taps, c->hop, a, st));
     }
     PDDC_HIP_TRY(launch_channelize_tail(c->in.carry(plan, d_packed), st));
     /* both launches were accepted: only now do the host-side counters move */
     c->in.commit(plan, nsamples);
+    if (nrows && list)
+        c->slot_dirty = false;
     c->rows += nrows;
     if (n_rows)
         *n_rows = (size_t)nrows;

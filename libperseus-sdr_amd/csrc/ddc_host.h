@@ -40,6 +40,21 @@ inline bool channel_range_ok(int nchan, int first, int count)
     return first >= 0 && first < nchan && count >= 1 && count <= nchan;
 }
 
+/* a channel list: channels[0 .. n), 1 <= n <= kChannelListMax, each in [0, nchan), pairwise distinct, any order */
+static constexpr int kChannelListMax = 1024;
+inline bool channel_list_ok(int nchan, const int *channels, int n)
+{
+    if (!channels || n < 1 || n > kChannelListMax || nchan < 1 || nchan > 4096)
+        return false;
+    bool seen[4096] = {};
+    for (int i = 0; i < n; ++i) {
+        if (channels[i] < 0 || channels[i] >= nchan || seen[channels[i]])
+            return false;
+        seen[channels[i]] = true;
+    }
+    return true;
+}
+
 /* hipFuncAttributeMaxDynamicSharedMemorySize of Kernel, once per device (the attribute is per device): every kernel
  * instantiation has flags of its own, so a kernel asks for ONE size wherever it is launched from.  (Two threads may
  * both set the attribute: the same value, harmless.) */

@@ -1,6 +1,9 @@
 /*
  * ddc_tuner.cpp -- host side of the tuner (include/perseus_ddc.h, pddc_tuner_*): the object, its receiver table, the
  * carried z values and counters, and the launches of a batch.  The kernels are in ddc_tuner.hip.
+ * List mode (pddc_tuner_set_channels) is host logic only: a receiver's column is the index of its channel in the list and
+ * `count` the list's length; k_tune takes any count and any column.  The table is rebuilt and uploaded by the next
+ * process(), as after any other change.
  */
 #include "ddc_host.h"
 #include "ddc_tuner.h"
@@ -15,6 +18,7 @@ struct pddc_tuner {
     int device = 0;
     int nchan = 0, hop = 0, first = 0, count = 0;
     int nrx = 0, ntaps = 0, decim = 0;
+    std::vector<short> slot;                        /* list mode: [nchan], column of channel k, -1: not listed; empty: range mode */
     int carry_cap = 1;                              /* max(ntaps - 1, 1) z values per receiver                    */
     int target_blocks = 0;
     std::vector<uint32_t> freg, phi;
@@ -26,6 +30,8 @@ struct pddc_tuner {
     int cur = 0;
     uint64_t rows = 0;                              /* rows taken since create / reset                            */
 };
+
+static_assert(kChannelListMax == kTuneMaxRx, "a channel list holds as many channels as a tuner has receivers");
 
 static int tune_log2(int nchan) { return nchan == 1024 ? 10 : nchan == 2048 ? 11 : nchan == 4096 ? 12 : 0; }
 
@@ -45,6 +51,22 @@ static bool tune_in_range(int nchan, int first, int count, uint32_t freg)
     return ((k - first) & (nchan - 1)) < count;
 }
 
+/* the column table of a list */
+static std::vector<short> tune_slots(int nchan, const int *channels, int n)
+{
+    std::vector<short> slot((size_t)nchan, (short)-1);
+    for (int i = 0; i < n; ++i)
+        slot[(size_t)channels[i]] = (short)i;
+    return slot;
+}
+
+static bool tune_listed(int nchan, const std::vector<short> &slot, uint32_t freg)
+{
+    int k;
+    tune_split(tune_log2(nchan), freg, &k, nullptr);
+    return slot[(size_t)k] >= 0;
+}
+
 static void tune_build_table(pddc_tuner *t)
 {
     const int b = tune_log2(t->nchan);
@@ -53,7 +75,8 @@ static void tune_build_table(pddc_tuner *t)
         int k;
         int32_t r;
         tune_split(b, t->freg[(size_t)j], &k, &r);
-        t->table[(size_t)j] = TuneRx{ (k - t->first) & (t->nchan - 1), r, t->phi[(size_t)j], j };
+        const int col = t->slot.empty() ? (k - t->first) & (t->nchan - 1) : (int)t->slot[(size_t)k];
+        t->table[(size_t)j] = TuneRx{ col, r, t->phi[(size_t)j], j };
     }
     std::stable_sort(t->table.begin(), t->table.end(), [](const TuneRx &x, const TuneRx &y) { return x.col < y.col; });
 }
@@ -178,7 +201,9 @@ int pddc_tuner_set_freq(pddc_tuner *t, int rx, uint32_t freg)
         return pddc_set_error_(PDDC_EINVAL, "null argument");
     if (rx < 0 || rx >= t->nrx)
         return pddc_set_error_(PDDC_EINVAL, "tuner: receiver %d (0 .. %d)", rx, t->nrx - 1);
-    if (!tune_in_range(t->nchan, t->first, t->count, freg))
+    if (!t->slot.empty() && !tune_listed(t->nchan, t->slot, freg))
+        return pddc_set_error_(PDDC_EINVAL, "tuner: the channel of word 0x%08x is not in the channel list", freg);
+    if (t->slot.empty() && !tune_in_range(t->nchan, t->first, t->count, freg))
         return pddc_set_error_(PDDC_EINVAL, "tuner: word 0x%08x lies outside the channel range", freg);
     /* the accumulator is continuous: the increment changes at the next row, s0 = rows so far, the phase does not */
     const uint32_t sd = (uint32_t)(t->rows * (uint64_t)t->hop);
@@ -200,8 +225,48 @@ int pddc_tuner_set_range(pddc_tuner *t, int first, int count)
                                    t->freg[(size_t)j]);
     t->first = first;
     t->count = count;
+    t->slot.clear();
     t->dirty = true;
     return PDDC_OK;
+}
+
+int pddc_tuner_set_channels(pddc_tuner *t, const int *channels, int n)
+{
+    if (!t)
+        return pddc_set_error_(PDDC_EINVAL, "null argument");
+    if (!channel_list_ok(t->nchan, channels, n))
+        return pddc_set_error_(PDDC_EINVAL, "tuner: a list of %d channels (1 .. %d, each 0 .. nchan-1, no duplicates)", n,
+                               kChannelListMax);
+    std::vector<short> slot = tune_slots(t->nchan, channels, n);
+    for (int j = 0; j < t->nrx; ++j)
+        if (!tune_listed(t->nchan, slot, t->freg[(size_t)j]))
+            return pddc_set_error_(PDDC_EINVAL, "tuner: the channel of receiver %d (word 0x%08x) is not in that list", j,
+                                   t->freg[(size_t)j]);
+    t->slot.swap(slot);
+    t->first = 0;
+    t->count = n;
+    t->dirty = true;
+    return PDDC_OK;
+}
+
+int pddc_tuner_channel_list(int nchan, const uint32_t *freg, int nrx, int *channels)
+{
+    const int b = tune_log2(nchan);
+    if (!b)
+        return pddc_set_error_(PDDC_EINVAL, "tuner: nchan %d (1024, 2048 or 4096)", nchan);
+    if (!freg || !channels || nrx < 1)
+        return pddc_set_error_(PDDC_EINVAL, "tuner: %d words and room for as many channels", nrx);
+    std::vector<bool> seen((size_t)nchan, false);
+    for (int j = 0; j < nrx; ++j) {
+        int k;
+        tune_split(b, freg[j], &k, nullptr);
+        seen[(size_t)k] = true;
+    }
+    int n = 0;
+    for (int k = 0; k < nchan; ++k)
+        if (seen[(size_t)k])
+            channels[n++] = k;
+    return n;
 }
 
 int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_out, size_t out_stride, size_t *n_out,
