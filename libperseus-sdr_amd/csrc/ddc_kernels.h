@@ -35,6 +35,22 @@ Tunables &tunables();
 bool set_tunable(const char *name, int value);       /* false: no such knob */
 bool get_tunable(const char *name, int *value);
 
+/* The NCO state of a batch, as every vector kernel that mixes takes it: phase(n) = n * freg + phase_off (mod 2^32) for
+ * the absolute sample index n, which keeps the phase continuous across retunes (the FPGA's accumulator never jumps).
+ * The samples in FRONT of the batch (a stage's packed history) were mixed with freg_hist -- == freg unless this is the
+ * first batch after a retune -- and the phase is continuous at n0.  The matrix kernels fold the NCO into their taps and
+ * keep three fields of their own (FirI8xArgs).                                                                      */
+struct NcoArgs {
+    unsigned long long n0 = 0;        /* absolute index of batch sample 0                                          */
+    uint32_t freg = 0;                /* tuning word                                                               */
+    uint32_t phase_off = 0;
+    uint32_t freg_hist = 0;           /* the word the history was mixed with                                       */
+    float    lo_c[8], lo_s[8];        /* cos / -sin of step e * freg, e = 0..7 (nco_fill_steps: host, double)      */
+    float    lo_c_hist[8], lo_s_hist[8];   /* the same for freg_hist                                               */
+};
+/* host: the four step-phasor arrays from the record's two words */
+void nco_fill_steps(NcoArgs *a);
+
 /* A THIRD stage fused behind the decimate-by-8 pair (launch_fir8_fused3): a plain decimate-by-d FIR on the second
  * stage's outputs, which then never reach HBM either -- the whole cascade is ONE streaming pass (x320 = 8*8*5:
  * 6 B read + 8/320 B written per input sample).  The stage runs at 1/64 of the input rate, so it is written for
@@ -74,7 +90,7 @@ struct GenTail {
     const float *hist = nullptr;      /* the H samples in front of it                                              */
     float       *hist_out = nullptr;  /* receives the last H samples of [hist | in]                                */
     float       *out = nullptr;       /* float2 outputs                                                            */
-    const float *taps = nullptr;      /* duplicated table (h[k], h[k]), see launch_fir_generic                     */
+    const float *taps = nullptr;      /* duplicated table (h[k], h[k]), see DecimArgs                              */
     long long    first = 0, n_out = 0, n_batch = 0;
     int          H = 0, D = 0, ntaps = 0;
     int          span = 0, a = 31;    /* block shape (gen_tail_shape)                                              */
@@ -110,17 +126,13 @@ struct Fir8Args {
     Fir8Stage3   s3;                   /* launch_fir8_fused3 only                          */
     GenTail      tail;                 /* launch_fir8_fused2 only: the previous batch's tail, carried along */
     long long   n_in;        /* samples in the batch, multiple of 8            */
-    unsigned long long n0;   /* absolute index of batch sample 0 (NCO phase)   */
-    uint32_t    freg;        /* NCO tuning word                                */
-    uint32_t    phase_off = 0;   /* phase(n) = n*freg + phase_off (mod 2^32): keeps the phase continuous
-                                across retunes (the FPGA's accumulator never jumps)          */
-    uint32_t    freg_hist = 0;   /* tuning word the samples in `hist` were mixed with (== freg unless
-                                this is the first batch after a retune)                       */
-    float       lo_c[8];     /* cos/sin of step e*freg, e=0..7 (host, double)  */
-    float       lo_s[8];
-    float       lo_c_hist[8];   /* the same for freg_hist                        */
-    float       lo_s_hist[8];
+    NcoArgs     nco;         /* hist is mixed with nco.freg_hist                */
 };
+/* k_fir8 reads the record where it lies among the kernel arguments: these are the offsets it has always had */
+static_assert(sizeof(Fir8Args) == 448 && offsetof(Fir8Args, n_in) == 288 && offsetof(Fir8Args, nco) == 296 &&
+                  offsetof(Fir8Args, nco.freg) == 304 && offsetof(Fir8Args, nco.lo_c) == 316 &&
+                  offsetof(Fir8Args, nco.lo_s_hist) == 412,
+              "Fir8Args: n_in, then the NCO record (8 + 12 + 128 bytes, padded to 8)");
 
 /* ---- several streams, one launch chain ("gang"): the drop-in API's virtual receivers that share a GPU --------------
  * Up to kFir8ManyMax streams with the SAME plan and batch length go through one launch of each kernel: blockIdx.y is
@@ -286,47 +298,39 @@ hipError_t launch_fir8_fused3(int ntb, int R, bool mix, const Fir8Args &a, hipSt
 /* returns hipSuccess or the launch error */
 hipError_t launch_fir8(int ntb, int R, InFmt fmt, bool mix, const Fir8Args &a, hipStream_t s, int NT = 256);
 
-hipError_t launch_unpack24(const void *d_in, long long nsamples, void *d_out, bool to_i32,
-                           bool mix, unsigned long long n0, uint32_t freg, uint32_t phase_off,
-                           const float *lo_c, const float *lo_s, hipStream_t s);
+/* packed -> float2 (or -> int32 pairs, to_i32), mixed with the record's word, offset and n0 where `mix` is given */
+hipError_t launch_unpack24(const void *d_in, long long nsamples, void *d_out, bool to_i32, const NcoArgs *mix,
+                           hipStream_t s);
 
-/* generic decimating FIR on float2: out[q] = sum_k h[k]*x[first + q*D - k],
- * x indexed relative to `in`; x[-H..-1] come from `hist` (H >= ntaps-1).
- * `taps` is the DUPLICATED table: entry k = the pair (h[k], h[k]) (a naturally aligned SGPR pair for the packed
- * FMA); it must be readable, as zeros, over entries [-3*D - 8, ntaps + 3*D + 8).  hist_out (or
- * NULL) receives the last H samples of [hist | in(n_batch)]; must not alias hist. */
-hipError_t launch_fir_generic(const float *in, const float *hist, int H, long long first, long long n_out,
-                              int D, const float *taps, int ntaps, float *out, float *hist_out,
-                              long long n_batch, hipStream_t s);
+/* One launch of a plain decimator: out[q] = sum_k h[k] * x[first + q*D - k], q < n_out, x indexed relative to `in`;
+ * x[-H .. -1] come from `hist` (H >= ntaps - 1).  hist_out (or NULL) receives the last H samples of
+ * [hist | in(n_batch)]; it must not alias hist.
+ * fmt = IN_PACKED24 (stage 0 of a plan whose first decimation is not the fused 8): batch, hist and hist_out are 24-bit
+ * packed, H % 8 == 0 and n_batch % 8 == 0; the block unpacks and -- `mix` given -- mixes while it stages its span, the
+ * history with mix->freg_hist.  `mix` goes with packed input only.
+ * Two kernels serve it, and a stage may go back and forth between them from batch to batch (the history is the same):
+ * k_firp, the register-blocked one, where `taps_firp` is given and firp_supported(D, ntaps); k_fir_generic otherwise.
+ *   taps       the DUPLICATED table: entry k = the pair (h[k], h[k]) (a naturally aligned SGPR pair for the packed FMA),
+ *              readable, as zeros, over entries [-3*D - 8, ntaps + 3*D + 8)
+ *   taps_firp  (h[k], h[k]) pairs zero padded to firp_taps_len(D, ntaps) taps, nothing in front; for packed input
+ *              scaled by kFir8PackedTapScale (k_firp leaves the unpack scale to the taps, like k_fir8)            */
+struct DecimArgs {
+    const void  *in = nullptr, *hist = nullptr;
+    void        *hist_out = nullptr;
+    float       *out = nullptr;       /* float2 outputs                                                            */
+    const float *taps = nullptr, *taps_firp = nullptr;
+    long long    first = 0, n_out = 0, n_batch = 0;
+    int          H = 0, D = 0, ntaps = 0;
+    InFmt        fmt = IN_F32C;
+    const NcoArgs *mix = nullptr;
+};
+hipError_t launch_decim(const DecimArgs &d, hipStream_t s);          /* n_out <= 0: nothing to do, hipSuccess */
 
-/* The same decimator fed with 24-bit PACKED samples (stage 0 of a plan whose first decimation is not
- * 8): the block unpacks and -- `mix` -- mixes while it stages its input span; batch, hist (H samples,
- * H % 8 == 0) and hist_out are packed, n_batch % 8 == 0.  phase(n) = n*freg + phase_off for the batch,
- * and the history is mixed with freg_hist (phase-continuous at n0).                              */
-hipError_t launch_fir_generic_packed(const void *in_packed, const void *hist_packed, int H, long long first,
-                                     long long n_out, int D, const float *taps, int ntaps, float *out,
-                                     void *hist_out_packed, long long n_batch, bool mix, unsigned long long n0,
-                                     uint32_t freg, uint32_t phase_off, uint32_t freg_hist, const float *lo_c,
-                                     const float *lo_s, const float *lo_c_hist, const float *lo_s_hist, hipStream_t s);
-
-/* k_firp: the register-blocked decimator for the decimations the rate plans use besides 8 (4, 5, 10), float2 or packed
- * (+ NCO) input: same contract as launch_fir_generic / launch_fir_generic_packed except for the tap table -- (h[k], h[k])
- * pairs zero padded to firp_taps_len(D, ntaps) taps, nothing in front -- and that `mx` may be NULL for float2 input.
- * The history a stage keeps (H >= ntaps - 1, any length) is the same, so a stage can go back and forth between the
- * two kernels from batch to batch.                                                                               */
-struct GenMixArgs;
+/* k_firp is built for the decimations the rate plans use besides the fused 8 (4, 5, 8, 10) */
 bool firp_supported(int D, int ntaps);
 int  firp_taps_len(int D, int ntaps);
 int  firp_nbq(int D, int ntaps);
 size_t firp_lds_bytes(int D, int ntaps);
-hipError_t launch_firp(int infmt, bool mix, const void *in, const void *hist, int H, long long first, long long n_out,
-                       int D, const float *taps2, int ntaps, float *out, void *hist_out, long long n_batch,
-                       const GenMixArgs *mx, hipStream_t s);
-hipError_t launch_firp_packed(const void *in_packed, const void *hist_packed, int H, long long first, long long n_out,
-                              int D, const float *taps2, int ntaps, float *out, void *hist_out_packed, long long n_batch,
-                              bool mix, unsigned long long n0, uint32_t freg, uint32_t phase_off, uint32_t freg_hist,
-                              const float *lo_c, const float *lo_s, const float *lo_c_hist, const float *lo_s_hist,
-                              hipStream_t s);
 
 /* false when even the smallest block shape of the generic kernel cannot stage its input span
  * ((63*D + ntaps + 10) samples) in the 160 KiB of LDS: such a stage is refused at create time */

@@ -59,6 +59,7 @@
 #include "ddc_dev.h"
 #include "ddc_host.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -229,6 +230,22 @@ __device__ __forceinline__ void mix8(float (&xi)[8], float (&xq)[8], unsigned lo
     mix8_lo(xi, xq, cb, sb, p);
 }
 
+static void lo_steps(uint32_t freg, float *c, float *s)
+{
+    const double k = 6.283185307179586476925286766559 / 4294967296.0;
+    for (int e = 0; e < 8; ++e) {
+        const uint32_t ph = (uint32_t)((uint64_t)e * freg);
+        c[e] = (float)std::cos(k * (double)ph);
+        s[e] = (float)(-std::sin(k * (double)ph));
+    }
+}
+
+void nco_fill_steps(NcoArgs *a)
+{
+    lo_steps(a->freg, a->lo_c, a->lo_s);
+    lo_steps(a->freg_hist, a->lo_c_hist, a->lo_s_hist);
+}
+
 /* ======================================================================== */
 /* k_unpack24                                                               */
 /* ======================================================================== */
@@ -340,22 +357,20 @@ __global__ __launch_bounds__(256) void k_unpack24(UnpackArgs p)
     }
 }
 
-hipError_t launch_unpack24(const void *d_in, long long ns, void *d_out, bool to_i32, bool mix,
-                           unsigned long long n0, uint32_t freg, uint32_t phase_off, const float *lo_c,
-                           const float *lo_s, hipStream_t s)
+hipError_t launch_unpack24(const void *d_in, long long ns, void *d_out, bool to_i32, const NcoArgs *mix, hipStream_t s)
 {
     if (ns <= 0)
         return hipSuccess;
-    UnpackArgs a;
+    UnpackArgs a = {};
     a.in = static_cast<const uint8_t *>(d_in);
     a.out = d_out;
     a.ns = ns;
-    a.n0 = n0;
-    a.freg = freg;
-    a.phase_off = phase_off;
-    for (int e = 0; e < 8; ++e) {
-        a.lo_c[e] = lo_c ? lo_c[e] : 1.0f;
-        a.lo_s[e] = lo_s ? lo_s[e] : 0.0f;
+    if (mix) {
+        a.n0 = mix->n0;
+        a.freg = mix->freg;
+        a.phase_off = mix->phase_off;
+        std::copy(mix->lo_c, mix->lo_c + 8, a.lo_c);
+        std::copy(mix->lo_s, mix->lo_s + 8, a.lo_s);
     }
     const long long ngroups = (ns + 7) >> 3;
     long long blocks = (ngroups + 255) / 256;
@@ -375,18 +390,19 @@ hipError_t launch_unpack24(const void *d_in, long long ns, void *d_out, bool to_
 /* ======================================================================== */
 /* k_fir_generic, the kernel body (its description and launchers: further down) */
 /* ======================================================================== */
-struct GenMixArgs {
-    unsigned long long n0;      /* absolute index of batch sample 0                            */
-    uint32_t freg, phase_off;   /* phase(n) = n*freg + phase_off                               */
-    uint32_t freg_hist;         /* word the history samples were mixed with (first batch after a retune) */
-    float lo_c[8], lo_s[8];     /* step phasors of freg                                        */
-    float lo_c_hist[8], lo_s_hist[8];
+/* the NCO record plus what k_firp's packed staging wants.  (A base, not a member: lo512_c then starts in the record's
+ * tail padding, at the offset the kernels have always read it from.) */
+struct GenMixArgs : NcoArgs {
     /* k_firp's packed staging: a thread's pairs of samples lie 512 apart; LO(512 u freg), u = 0..15, from the host in
      * double.  (A recurrence phasor *= LO(512) carried the rounding of that ONE step phasor u times: 7.8e-7 of full
      * scale in the worst of 1200 random cases, against the 1e-6 bar; from this table it is one product from an exact
      * phase whatever u is.) */
     float lo512_c[16], lo512_s[16];
 };
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(GenMixArgs) == 280 && offsetof(GenMixArgs, lo512_c) == 148, "GenMixArgs: lo512_c behind lo_s_hist");
+#pragma clang diagnostic pop
 
 /* the body of one block: `bid` its index, `sd` its LDS, NT its threads -- also run by the extra blocks k_fir8 carries
  * along for the PREVIOUS batch's tail (Fir8Args::tail)                                                          */
@@ -1000,7 +1016,7 @@ __device__ __forceinline__ void group_to_float(const u32x4 (&raw)[NW], float (&x
         }
     }
     if (MIX)     /* zero-filled groups stay zero; the index wraps correctly for negative offsets */
-        mix8(xi, xq, nabs, p);
+        mix8(xi, xq, nabs, p.nco);
 }
 
 /* same, with the local oscillator value of the group's first sample supplied */
@@ -1009,7 +1025,7 @@ __device__ __forceinline__ void group_to_float_lo(const u32x4 (&raw)[NW], float 
                                                   float sb, const Fir8Args &p)
 {
     group_to_float<INFMT, false, NW>(raw, xi, xq, 0ull, p);
-    mix8_lo(xi, xq, cb, sb, p);
+    mix8_lo(xi, xq, cb, sb, p.nco);
 }
 
 /* rotated LDS write of group v: e=0 -> slot 7 of group v-1 ; e=1..7 -> slots 0..6 of group v */
@@ -1610,57 +1626,15 @@ static GenShape pick_generic_shape(long long n_out, int D, int ntaps, int ncu)
     return g;
 }
 
-/* can launch_fir_generic stage a block of this decimator in LDS at all? */
+/* can k_fir_generic stage a block of this decimator in LDS at all? */
 bool fir_generic_supported(int D, int ntaps)
 {
     return D >= 1 && ntaps >= 1 && pick_generic_shape(1 << 20, D, ntaps, 256).NT != 0;
 }
 
-/* `taps` is the DUPLICATED table -- entry k is the pair (h[k], h[k]), 8 bytes -- and must be readable
- * (zeros) over entries [-3*D - 8, ntaps + 3*D + 8): the pipeline uploads its tap tables that way.  hist_out (or NULL) receives the last H samples of
- * [hist(H) | in(n_batch)]; it must not alias hist.                                  */
-static hipError_t launch_fir_generic_any(const void *in, const void *hist, int H, long long first, long long n_out,
-                                         int D, const float *taps, int ntaps, float *out, void *hist_out,
-                                         long long n_batch, int packed_mode /* 0 float2, 1 packed, 2 packed + mix */,
-                                         const GenMixArgs &mx, hipStream_t s);
-
-hipError_t launch_fir_generic(const float *in, const float *hist, int H, long long first, long long n_out,
-                              int D, const float *taps, int ntaps, float *out, float *hist_out,
-                              long long n_batch, hipStream_t s)
+/* launch_decim on k_fir_generic (n_out > 0, arguments checked) */
+static hipError_t launch_fir_generic(const DecimArgs &d, const GenMixArgs &mx, hipStream_t s)
 {
-    GenMixArgs mx = {};
-    return launch_fir_generic_any(in, hist, H, first, n_out, D, taps, ntaps, out, hist_out, n_batch, 0, mx, s);
-}
-
-hipError_t launch_fir_generic_packed(const void *in_packed, const void *hist_packed, int H, long long first,
-                                     long long n_out, int D, const float *taps, int ntaps, float *out,
-                                     void *hist_out_packed, long long n_batch, bool mix, unsigned long long n0,
-                                     uint32_t freg, uint32_t phase_off, uint32_t freg_hist, const float *lo_c,
-                                     const float *lo_s, const float *lo_c_hist, const float *lo_s_hist, hipStream_t s)
-{
-    if ((H & 7) || (n_batch & 7))
-        return hipErrorInvalidValue;
-    GenMixArgs mx = {};
-    mx.n0 = n0;
-    mx.freg = freg;
-    mx.phase_off = phase_off;
-    mx.freg_hist = freg_hist;
-    for (int e = 0; e < 8; ++e) {
-        mx.lo_c[e] = lo_c ? lo_c[e] : 1.0f;
-        mx.lo_s[e] = lo_s ? lo_s[e] : 0.0f;
-        mx.lo_c_hist[e] = lo_c_hist ? lo_c_hist[e] : 1.0f;
-        mx.lo_s_hist[e] = lo_s_hist ? lo_s_hist[e] : 0.0f;
-    }
-    return launch_fir_generic_any(in_packed, hist_packed, H, first, n_out, D, taps, ntaps, out, hist_out_packed, n_batch,
-                                  mix ? 2 : 1, mx, s);
-}
-
-static hipError_t launch_fir_generic_any(const void *in, const void *hist, int H, long long first, long long n_out,
-                                         int D, const float *taps, int ntaps, float *out, void *hist_out,
-                                         long long n_batch, int packed_mode, const GenMixArgs &mx, hipStream_t s)
-{
-    if (n_out <= 0)
-        return hipSuccess;
     int dev = 0;
     (void)hipGetDevice(&dev);
     static int ncu_of[64] = { 0 };
@@ -1670,49 +1644,22 @@ static hipError_t launch_fir_generic_any(const void *in, const void *hist, int H
             n = 256;
         ncu_of[dev & 63] = n;
     }
-    const int ncu = ncu_of[dev & 63];
-    const GenShape g = pick_generic_shape(n_out, D, ntaps, ncu);
-    const int NT = g.NT, P = g.P, span = g.span, a = g.a;
-    const size_t lds = g.lds;
-    if (NT == 0)
+    const GenShape g = pick_generic_shape(d.n_out, d.D, d.ntaps, ncu_of[dev & 63]);
+    if (g.NT == 0)
         return hipErrorInvalidValue;           /* span does not fit LDS even one output per thread */
-    const dim3 grid((unsigned)((n_out + (long long)NT * P - 1) / ((long long)NT * P))), blk((unsigned)NT);
-#define PDDC_GEN3(PP, PK, MX)                                                                      \
-    do {                                                                                          \
-        static int attr_lds[64] = { 0 };            /* per device */                             \
-        if ((int)lds > attr_lds[dev & 63]) {                                                      \
-            /* the whole LDS once (launch_gen_tail sets the same attribute of the same function) */   \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fir_generic<PP, PK, MX>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            if (e != hipSuccess)                                                                  \
-                return e;                                                                         \
-            attr_lds[dev & 63] = 160 * 1024;                                                      \
-        }                                                                                         \
-        hipLaunchKernelGGL((k_fir_generic<PP, PK, MX>), grid, blk, lds, s, reinterpret_cast<const float2 *>(in), \
-                           reinterpret_cast<const float2 *>(hist), H, first, n_out, D,            \
-                           (const float PDDC_CONSTANT *)taps, ntaps, reinterpret_cast<float2 *>(out), span, a, \
-                           reinterpret_cast<float2 *>(hist_out), n_batch, mx);                    \
-    } while (0)
-#define PDDC_GEN(PP)                                                                               \
-    do {                                                                                          \
-        if (packed_mode == 2)                                                                     \
-            PDDC_GEN3(PP, true, true);                                                            \
-        else if (packed_mode == 1)                                                                \
-            PDDC_GEN3(PP, true, false);                                                           \
-        else                                                                                      \
-            PDDC_GEN3(PP, false, false);                                                          \
-    } while (0)
-    if (P == 4)
-        PDDC_GEN(4);
-    else if (P == 3)
-        PDDC_GEN(3);
-    else if (P == 2)
-        PDDC_GEN(2);
-    else
-        PDDC_GEN(1);
+    const long long per_block = (long long)g.NT * g.P;
+    const dim3 grid((unsigned)((d.n_out + per_block - 1) / per_block)), blk((unsigned)g.NT);
+    /* the whole LDS (launch_gen_tail launches k_fir_generic<1, false, false> too: one cap per kernel) */
+#define PDDC_GEN3(PP, PK, MX)                                                                                           \
+    launch_dynamic_lds<&k_fir_generic<PP, PK, MX>>(                                                                     \
+        160 * 1024, grid, blk, g.lds, s, reinterpret_cast<const float2 *>(d.in), reinterpret_cast<const float2 *>(d.hist), \
+        d.H, d.first, d.n_out, d.D, (const float PDDC_CONSTANT *)d.taps, d.ntaps, reinterpret_cast<float2 *>(d.out),   \
+        g.span, g.a, reinterpret_cast<float2 *>(d.hist_out), d.n_batch, mx)
+#define PDDC_GEN(PP)                                                                                                    \
+    (d.fmt != IN_PACKED24 ? PDDC_GEN3(PP, false, false) : d.mix ? PDDC_GEN3(PP, true, true) : PDDC_GEN3(PP, true, false))
+    return g.P == 4 ? PDDC_GEN(4) : g.P == 3 ? PDDC_GEN(3) : g.P == 2 ? PDDC_GEN(2) : PDDC_GEN(1);
 #undef PDDC_GEN
 #undef PDDC_GEN3
-    return hipGetLastError();
 }
 
 template <int D, int P, int INFMT, bool MIX>
@@ -1771,28 +1718,29 @@ static hipError_t launch_firp_t(int infmt, bool mix, const FirpArgs &a, int ntap
     return launch_dynamic_lds<&k_firp<D, P, IN_F32C, false>>(lds_cap, grid, blk, lds, s, a);
 }
 
-/* same contract as launch_fir_generic / launch_fir_generic_packed; `taps2` = (h, h) pairs zero padded to
- * firp_taps_len(D, ntaps) taps                                                                                 */
-hipError_t launch_firp(int infmt, bool mix, const void *in, const void *hist, int H, long long first, long long n_out,
-                       int D, const float *taps2, int ntaps, float *out, void *hist_out, long long n_batch,
-                       const GenMixArgs *mx, hipStream_t s)
+/* launch_decim on k_firp (n_out > 0, arguments checked, firp_supported(D, ntaps)) */
+static hipError_t launch_firp(const DecimArgs &d, const GenMixArgs &mx, hipStream_t s)
 {
-    if (n_out <= 0)
-        return hipSuccess;
-    if (!firp_supported(D, ntaps) || (infmt == IN_PACKED24 && ((H & 7) || (n_batch & 7))))
-        return hipErrorInvalidValue;
+    const int infmt = d.fmt, D = d.D, ntaps = d.ntaps;
+    const bool mix = d.mix != nullptr;
     FirpArgs a;
-    a.in = in;
-    a.hist = hist;
-    a.hist_out = hist_out;
-    a.out = out;
-    a.taps2 = taps2;
-    a.first = first;
-    a.n_out = n_out;
-    a.n_batch = n_batch;
-    a.H = H;
+    a.in = d.in;
+    a.hist = d.hist;
+    a.hist_out = d.hist_out;
+    a.out = d.out;
+    a.taps2 = d.taps_firp;
+    a.first = d.first;
+    a.n_out = d.n_out;
+    a.n_batch = d.n_batch;
+    a.H = d.H;
     a.nbq = firp_nbq(D, ntaps);
-    a.mx = mx ? *mx : GenMixArgs{};
+    a.mx = mx;
+    for (int u = 0; mix && u < 16; ++u) {               /* exp(-j 2 pi (512 u freg mod 2^32) / 2^32), in double */
+        const uint32_t ph = (uint32_t)(512ull * (unsigned long long)u * mx.freg);
+        const double th = 6.283185307179586476925 * (double)ph / 4294967296.0;
+        a.mx.lo512_c[u] = (float)std::cos(th);
+        a.mx.lo512_s[u] = (float)(-std::sin(th));
+    }
     /* development: PDDC_FIRP_PACKED_P=1 gives the packed /10 first stage tiles of 256 outputs (one per lane) */
     const int pp = tunables().firp_packed_p.load();
     if (D == 10 && infmt == IN_PACKED24 && pp == 1) {
@@ -1806,31 +1754,17 @@ hipError_t launch_firp(int infmt, bool mix, const void *in, const void *hist, in
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_firp_packed(const void *in_packed, const void *hist_packed, int H, long long first, long long n_out,
-                              int D, const float *taps2, int ntaps, float *out, void *hist_out_packed, long long n_batch,
-                              bool mix, unsigned long long n0, uint32_t freg, uint32_t phase_off, uint32_t freg_hist,
-                              const float *lo_c, const float *lo_s, const float *lo_c_hist, const float *lo_s_hist,
-                              hipStream_t s)
+hipError_t launch_decim(const DecimArgs &d, hipStream_t s)
 {
+    if (d.n_out <= 0)
+        return hipSuccess;
+    const bool packed = d.fmt == IN_PACKED24;
+    if ((packed && ((d.H & 7) || (d.n_batch & 7))) || (d.mix && !packed))
+        return hipErrorInvalidValue;
     GenMixArgs mx = {};
-    mx.n0 = n0;
-    mx.freg = freg;
-    mx.phase_off = phase_off;
-    mx.freg_hist = freg_hist;
-    for (int e = 0; e < 8; ++e) {
-        mx.lo_c[e] = lo_c ? lo_c[e] : 1.0f;
-        mx.lo_s[e] = lo_s ? lo_s[e] : 0.0f;
-        mx.lo_c_hist[e] = lo_c_hist ? lo_c_hist[e] : 1.0f;
-        mx.lo_s_hist[e] = lo_s_hist ? lo_s_hist[e] : 0.0f;
-    }
-    for (int u = 0; u < 16; ++u) {                      /* exp(-j 2 pi (512 u freg mod 2^32) / 2^32), in double */
-        const uint32_t ph = (uint32_t)(512ull * (unsigned long long)u * freg);
-        const double th = 6.283185307179586476925 * (double)ph / 4294967296.0;
-        mx.lo512_c[u] = (float)std::cos(th);
-        mx.lo512_s[u] = (float)(-std::sin(th));
-    }
-    return launch_firp(IN_PACKED24, mix, in_packed, hist_packed, H, first, n_out, D, taps2, ntaps, out, hist_out_packed,
-                       n_batch, &mx, s);
+    if (d.mix)
+        static_cast<NcoArgs &>(mx) = *d.mix;
+    return d.taps_firp && firp_supported(d.D, d.ntaps) ? launch_firp(d, mx, s) : launch_fir_generic(d, mx, s);
 }
 
 bool gen_tail_shape(GenTail *t, size_t lds_cap, bool have_taps2)
@@ -1862,10 +1796,15 @@ hipError_t launch_gen_tail(const GenTail &t, hipStream_t s)
 {
     if (t.nblocks <= 0)
         return hipSuccess;
-    if (t.kind == 1)
-        return launch_firp(IN_F32C, false, t.in, t.hist, t.H, t.first, t.n_out, t.D, t.taps2, t.ntaps, t.out, t.hist_out,
-                           t.n_batch, nullptr, s);
-    /* the whole LDS, as launch_fir_generic_any asks for the same function */
+    if (t.kind == 1) {
+        DecimArgs d;
+        d.in = t.in, d.hist = t.hist, d.hist_out = t.hist_out, d.out = t.out;
+        d.taps = t.taps, d.taps_firp = t.taps2;
+        d.first = t.first, d.n_out = t.n_out, d.n_batch = t.n_batch;
+        d.H = t.H, d.D = t.D, d.ntaps = t.ntaps;
+        return launch_decim(d, s);
+    }
+    /* the record's own shape (the body k_fir8 carries); the whole LDS, as launch_decim asks for the same function */
     const GenMixArgs mx = {};
     return launch_dynamic_lds<&k_fir_generic<1, false, false>>(
         160 * 1024, dim3((unsigned)t.nblocks), dim3(256), t.lds, s, reinterpret_cast<const float2 *>(t.in),

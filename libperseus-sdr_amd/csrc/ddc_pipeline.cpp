@@ -90,18 +90,18 @@ struct pddc_pipeline {
     uint32_t flags = 0;
     int nstages = 0;
     Stage st[PDDC_MAX_STAGES];
-    uint32_t freg = 0;
-    /* phase(n) = n*freg + phase_off (mod 2^32).  A retune at sample n changes freg and moves
+    /* The NCO state, as the kernels take it.  n0: the absolute sample counter (stage 0 input); freg: the word in force.
+     * phase(n) = n*freg + phase_off (mod 2^32).  A retune at sample n changes freg and moves
      * phase_off by n*(freg_old - freg_new), so the phase is continuous there -- the FPGA's NCO
      * is a phase accumulator, a new tuning word changes its increment, never its value.
-     * freg_applied: the word the last processed batch was mixed with (the fused kernel re-mixes
-     * its raw packed history and needs it for the first batch after a retune).               */
-    uint32_t phase_off = 0;
-    uint32_t freg_applied = 0;
+     * freg_hist: the word the last processed batch was mixed with, the "applied" one (the fused kernel re-mixes
+     * its raw packed history and needs it for the first batch after a retune).  The step phasors follow the two
+     * words (nco_fill_steps).                                                                 */
+    NcoArgs nco;
     bool fresh = true;            /* nothing processed since create / reset / seek */
     /* Tuning-word segments that still reach into stage 0's history window [n0 - H, n0): {first
      * sample, word, offset}; the last one is the word in force.  Stage 0 keeps its history as raw
-     * packed samples and mixes them when it reads them, with ONE word (freg_applied): that is exact
+     * packed samples and mixes them when it reads them, with ONE word (nco.freg_hist): that is exact
      * as long as the whole window was mixed with one word.  Batches shorter than the history with
      * retunes between them break that; such a batch takes the float route (process(): "mixed
      * history"), where each stretch of the history is mixed with its own word.                  */
@@ -116,9 +116,6 @@ struct pddc_pipeline {
     bool time_stage0 = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
-    float lo_c[8], lo_s[8];
-    float lo_c_applied[8], lo_s_applied[8];   /* step phasors of freg_applied */
-    unsigned long long n0 = 0;    /* absolute sample counter (stage 0 input)    */
     int R = 4;                    /* outputs per lane of the fused kernel (4: 16 waves/CU) */
     int NT = 256;                 /* threads per block of the unfused stage-0 kernel (128: four blocks per CU) */
     /* staging for push_host / push_host_async: two slots, so that the H2D copy of batch k+1,
@@ -240,22 +237,6 @@ static float round_to_half(float v)
     /* round-to-nearest-even to IEEE binary16, returned widened to float */
     _Float16 h = (_Float16)v;
     return (float)h;
-}
-
-static void lo_steps(uint32_t freg, float *c, float *s)
-{
-    const double k = 6.283185307179586476925286766559 / 4294967296.0;
-    for (int e = 0; e < 8; ++e) {
-        const uint32_t ph = (uint32_t)((uint64_t)e * freg);
-        c[e] = (float)std::cos(k * (double)ph);
-        s[e] = (float)(-std::sin(k * (double)ph));
-    }
-}
-
-static void compute_lo_steps(pddc_pipeline *p)
-{
-    lo_steps(p->freg, p->lo_c, p->lo_s);
-    lo_steps(p->freg_applied, p->lo_c_applied, p->lo_s_applied);
 }
 
 static bool stage_fused_capable(const Stage &s)
@@ -707,8 +688,7 @@ int pddc_unpack24_f32(const void *d_packed, size_t nsamples, void *d_out, void *
         return rc;
     if ((rc = check_unpack_args(d_packed, d_out, nsamples)))
         return rc;
-    PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, d_out, false, false, 0, 0, 0, nullptr, nullptr,
-                                 (hipStream_t)stream));
+    PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, d_out, false, nullptr, (hipStream_t)stream));
     return PDDC_OK;
 }
 
@@ -719,8 +699,7 @@ int pddc_unpack24_i32(const void *d_packed, size_t nsamples, void *d_out, void *
         return rc;
     if ((rc = check_unpack_args(d_packed, d_out, nsamples)))
         return rc;
-    PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, d_out, true, false, 0, 0, 0, nullptr, nullptr,
-                                 (hipStream_t)stream));
+    PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, d_out, true, nullptr, (hipStream_t)stream));
     return PDDC_OK;
 }
 
@@ -840,7 +819,7 @@ int pddc_pipeline_create(pddc_pipeline **out, int device, const pddc_stage_desc 
     if (const char *e = getenv("PDDC_FIR8_NT"))
         if (fir8_nt_supported(p->st[0].ntb, p->R, atoi(e)))
             p->NT = atoi(e);
-    compute_lo_steps(p);
+    nco_fill_steps(&p->nco);
     hipError_t e = hipSuccess;
     for (int i = 0; i < nstages && e == hipSuccess; ++i) {
         Stage &s = p->st[i];
@@ -967,15 +946,15 @@ int pddc_pipeline_reset(pddc_pipeline *p)
         return fail(PDDC_EINVAL, "null pipeline");
     PDDC_HIP_TRY(hipSetDevice(p->device));
     PDDC_HIP_TRY(hipDeviceSynchronize());
-    p->n0 = 0;
-    p->phase_off = 0;
-    p->freg_applied = p->freg;
-    compute_lo_steps(p);
+    p->nco.n0 = 0;
+    p->nco.phase_off = 0;
+    p->nco.freg_hist = p->nco.freg;
+    nco_fill_steps(&p->nco);
     p->fresh = true;
     ++p->hist_ver;
     p->carry_pending = false;                         /* a reset stream has no tail to finish */
     p->ov_parity = 0;
-    p->segs.assign(1, pddc_pipeline::WordSeg{ 0, p->freg, 0u });      /* samples before the start are zeros */
+    p->segs.assign(1, pddc_pipeline::WordSeg{ 0, p->nco.freg, 0u });      /* samples before the start are zeros */
     PDDC_HIP_TRY(hipMemset(p->d_sched, 0, 64));
     if (p->d_flags)
         PDDC_HIP_TRY(hipMemset(p->d_flags, 0, sizeof(unsigned) * (size_t)fir8_fused3_max_chunks()));
@@ -993,26 +972,26 @@ int pddc_pipeline_set_freg(pddc_pipeline *p, uint32_t freg)
 {
     if (!p)
         return fail(PDDC_EINVAL, "null pipeline");
-    if (freg != p->freg) {
+    if (freg != p->nco.freg) {
         if (p->fresh) {
             /* before the first batch: the stream starts with this word, offset 0 */
-            p->freg_applied = freg;
+            p->nco.freg_hist = freg;
             p->segs.assign(1, pddc_pipeline::WordSeg{ 0, freg, 0u });
         } else {
             /* takes effect at sample n0 (the next one to be processed), phase-continuous there */
-            p->phase_off += (uint32_t)p->n0 * (p->freg - freg);
-            if (!p->segs.empty() && p->segs.back().n_begin == (long long)p->n0)
-                p->segs.back() = pddc_pipeline::WordSeg{ (long long)p->n0, freg, p->phase_off };
+            p->nco.phase_off += (uint32_t)p->nco.n0 * (p->nco.freg - freg);
+            if (!p->segs.empty() && p->segs.back().n_begin == (long long)p->nco.n0)
+                p->segs.back() = pddc_pipeline::WordSeg{ (long long)p->nco.n0, freg, p->nco.phase_off };
             else
-                p->segs.push_back(pddc_pipeline::WordSeg{ (long long)p->n0, freg, p->phase_off });
+                p->segs.push_back(pddc_pipeline::WordSeg{ (long long)p->nco.n0, freg, p->nco.phase_off });
         }
-        p->freg = freg;
-        compute_lo_steps(p);
+        p->nco.freg = freg;
+        nco_fill_steps(&p->nco);
     }
     return PDDC_OK;
 }
 
-uint32_t pddc_pipeline_get_phase_offset(const pddc_pipeline *p) { return p ? p->phase_off : 0; }
+uint32_t pddc_pipeline_get_phase_offset(const pddc_pipeline *p) { return p ? p->nco.phase_off : 0; }
 
 /* kernel selection by API state (not by environment): name -> field */
 static int *option_field(pddc_pipeline *p, const char *name)
@@ -1082,7 +1061,7 @@ int pddc_pipeline_set_center_freq(pddc_pipeline *p, double hz)
     return pddc_pipeline_set_freg(p, pddc_nco_freg(hz, PDDC_ADC_CLK_HZ));
 }
 
-uint32_t pddc_pipeline_get_freg(const pddc_pipeline *p) { return p ? p->freg : 0; }
+uint32_t pddc_pipeline_get_freg(const pddc_pipeline *p) { return p ? p->nco.freg : 0; }
 
 int pddc_pipeline_seek(pddc_pipeline *p, uint64_t abs_sample)
 {
@@ -1104,7 +1083,7 @@ int pddc_pipeline_seek(pddc_pipeline *p, uint64_t abs_sample)
     int rc = pddc_pipeline_reset(p);
     if (rc)
         return rc;
-    p->n0 = abs_sample;
+    p->nco.n0 = abs_sample;
     for (int i = 0; i < p->nstages; ++i)
         p->st[i].consumed = at[i];
     return PDDC_OK;
@@ -1237,7 +1216,7 @@ int pddc_pipeline_uses_fused(const pddc_pipeline *p) { return p && stage0_fused(
 /* how many tuning words do stage 0's history window [n0 - H, n0) and the batch behind it see?  1: one word, one offset */
 static size_t words_in_window(const pddc_pipeline *p)
 {
-    const long long w0 = (long long)p->n0 - (long long)p->st[0].hist;
+    const long long w0 = (long long)p->nco.n0 - (long long)p->st[0].hist;
     size_t first = 0;
     while (first + 1 < p->segs.size() && p->segs[first + 1].n_begin <= w0)
         ++first;
@@ -1421,7 +1400,7 @@ static int i8x_prepare(pddc_pipeline *p, bool mix, bool fuse2, hipStream_t s, Fi
 {
     pddc_pipeline::I8x &x = p->i8x;
     const Stage &s0 = p->st[0];
-    const uint32_t word = mix ? p->freg : 0u;
+    const uint32_t word = mix ? p->nco.freg : 0u;
     if (!(x.cur >= 0 && x.freg == word && x.mix == mix && x.fuse2 == fuse2 && x.taps_ver == p->taps_ver && x.stream == s)) {
         if (x.cur >= 0) {
             if (x.stream == s) {
@@ -1477,9 +1456,9 @@ static int i8x_prepare(pddc_pipeline *p, bool mix, bool fuse2, hipStream_t s, Fi
     q.scale = x.scale;
     q.ct[0] = x.ct[0];
     q.ct[1] = x.ct[1];
-    q.n0 = p->n0;
+    q.n0 = p->nco.n0;
     q.freg = word;
-    q.phase_off = mix ? p->phase_off : 0u;
+    q.phase_off = mix ? p->nco.phase_off : 0u;
     return PDDC_OK;
 }
 
@@ -1487,7 +1466,7 @@ static int i8x_d10_prepare(pddc_pipeline *p, int delay, hipStream_t s, FirI8xArg
 {
     pddc_pipeline::I8x::D10 &e = p->i8x.d10[delay & 7];
     const Stage &s0 = p->st[0];
-    if (!(e.valid && e.freg == p->freg && e.taps_ver == p->taps_ver && e.stream == s)) {
+    if (!(e.valid && e.freg == p->nco.freg && e.taps_ver == p->taps_ver && e.stream == s)) {
         const size_t nb = fir_i8x_d10_table_bytes();
         if (e.valid) {
             /* a retune or new taps: the set in use stays where it is for the launches already queued -- an event behind them --
@@ -1514,10 +1493,10 @@ static int i8x_d10_prepare(pddc_pipeline *p, int delay, hipStream_t s, FirI8xArg
             b.left_valid = false;
         }
         e.valid = false;
-        if (!fir_i8x_d10_build_tables(s0.taps.data(), s0.ntaps, delay, p->freg, static_cast<int8_t *>(b.h), &e.scale, e.ct))
+        if (!fir_i8x_d10_build_tables(s0.taps.data(), s0.ntaps, delay, p->nco.freg, static_cast<int8_t *>(b.h), &e.scale, e.ct))
             return fail(PDDC_EINVAL, "k_fir_i8x: the taps cannot be quantised (all zero, or not finite)");
         PDDC_HIP_TRY(hipMemcpyAsync(b.d, b.h, nb, hipMemcpyHostToDevice, s));
-        e.freg = p->freg;
+        e.freg = p->nco.freg;
         e.taps_ver = p->taps_ver;
         e.stream = s;
         e.valid = true;
@@ -1527,9 +1506,9 @@ static int i8x_d10_prepare(pddc_pipeline *p, int delay, hipStream_t s, FirI8xArg
     q.scale = e.scale;
     q.ct[0] = e.ct[0];
     q.ct[1] = e.ct[1];
-    q.n0 = p->n0;
-    q.freg = p->freg;
-    q.phase_off = p->phase_off;
+    q.n0 = p->nco.n0;
+    q.freg = p->nco.freg;
+    q.phase_off = p->nco.phase_off;
     return PDDC_OK;
 }
 
@@ -1774,17 +1753,8 @@ static int stage0_event(pddc_pipeline *p, hipStream_t s, bool start)
 
 static void fill_fir8_args(const pddc_pipeline *p, Fir8Args &a)
 {
-    a.n0 = p->n0;
-    a.freg = p->freg;
-    a.phase_off = p->phase_off;
-    a.freg_hist = p->freg_applied;
+    a.nco = p->nco;
     a.sched = p->d_sched;
-    for (int e = 0; e < 8; ++e) {
-        a.lo_c[e] = p->lo_c[e];
-        a.lo_s[e] = p->lo_s[e];
-        a.lo_c_hist[e] = p->lo_c_applied[e];
-        a.lo_s_hist[e] = p->lo_s_applied[e];
-    }
 }
 
 static void fill_stage3_args(const pddc_pipeline *p, Fir8Args &a, float *dst, size_t off, size_t n_out, bool advance)
@@ -1909,15 +1879,15 @@ static bool mixed_history(pddc_pipeline *p)
 {
     if (!(p->flags & PDDC_F_MIX) || !(stage0_fused(p) || stage0_packed_generic(p)))
         return false;
-    const long long w0 = (long long)p->n0 - (long long)p->st[0].hist;
+    const long long w0 = (long long)p->nco.n0 - (long long)p->st[0].hist;
     while (p->segs.size() >= 2 && p->segs[1].n_begin <= w0)
         p->segs.erase(p->segs.begin());
     const size_t k = p->segs.size();
-    const bool ok = k == 1 || (k == 2 && p->segs[1].n_begin == (long long)p->n0);
+    const bool ok = k == 1 || (k == 2 && p->segs[1].n_begin == (long long)p->nco.n0);
     const uint32_t hist_word = p->segs[0].freg;
-    if (ok && hist_word != p->freg_applied) {      /* cannot happen while set_freg keeps both in step */
-        p->freg_applied = hist_word;
-        compute_lo_steps(p);
+    if (ok && hist_word != p->nco.freg_hist) {      /* cannot happen while set_freg keeps both in step */
+        p->nco.freg_hist = hist_word;
+        nco_fill_steps(&p->nco);
     }
     return !ok;
 }
@@ -1978,7 +1948,7 @@ static int build_first(pddc_pipeline *p, Route route, const BatchPlan &b, const 
         q.out = dst;
         q.n_in = (long long)nsamples;
         if (route == Route::I8xD10)
-            q.n0 = p->n0 + (unsigned long long)q.in_off;
+            q.n0 = p->nco.n0 + (unsigned long long)q.in_off;
         if (pair) {
             q.hist2 = s1.d_hist[s1.cur];
             q.hist2_out = hist2_out;
@@ -2095,6 +2065,13 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
     void *h_in = st.d_hist[st.cur], *h_out = st.d_hist[st.cur ^ 1];
     const void *x = d_packed;                       /* this stage's input batch */
     bool hist_done = false;
+    /* the stage as a plain decimator: launched below unless another kernel takes the stage */
+    DecimArgs d;
+    d.hist = h_in, d.hist_out = h_out, d.out = dst;
+    d.taps = st.d_taps_dup, d.taps_firp = st.d_taps_firp;         /* k_firp (by 4, 5, 8, 10) where its table exists */
+    d.first = (long long)off[i], d.n_out = (long long)n_in[i + 1], d.n_batch = (long long)n_in[i];
+    d.H = st.hist, d.D = st.decim, d.ntaps = st.ntaps;
+    bool plain = st.interp == 1;
     if (i == 0 && route == Route::MixedHist) {
         /* rare: batches shorter than the history with retunes between them.  The packed history
          * is unpacked and mixed stretch by stretch, each with the word and offset that applied to
@@ -2105,48 +2082,35 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
             return rc;
         if (!p->d_hist_f32)
             PDDC_HIP_TRY(hipMalloc(&p->d_hist_f32, (size_t)PDDC_MAX_TAPS * 8 + 256));
-        const long long w0 = (long long)p->n0 - H;
+        const long long w0 = (long long)p->nco.n0 - H;
         for (size_t k = 0; k < p->segs.size(); ++k) {
             const long long a0 = std::max(w0, k == 0 ? w0 : p->segs[k].n_begin);
-            const long long a1 = std::min((long long)p->n0, k + 1 < p->segs.size() ? p->segs[k + 1].n_begin
-                                                                                   : (long long)p->n0);
+            const long long a1 = std::min((long long)p->nco.n0, k + 1 < p->segs.size() ? p->segs[k + 1].n_begin
+                                                                                       : (long long)p->nco.n0);
             if (a1 <= a0)
                 continue;
-            float lc[8], ls[8];
-            lo_steps(p->segs[k].freg, lc, ls);
+            NcoArgs seg;
+            seg.n0 = (unsigned long long)a0;
+            seg.freg = seg.freg_hist = p->segs[k].freg;
+            seg.phase_off = p->segs[k].off;
+            nco_fill_steps(&seg);
             PDDC_HIP_TRY(launch_unpack24(static_cast<const uint8_t *>(h_in) + (a0 - w0) * PDDC_PACKED_BYTES, a1 - a0,
-                                         p->d_hist_f32 + 2 * (a0 - w0), false, true, (unsigned long long)a0,
-                                         p->segs[k].freg, p->segs[k].off, lc, ls, s));
+                                         p->d_hist_f32 + 2 * (a0 - w0), false, &seg, s));
         }
-        PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, true, p->n0, p->freg, p->phase_off,
-                                     p->lo_c, p->lo_s, s));
-        if (n_in[1] > 0)
-            PDDC_HIP_TRY(launch_fir_generic(st.d_buf, p->d_hist_f32, H, (long long)off[0], (long long)n_in[1], st.decim,
-                                            st.d_taps_dup, st.ntaps, dst, nullptr, (long long)nsamples, s));
-        /* hist_done stays false: the packed history moves on below (x == d_packed) */
+        PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, &p->nco, s));
+        /* floats, whose taps k_firp's stage-0 table does not hold (it carries the unpack scale); no hist_out: the
+         * packed history moves on below (x == d_packed) */
+        d.in = st.d_buf, d.hist = p->d_hist_f32, d.hist_out = nullptr, d.taps_firp = nullptr;
     } else if (i == 0 && route == Route::PackedGeneric) {
-        if (n_in[1] > 0) {
-            if (st.d_taps_firp)           /* register-blocked kernel for /4 /5 /8 /10 */
-                PDDC_HIP_TRY(launch_firp_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1], st.decim,
-                                                st.d_taps_firp, st.ntaps, dst, h_out, (long long)nsamples, mix, p->n0,
-                                                p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s, p->lo_c_applied,
-                                                p->lo_s_applied, s));
-            else
-                PDDC_HIP_TRY(launch_fir_generic_packed(d_packed, h_in, st.hist, (long long)off[0], (long long)n_in[1],
-                                                       st.decim, st.d_taps_dup, st.ntaps, dst, h_out, (long long)nsamples,
-                                                       mix, p->n0, p->freg, p->phase_off, p->freg_applied, p->lo_c, p->lo_s,
-                                                       p->lo_c_applied, p->lo_s_applied, s));
-            hist_done = true;             /* block 0 of the kernel wrote the new (packed) history */
-        }
+        d.in = d_packed, d.fmt = IN_PACKED24, d.mix = mix ? &p->nco : nullptr;
     } else {
         if (i == 0) {
             /* generic first stage: unpack(+mix) to float2, then the generic FIR */
             if ((rc = ensure_buf(st, nsamples + 8)))
                 return rc;
-            PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, mix, p->n0, p->freg,
-                                         p->phase_off, p->lo_c, p->lo_s, s));
+            PDDC_HIP_TRY(launch_unpack24(d_packed, (long long)nsamples, st.d_buf, false, mix ? &p->nco : nullptr, s));
         }
-        x = st.d_buf;
+        d.in = x = st.d_buf;
         const bool fast = i > 0 && st.ntb != 0 && !(p->flags & PDDC_F_NO_FAST) &&
                           fir8_supported(st.ntb, p->R) && (n_in[i] % 8 == 0) && off[i] == 0 &&
                           (st.consumed % 8 == 0) && n_in[i] > 0;
@@ -2161,6 +2125,7 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
             fill_fir8_args(p, a);
             PDDC_HIP_TRY(launch_fir8(st.ntb, p->R, IN_F32C, false, a, s));
             hist_done = a.hist_out != nullptr;
+            plain = false;
         } else if (st.interp > 1) {
             if (n_in[i + 1] > 0 && st.d_taps_poly && !(p->flags & PDDC_F_NO_FAST)) {
                 PDDC_HIP_TRY(launch_resample_lds(static_cast<const float *>(x), static_cast<const float *>(h_in), st.hist,
@@ -2173,17 +2138,11 @@ static int run_stage(pddc_pipeline *p, int i, Route route, const BatchPlan &b, c
                                              st.consumed, b.m0[i], (long long)n_in[i + 1], st.interp, st.decim,
                                              st.d_taps, st.ntaps, dst, s));
             }
-        } else if (n_in[i + 1] > 0) {
-            if (st.d_taps_firp)
-                PDDC_HIP_TRY(launch_firp(IN_F32C, false, x, h_in, st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
-                                         st.d_taps_firp, st.ntaps, dst, h_out, (long long)n_in[i], nullptr, s));
-            else
-                PDDC_HIP_TRY(launch_fir_generic(static_cast<const float *>(x), static_cast<const float *>(h_in),
-                                                st.hist, (long long)off[i], (long long)n_in[i + 1], st.decim,
-                                                st.d_taps_dup, st.ntaps, dst, static_cast<float *>(h_out),
-                                                (long long)n_in[i], s));
-            hist_done = true;             /* block 0 of the kernel wrote the new history */
         }
+    }
+    if (plain && d.n_out > 0) {
+        PDDC_HIP_TRY(launch_decim(d, s));
+        hist_done = d.hist_out != nullptr;          /* block 0 of the kernel wrote the new history */
     }
     if (n_in[i] > 0 && !hist_done)
         PDDC_HIP_TRY(launch_hist_update(h_out, h_in, st.hist, x, (long long)n_in[i], st.hist_elem, s));
@@ -2198,10 +2157,10 @@ static void commit_batch(pddc_pipeline *p, const BatchPlan &b)
             p->st[i].cur ^= 1;
         p->st[i].consumed += b.n_in[i];
     }
-    p->n0 += b.n_in[0];
-    if (p->freg_applied != p->freg) {
-        p->freg_applied = p->freg;
-        compute_lo_steps(p);
+    p->nco.n0 += b.n_in[0];
+    if (p->nco.freg_hist != p->nco.freg) {
+        p->nco.freg_hist = p->nco.freg;
+        nco_fill_steps(&p->nco);
     }
     p->fresh = false;
     ++p->hist_ver;
@@ -3114,10 +3073,10 @@ int pddc_pipeline_save_state(pddc_pipeline *p, void *h_buf, size_t capacity, siz
     h.flags = p->flags;
     h.R = p->R;
     h.NT = p->NT;
-    h.n0 = p->n0;
-    h.freg = p->freg;
-    h.phase_off = p->phase_off;
-    h.freg_applied = p->freg_applied;
+    h.n0 = p->nco.n0;
+    h.freg = p->nco.freg;
+    h.phase_off = p->nco.phase_off;
+    h.freg_applied = p->nco.freg_hist;
     h.fresh = p->fresh ? 1u : 0u;
     h.nsegs = (uint32_t)p->segs.size();
     for (int i = 0; i < p->nstages; ++i) {
@@ -3187,13 +3146,13 @@ int pddc_pipeline_restore_state(pddc_pipeline *p, const void *h_buf, size_t nbyt
         s.consumed = h.st[i].consumed;
         r += nb;
     }
-    p->n0 = h.n0;
-    p->freg = h.freg;
-    p->phase_off = h.phase_off;
-    p->freg_applied = h.freg_applied;
+    p->nco.n0 = h.n0;
+    p->nco.freg = h.freg;
+    p->nco.phase_off = h.phase_off;
+    p->nco.freg_hist = h.freg_applied;
     p->fresh = h.fresh != 0;
     ++p->hist_ver;
-    compute_lo_steps(p);
+    nco_fill_steps(&p->nco);
     return PDDC_OK;
 }
 

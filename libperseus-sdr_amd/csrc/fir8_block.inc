@@ -131,7 +131,7 @@
         group_to_float<IN_F32C, false, 4>(h2raw, xi, xq, 0ull, p);
         if (MIX) {      /* stored values are final; inside tile 0 they must become final by * phi_0 */
             float c0, s0;
-            nco_lo((uint32_t)p.n0 * p.freg + p.phase_off, c0, s0);
+            nco_lo((uint32_t)p.nco.n0 * p.nco.freg + p.nco.phase_off, c0, s0);
 #pragma unroll
             for (int e = 0; e < 8; ++e)
                 cmul(xi[e], xq[e], c0, -s0);
@@ -590,15 +590,15 @@
         wg_c[k] = 1.0f;
         wg_s[k] = 0.0f;
         if (MIX && !WTAB)
-            nco_lo((uint32_t)(8 * (gtid + NT * k)) * p.freg, wg_c[k], wg_s[k]);
+            nco_lo((uint32_t)(8 * (gtid + NT * k)) * p.nco.freg, wg_c[k], wg_s[k]);
         if (WTAB) {
 #pragma unroll
             for (int e = 0; e < 8; ++e)
-                nco_lo((uint32_t)(8 * (gtid + NT * k) + e) * p.freg, w_c[k][e], w_s[k][e]);
+                nco_lo((uint32_t)(8 * (gtid + NT * k) + e) * p.nco.freg, w_c[k][e], w_s[k][e]);
         }
     }
     if (MIX)
-        nco_lo((uint32_t)G::TI * p.freg, d_c, d_s);
+        nco_lo((uint32_t)G::TI * p.nco.freg, d_c, d_s);
     /* The tile's phasor is the same for every lane: lane l computes the one of tile ph_base + l, once per 64
      * consecutive tiles, and each tile fetches its own with v_readlane -- the sin/cos polynomial is ~25 VALU
      * instructions, a tenth of what a wave of the fused pair issues per tile (same-box A/B -0.4 %).           */
@@ -610,11 +610,11 @@
         c = 1.0f;
         sn = 0.0f;
         if (MIX && !PHTAB)
-            nco_lo((uint32_t)(p.n0 + (unsigned long long)((long long)tile * G::TI)) * p.freg + p.phase_off, c, sn);
+            nco_lo((uint32_t)(p.nco.n0 + (unsigned long long)((long long)tile * G::TI)) * p.nco.freg + p.nco.phase_off, c, sn);
         if (PHTAB) {
             if (tile < ph_base || tile >= ph_base + 64) {            /* uniform */
                 ph_base = tile;
-                nco_lo(((uint32_t)p.n0 + (uint32_t)(tile + (tid & 63)) * (uint32_t)G::TI) * p.freg + p.phase_off, ph_c,
+                nco_lo(((uint32_t)p.nco.n0 + (uint32_t)(tile + (tid & 63)) * (uint32_t)G::TI) * p.nco.freg + p.nco.phase_off, ph_c,
                        ph_s);
             }
             c  = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ph_c), tile - ph_base));
@@ -658,7 +658,7 @@
                 for (int e = 0; e < 8; ++e)
                     cmul(xi[e], xq[e], w_c[WTAB ? k : 0][e], w_s[WTAB ? k : 0][e]);
             } else if (MIX) {
-                mix8_lo(xi, xq, wg_c[k], wg_s[k], p);
+                mix8_lo(xi, xq, wg_c[k], wg_s[k], p.nco);
             }
             group_to_lds<R>(sI, sQ, v, xi, xq);
         }
@@ -675,11 +675,11 @@
                  * word and its step phasors come with the arguments (== the current ones otherwise). */
                 const bool old = (t == 0);                       /* uniform */
                 float cb, sb;
-                nco_lo((uint32_t)(8 * tid - 8 * npg) * (old ? p.freg_hist : p.freg), cb, sb);
+                nco_lo((uint32_t)(8 * tid - 8 * npg) * (old ? p.nco.freg_hist : p.nco.freg), cb, sb);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float sc = old ? p.lo_c_hist[e] : p.lo_c[e];
-                    const float ss = old ? p.lo_s_hist[e] : p.lo_s[e];
+                    const float sc = old ? p.nco.lo_c_hist[e] : p.nco.lo_c[e];
+                    const float ss = old ? p.nco.lo_s_hist[e] : p.nco.lo_s[e];
                     cmul(xi[e], xq[e], cb * sc - sb * ss, cb * ss + sb * sc);
                 }
             }

@@ -885,6 +885,37 @@ def test_packed_generic_first_stage(pkg, dev, O, D, nt, mix):
     slow.close()
 
 
+@pytest.mark.parametrize("nb", [4096, 32])
+@pytest.mark.parametrize("D,nt", [(10, 69), (7, 99)])
+def test_packed_first_stage_through_retunes(pkg, dev, O, D, nt, nb):
+    """Both kernels behind the plain-decimator launcher on a tuned packed first stage -- by 10 with 69 taps is k_firp's
+    (too long for the matrix cores' decimate-by-10 form), by 7 with 99 taps k_fir_generic's -- through retunes.
+    nb = 4096: four batches, a new word before the third: that batch mixes its packed history with the old word and its
+    own samples with the new one.  nb = 32: batches shorter than the history (72 and 104 samples) with a new word before
+    each of three consecutive ones: the window in front of the third holds three words, and the batch goes through the
+    mixed float history.  Every output against the double oracle, max|y - ref| / max|ref| <= 1e-6."""
+    rng = np.random.default_rng(D * 1000 + nt)
+    h = (rng.standard_normal(nt) / np.sqrt(nt)).astype(np.float32)
+    words = [0x9E3779B1, 381178347, 0x7FFFFFF1, 3000000000]
+    retune = {0: words[0], 2: words[1]} if nb == 4096 else {0: words[0], 4: words[1], 5: words[2], 6: words[3]}
+    nbatch = 4 if nb == 4096 else 12
+    packed = O.lcg_bytes(6 * nb * nbatch, 4242)
+    pipe = pkg.Pipeline([(D, h)], mix=True)
+    assert pipe.stage0_reads_packed and not pipe.fused and not pipe.on_i8(nb)
+    ys = []
+    for k in range(nbatch):
+        if k in retune:
+            pipe.set_freg(retune[k])
+        ys.append(pipe.process(to_dev(packed[6 * nb * k:6 * nb * (k + 1)], dev)).cpu().numpy().reshape(-1))
+    pipe.close()
+    y = np.concatenate(ys)
+    ref = O.ddc_chain_retuned(packed, [(D, h)], [(nb * k, w) for k, w in sorted(retune.items())])
+    err = O.rel_err(y, ref)
+    print(f"first stage /{D}, {nt} taps, batches of {nb}: rel err {err:.3e}")
+    assert y.size == ref.size
+    assert err <= FIR_TOL
+
+
 def test_perseus_api_1600k_plan_is_fused_end_to_end(pkg, dev, O, monkeypatch):
     """The 1.6 MS/s rate (10*5): first stage /10 through the packed-input generic kernel, vs the oracle."""
     import ctypes as C
