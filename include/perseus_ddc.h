@@ -572,6 +572,67 @@ int pddc_tuner_channel(int nchan, uint32_t freg, int *channel, int32_t *residue)
  * set_channels calls (host arithmetic, no device).  -> how many, or a negative PDDC_E* (NULL, nrx <= 0, unsupported nchan) */
 int pddc_tuner_channel_list(int nchan, const uint32_t *freg, int nrx, int *channels /* [nrx] */);
 
+/* ---- demod: AM, FM and SSB audio from the tuner's receivers ---------------------
+ * K receivers, each a complex float32 series z_j[m] at the tuner's output rate, give K real float32
+ * series a_j[m], one output per input.  m counts since create / reset and goes on across batches;
+ * z_j[-1] = 0.  All arithmetic is float32 with floating-point contraction off, the same operation
+ * sequence for every caller and every cut (DESIGN.md 8 spells the sequence).
+ * Detector d_j[m], by the receiver's mode:
+ *   PDDC_DEMOD_AM   d = sqrtf(re re + im im)
+ *   PDDC_DEMOD_FM   p = z[m] conj(z[m-1]) (four multiplies, one add, one subtract),
+ *                   d = atan2f(p.im, p.re) (1/pi), in [-1, 1]: 1 is a deviation of half the output rate.
+ *                   Where there is no older z (the first output after create, reset or a change of mode
+ *                   or flags) d = 0.
+ *   PDDC_DEMOD_SSB  theta = (bfo m + psi) mod 2^32 in unsigned 32-bit arithmetic, psi = 0 at create and
+ *                   reset; d = re c - im s with c + i s = exp(-2 pi i theta / 2^32): the real part of z
+ *                   times the phasor, the sign convention of pddc_nco_freg.  USB, LSB and CW are SSB with a
+ *                   choice of words: tune the tuner to the middle of the wanted sideband, give its low-pass
+ *                   half the sideband's width, and bfo moves the sideband back.
+ * Post stage, by the receiver's flags, sequential in m:
+ *   PDDC_DEMOD_DCBLOCK  y[m] = fmaf(rho, y[m-1], d[m] - d[m-1]), y[-1] = d[-1] = 0; without it y = d
+ *   PDDC_DEMOD_AGC      e[m] = fmaxf(|y[m]|, lambda e[m-1]), e[-1] = 0; g = fminf(gmax, target / e[m])
+ *                       (e = 0 gives gmax); a = y g; without it a = y
+ * rho, lambda, target, gmax are common to all receivers: 0 <= rho, lambda < 1; target, gmax > 0, finite.
+ * Carried per receiver: z[m-1], d[m-1], y[m-1], e[m-1], psi.  The bits of a_j[m] depend on the
+ * receiver's series, its mode / word / flag history and the four parameters alone: not on the cut into
+ * batches (0 outputs included), K, j's index, the other receivers, grid or tile sizes.
+ * set_rx(j, mode, bfo, flags) between two batches takes effect from the next output m0.  The word
+ * alone: phase-continuous, psi' = psi + (bfo - bfo') m0 mod 2^32 (the tuner's rule).  Another mode or
+ * other flags: that receiver's carried z, d, y, e return to their create values and psi = 0; m goes on.
+ * An unknown mode or flag: PDDC_EINVAL, nothing changed.
+ * process(): z is [nrx][z_stride] complex float32 and out [nrx][out_stride] float32, n values used per
+ * row (the strides in elements: the tuner's output view has its capacity as stride).  Every argument
+ * is checked before anything is queued: PDDC_EINVAL for NULL or misaligned (8 / 4 bytes) pointers with
+ * n > 0, PDDC_ECAPACITY when a stride is below n; n = 0 is valid and does nothing.  State moves only
+ * after the launch was accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_DEMOD_AM       0
+#define PDDC_DEMOD_FM       1
+#define PDDC_DEMOD_SSB      2
+#define PDDC_DEMOD_DCBLOCK  0x1u
+#define PDDC_DEMOD_AGC      0x2u
+typedef struct pddc_demod_rx {
+    int mode;             /* PDDC_DEMOD_AM / _FM / _SSB                   */
+    uint32_t bfo;         /* SSB: the BFO word (frequency bfo fs_out / 2^32) */
+    uint32_t flags;       /* PDDC_DEMOD_DCBLOCK | PDDC_DEMOD_AGC          */
+} pddc_demod_rx;
+typedef struct pddc_demod_params {
+    float rho;            /* DC block pole                                */
+    float lambda;         /* AGC envelope decay per output                */
+    float target;         /* AGC output level                             */
+    float gmax;           /* AGC largest gain                             */
+} pddc_demod_params;
+typedef struct pddc_demod pddc_demod;
+int pddc_demod_create(pddc_demod **out, int device, int nrx, const pddc_demod_rx *rx /* [nrx], copied */,
+                      const pddc_demod_params *params);
+int pddc_demod_destroy(pddc_demod *d);
+int pddc_demod_reset(pddc_demod *d);                  /* m, carried values, psi; synchronises the device */
+int pddc_demod_set_rx(pddc_demod *d, int rx, int mode, uint32_t bfo, uint32_t flags);
+int pddc_demod_process(pddc_demod *d, const void *d_z, size_t n, size_t z_stride, void *d_out, size_t out_stride,
+                       void *stream);
+/* outputs per tile of the kernel's walk (for tests that place batch cuts on its seams) */
+int pddc_demod_tile_outputs(void);
+
 /* pinned host memory for the two calls above */
 int pddc_host_alloc(void **h_ptr, size_t nbytes);
 int pddc_host_free(void *h_ptr);

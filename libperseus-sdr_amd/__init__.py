@@ -60,6 +60,16 @@ class StageDesc(C.Structure):
                 ("interp", C.c_int)]
 
 
+class DemodRx(C.Structure):
+    """pddc_demod_rx (include/perseus_ddc.h)"""
+    _fields_ = [("mode", C.c_int), ("bfo", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class DemodParams(C.Structure):
+    """pddc_demod_params (include/perseus_ddc.h)"""
+    _fields_ = [("rho", C.c_float), ("lam", C.c_float), ("target", C.c_float), ("gmax", C.c_float)]
+
+
 _ddc = None
 
 
@@ -224,6 +234,15 @@ def ddc_lib() -> C.CDLL:
     L.pddc_tuner_next_outputs.restype = C.c_uint64
     L.pddc_tuner_outputs.argtypes = [C.c_int, C.c_int, C.c_uint64, sz]
     L.pddc_tuner_outputs.restype = C.c_uint64
+    L.pddc_demod_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(DemodRx), C.POINTER(DemodParams)]
+    L.pddc_demod_destroy.argtypes = [vp]
+    L.pddc_demod_reset.argtypes = [vp]
+    L.pddc_demod_set_rx.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32]
+    L.pddc_demod_process.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    L.pddc_demod_tile_outputs.argtypes = []
+    for name in ("pddc_demod_create", "pddc_demod_destroy", "pddc_demod_reset", "pddc_demod_set_rx", "pddc_demod_process",
+                 "pddc_demod_tile_outputs"):
+        getattr(L, name).restype = C.c_int
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
     L.pddc_pipeline_time_stage0_inline.restype = C.c_int
@@ -733,7 +752,7 @@ def _packed_arg(kind, packed, nsamples):
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer and Tuner share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner and Demod share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1019,6 +1038,73 @@ class Tuner(_StreamObject):
         ch, ptr = _channel_list(channels)
         check(ddc_lib().pddc_tuner_set_channels(self._h, ptr, ch.size))
         self.channels, self.first, self.count = ch, 0, int(ch.size)
+
+
+PDDC_DEMOD_AM, PDDC_DEMOD_FM, PDDC_DEMOD_SSB = 0, 1, 2
+PDDC_DEMOD_DCBLOCK, PDDC_DEMOD_AGC = 0x1, 0x2
+
+
+def demod_tile_outputs() -> int:
+    """pddc_demod_tile_outputs: outputs per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_demod_tile_outputs())
+
+
+def demod_ssb_words(fs: float, out_rate: float, carrier_hz: float, lo_hz: float, hi_hz: float, upper: bool = True):
+    """The two words of a single-sideband receiver for the audio band lo_hz .. hi_hz above (upper) or below the carrier:
+    the Tuner's word, tuned to the middle of that sideband (pddc_nco_freg's rule on fs, the ADC rate), and the BFO word
+    of Demod at out_rate, which moves the sideband back: an audio tone f comes out of the tuner at f - (lo + hi) / 2
+    (upper) or (lo + hi) / 2 - f (lower), and the phasor exp(-2 pi i bfo m / 2^32) puts it at +f or -f, whose real part
+    is the tone.  Give the Tuner's low-pass the half width (hi - lo) / 2.  CW is a narrow band around the wanted pitch.
+    -> (tuner word, bfo), both in 0 .. 2^32 - 1."""
+    mid = 0.5 * (float(lo_hz) + float(hi_hz))
+    sign = 1.0 if upper else -1.0
+    word = int((float(carrier_hz) + sign * mid) / float(fs) * 4294967296.0) & 0xFFFFFFFF
+    bfo = int(round(-sign * mid / float(out_rate) * 4294967296.0)) & 0xFFFFFFFF
+    return word, bfo
+
+
+class Demod(_StreamObject):
+    """pddc_demod: AM, FM and SSB audio from complex series such as Tuner.process returns, one real float32 output per
+    input, on the device (include/perseus_ddc.h).  rx: one (mode, bfo, flags) per receiver -- mode PDDC_DEMOD_AM / _FM /
+    _SSB, bfo the 32-bit BFO word of SSB (demod_ssb_words), flags PDDC_DEMOD_DCBLOCK | PDDC_DEMOD_AGC.  rho (DC block
+    pole), lam (AGC envelope decay per output), target and gmax (AGC level and largest gain) are common to all
+    receivers.  Feed it every batch in order on one stream; outputs are bit-identical however the series is cut."""
+    _kind = "demod"
+
+    def __init__(self, rx, device: int = 0, rho: float = 0.995, lam: float = 0.9995, target: float = 0.25,
+                 gmax: float = 1.0e4):
+        rx = [tuple(r) for r in rx]
+        self.nrx, self.device = len(rx), device
+        arr = (DemodRx * max(self.nrx, 1))()
+        for j, (mode, bfo, flags) in enumerate(rx):
+            arr[j] = DemodRx(int(mode), int(bfo) & 0xFFFFFFFF, int(flags) & 0xFFFFFFFF)
+        self.params = DemodParams(rho, lam, target, gmax)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_demod_create(C.byref(h), device, self.nrx, arr, C.byref(self.params)))
+        self._h = h
+
+    def process(self, z, out=None, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the view Tuner.process
+        returns is fine).  -> float32 [nrx, n] (a view of `out`, a float32 CUDA tensor [nrx, capacity] with contiguous
+        rows, if given)."""
+        import torch
+        if z.dtype != torch.complex64 or z.dim() != 2 or z.shape[0] != self.nrx or (z.shape[1] > 1 and z.stride(1) != 1):
+            raise PddcError(-1, "demod: z must be a complex64 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        if out is None:
+            out = torch.empty((self.nrx, n), dtype=torch.float32, device=torch.device("cuda", self.device))
+        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != self.nrx or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise PddcError(-1, "demod: out must be a float32 tensor [nrx, capacity] with contiguous rows")
+        # the C ABI takes row strides; a capacity below n must reach it as one (PDDC_ECAPACITY) whatever the view's stride
+        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        check(ddc_lib().pddc_demod_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                           out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
+        return out[:, :n]
+
+    def set_rx(self, rx: int, mode: int, bfo: int = 0, flags: int = 0):
+        """receiver rx from the next output on: another word alone goes on phase-continuously, another mode or other
+        flags start that receiver's carried values afresh"""
+        check(ddc_lib().pddc_demod_set_rx(self._h, rx, int(mode), int(bfo) & 0xFFFFFFFF, int(flags) & 0xFFFFFFFF))
 
 
 class PinnedBuffer:

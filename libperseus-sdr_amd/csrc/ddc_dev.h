@@ -1,6 +1,6 @@
 /*
  * ddc_dev.h -- device-side helpers shared by the kernel translation units (ddc_kernels.hip, ddc_fir_i8.hip, ddc_tuner.hip,
- * and through ddc_packed.h the panorama and the channelizer).
+ * ddc_demod.hip, and through ddc_packed.h the panorama and the channelizer).
  * Internal; gfx950 only.
  */
 #ifndef PDDC_DDC_DEV_H
