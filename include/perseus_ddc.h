@@ -564,6 +564,11 @@ int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_
                        size_t *n_out, void *stream);
 /* outputs per receiver the NEXT process() of nrows writes */
 uint64_t pddc_tuner_next_outputs(const pddc_tuner *t, size_t nrows);
+/* what process(nrows) would launch now (host arithmetic: launches nothing, moves no counter):
+ * out = { receivers per block, outputs per tile, outputs per run, blocks along the outputs, rows carried afterwards }
+ * -- block x of a receiver group owns the outputs [x run, (x + 1) run) of the batch, tile by tile; with no outputs
+ * { group, tile, 0, 0, carried }.  For tests, which place their cases on these seams. */
+int pddc_tuner_schedule(const pddc_tuner *t, size_t nrows, int out[5]);
 /* the same without an object (host arithmetic, no device); 0 for unsupported sizes */
 uint64_t pddc_tuner_outputs(int ntaps, int decim, uint64_t rows_before, size_t nrows);
 /* channel and residue of a word (host arithmetic, no device); either pointer may be NULL */

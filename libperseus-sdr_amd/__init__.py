@@ -226,9 +226,10 @@ def ddc_lib() -> C.CDLL:
     L.pddc_tuner_channel.argtypes = [C.c_int, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int32)]
     L.pddc_tuner_set_channels.argtypes = [vp, C.POINTER(C.c_int), C.c_int]
     L.pddc_tuner_channel_list.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int)]
+    L.pddc_tuner_schedule.argtypes = [vp, sz, C.POINTER(C.c_int)]
     for f in (L.pddc_tuner_create, L.pddc_tuner_destroy, L.pddc_tuner_reset, L.pddc_tuner_set_freq,
               L.pddc_tuner_set_range, L.pddc_tuner_process, L.pddc_tuner_channel, L.pddc_tuner_set_channels,
-              L.pddc_tuner_channel_list):
+              L.pddc_tuner_channel_list, L.pddc_tuner_schedule):
         f.restype = C.c_int
     L.pddc_tuner_next_outputs.argtypes = [vp, sz]
     L.pddc_tuner_next_outputs.restype = C.c_uint64
@@ -995,6 +996,13 @@ class Tuner(_StreamObject):
     def next_outputs(self, nrows: int) -> int:
         """outputs per receiver the next process() of nrows rows writes (known from sizes alone)"""
         return int(ddc_lib().pddc_tuner_next_outputs(self._h, nrows))
+
+    def schedule(self, nrows: int) -> dict:
+        """pddc_tuner_schedule: what process() of nrows rows would launch now -- receivers per block, outputs per tile,
+        outputs per run, blocks along the outputs, rows carried afterwards.  Launches nothing, moves no counter."""
+        o = (C.c_int * 5)()
+        check(ddc_lib().pddc_tuner_schedule(self._h, nrows, o))
+        return {"group": o[0], "tile": o[1], "run": o[2], "blocks": o[3], "carried": o[4]}
 
     def process(self, rows, nrows=None, out=None, stream=None):
         """One batch of rows: the complex64 CUDA tensor [nrows, count] Channelizer.process returned (or a device

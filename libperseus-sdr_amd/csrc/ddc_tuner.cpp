@@ -81,6 +81,37 @@ static void tune_build_table(pddc_tuner *t)
     std::stable_sort(t->table.begin(), t->table.end(), [](const TuneRx &x, const TuneRx &y) { return x.col < y.col; });
 }
 
+/* what a batch of nrows launches: process() launches it, pddc_tuner_schedule reports it */
+struct TunePlan {
+    uint64_t m0, nout;                              /* outputs before this batch, outputs of this batch           */
+    int group, tile;                                /* receivers per block, outputs per tile                      */
+    long long run, blocks;                          /* outputs per block (a multiple of tile), blocks along them  */
+    uint64_t carried;                               /* rows the next batch's first output still needs             */
+};
+
+static TunePlan tune_plan(const pddc_tuner *t, size_t nrows)
+{
+    TunePlan p{};
+    const uint64_t R = (uint64_t)t->decim, total = t->rows + nrows;
+    p.m0 = windows_complete(t->ntaps, t->decim, t->rows);
+    const uint64_t m1 = windows_complete(t->ntaps, t->decim, total);
+    p.nout = m1 - p.m0;
+    p.group = tune_group(t->ntaps);
+    p.tile = tune_tile_outputs(t->ntaps, t->decim);
+    if (p.nout) {
+        /* outputs per block: the batch spread over the blocks that keep the device busy, but never runs so short that
+         * the porch (ntaps - 1 rows read again per run) outweighs them -- at least 4 (ntaps - 1) rows per run */
+        const long long groups = (t->nrx + p.group - 1) / p.group;
+        const long long runs = std::max(1LL, (long long)t->target_blocks / groups);
+        long long run = ((long long)p.nout + runs - 1) / runs;
+        run = std::max(run, (4LL * (t->ntaps - 1) + t->decim - 1) / t->decim);
+        p.run = (std::max(run, 1LL) + p.tile - 1) / p.tile * p.tile;
+        p.blocks = ((long long)p.nout + p.run - 1) / p.run;
+    }
+    p.carried = total > m1 * R ? total - m1 * R : 0;     /* m1 R: the first row the next output needs */
+    return p;
+}
+
 static void tune_free(pddc_tuner *t)
 {
     hipFree(t->d_table);
@@ -269,6 +300,19 @@ int pddc_tuner_channel_list(int nchan, const uint32_t *freg, int nrx, int *chann
     return n;
 }
 
+int pddc_tuner_schedule(const pddc_tuner *t, size_t nrows, int out[5])
+{
+    if (!t || !out)
+        return pddc_set_error_(PDDC_EINVAL, "null argument");
+    const TunePlan p = tune_plan(t, nrows);
+    out[0] = p.group;
+    out[1] = p.tile;
+    out[2] = (int)p.run;
+    out[3] = (int)p.blocks;
+    out[4] = (int)p.carried;
+    return PDDC_OK;
+}
+
 int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_out, size_t out_stride, size_t *n_out,
                        void *stream)
 {
@@ -277,9 +321,8 @@ int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_
     if (nrows && (!d_rows || ((uintptr_t)d_rows & 7)))
         return pddc_set_error_(PDDC_EINVAL, "d_rows must be an 8-byte aligned device pointer");
     const uint64_t R = (uint64_t)t->decim;
-    const uint64_t m0 = windows_complete(t->ntaps, t->decim, t->rows);
-    const uint64_t m1 = windows_complete(t->ntaps, t->decim, t->rows + nrows);
-    const uint64_t nout = m1 - m0;
+    const TunePlan plan = tune_plan(t, nrows);
+    const uint64_t m0 = plan.m0, nout = plan.nout;
     if (nout && (!d_out || ((uintptr_t)d_out & 7)))
         return pddc_set_error_(PDDC_EINVAL, "d_out must be an 8-byte aligned device pointer");
     if (nout > out_stride)
@@ -314,25 +357,17 @@ int pddc_tuner_process(pddc_tuner *t, const void *d_rows, size_t nrows, void *d_
     a.out = static_cast<float2 *>(d_out);
     a.out_stride = (long long)out_stride;
     if (nout) {
-        /* outputs per block: the batch spread over the blocks that keep the device busy, but never runs so short that
-         * the porch (ntaps - 1 rows read again per run) outweighs them -- at least 4 (ntaps - 1) rows per run */
-        const int g = tune_group(t->ntaps);
-        a.co = tune_tile_outputs(t->ntaps, t->decim);
-        const long long groups = (t->nrx + g - 1) / g;
-        const long long runs = std::max(1LL, (long long)t->target_blocks / groups);
-        long long run = ((long long)nout + runs - 1) / runs;
-        run = std::max(run, (4LL * (t->ntaps - 1) + t->decim - 1) / t->decim);
-        a.run = (std::max(run, 1LL) + a.co - 1) / a.co * a.co;
+        a.co = plan.tile;
+        a.run = plan.run;
         PDDC_HIP_TRY(launch_tune(a, st));
     }
-    const uint64_t keep_from = m1 * R;              /* the first row the next output needs */
-    const bool carries = total > keep_from;
+    const bool carries = plan.carried > 0;
     if (carries) {
         TuneCarryArgs c{};
         c.t = a;
         c.new_carry = t->d_carry[t->cur ^ 1];
         c.keep_u = (long long)(nout * R);
-        c.new_len = (int)(total - keep_from);
+        c.new_len = (int)plan.carried;
         PDDC_HIP_TRY(launch_tune_carry(c, st));
     }
     /* every launch was accepted: only now do the host-side counters move */

@@ -283,3 +283,123 @@ def test_float32_models_against_double(lcg19):
     print(f"worst: tuner {worst_t:.3e} (TOL_TUNER {TR.TOL_TUNER:.3e}), chain {worst_c:.3e} (TOL_CHAIN {TR.TOL_CHAIN:.3e})")
     assert worst_t <= 1.005 * TR.MODEL_WORST_TUNER and worst_c <= 1.005 * TR.MODEL_WORST_CHAIN
     assert TR.TOL_TUNER == 7 * TR.MODEL_WORST_TUNER and TR.TOL_CHAIN == 7 * TR.MODEL_WORST_CHAIN
+
+
+def test_receiver_set_in_a_wrapped_range():
+    """receiver_set_in: every word's channel lies in the range, wrapped or not; the boundary residues sit on the range's
+    first and last channel and on channel 0 where the range holds it; two words are identical; about nrx / count
+    receivers share a column."""
+    for M, first, count, nrx in ((1024, 1024 - 20, 64, 1024), (4096, 4094, 4, 16), (1024, 100, 50, 300), (1024, 0, 1024, 64)):
+        words = TR.receiver_set_in(M, first, count, nrx)
+        assert len(words) == nrx and words == TR.receiver_set_in(M, first, count, nrx)
+        cols = TR.columns_of(M, first, words)
+        assert cols.min() >= 0 and cols.max() < count
+        half = 1 << (31 - (M.bit_length() - 1))
+        kr = [TR.channel_of(M, f) for f in words]
+        ends = [first, (first + count - 1) % M] + ([0] if (0 - first) % M < count and first and (first + count - 1) % M else [])
+        for k in ends:
+            for r in (-half, -1, 0, 1, half - 1):
+                assert (k, r) in kr, (M, first, k, r)
+        if nrx > 5 * len(ends) + 1:
+            assert len(set(words)) < nrx
+    cols = TR.columns_of(1024, 1024 - 20, TR.receiver_set_in(1024, 1024 - 20, 64, 1024))
+    per = np.bincount(cols, minlength=64)
+    print(f"receivers per column, K 1024 on 64: {per.min()} .. {per.max()}")
+    assert per.min() >= 4 and per.max() >= 16 and (cols == 20).sum() >= 5          # channel 0 is column 20
+
+
+def test_fir_decim_mm_is_fir_decim():
+    """The sliding-window matrix product gives fir_decim's sums (another order, in double): <= 1e-13 of the largest value,
+    at sizes on both sides of its block and with a ragged last block."""
+    rng = np.random.default_rng(3)
+    for T, Rd, S in ((1, 1, 50), (2, 1, 300), (5, 4, 333), (64, 64, 1000), (130, 7, 1500), (512, 1, 1500), (512, 63, 1500),
+                     (64, 4, 63), (64, 4, 64)):
+        z = rng.standard_normal((S, 7)) + 1j * rng.standard_normal((S, 7))
+        for h in (TR.random_lowpass(T), TR.kaiser_lowpass(T, Rd)):
+            a, b = TR.fir_decim(z, h, Rd), TR.fir_decim_mm(z, h, Rd)
+            assert a.shape == b.shape == (TR.noutputs_of(S, T, Rd), 7)
+            if a.size:
+                assert TR.err(b, a) <= 1e-13, (T, Rd, TR.err(b, a))
+                assert TR.err(TR.fir_decim_mm(z, h, Rd, block=3), a) <= 1e-13
+
+
+def test_tunerref_from_a_row_offset():
+    """A TunerRef started at row0 = 1000 with the words and the phi a full run had there, handed the rows from 1000 on
+    with the same later retune, gives the full run's outputs from output 1000 / R on: <= 1e-12 of the largest value.  The
+    phi there is also what the rule gives in exact integers."""
+    M, D, T, Rd, S, row0 = 1024, 512, 64, 4, 3000, 1000
+    first, count = 1024 - 20, 64
+    y = TR.gaussian_rows(S, count, seed=5).astype(np.complex128)
+    words = TR.receiver_set_in(M, first, count, 12)
+    h = TR.kaiser_lowpass(T, Rd)
+    f1, f2, f3 = (3 << 22) + 4321, (1023 << 22) - 77, (0 << 22) + (1 << 21) - 1
+    full = TR.TunerRef(M, D, words, h, Rd)
+    outs = [full.process(y[:400], first)]
+    full.set_freq(2, f1)
+    full.set_freq(5, f2)
+    outs.append(full.process(y[400:row0], first))
+    there_words, there_phi = list(full.words), list(full.phi)
+    assert there_phi[2] == ((words[2] - f1) * ((400 * D) & TR.MASK)) & TR.MASK and there_phi[0] == 0
+    outs.append(full.process(y[row0:1200], first))
+    full.set_freq(2, f3)
+    outs.append(full.process(y[1200:], first))
+    want = np.concatenate(outs, axis=1)
+    part = TR.TunerRef(M, D, there_words, h, Rd, row0=row0, phi=there_phi)
+    got = [part.process(y[row0:1200], first)]
+    part.set_freq(2, f3)
+    got.append(part.process(y[1200:], first))
+    got = np.concatenate(got, axis=1)
+    assert part.phi == full.phi
+    assert got.shape[1] == TR.noutputs_of(S - row0, T, Rd) and want.shape[1] == TR.noutputs_of(S, T, Rd)
+    e = TR.err(got, want[:, row0 // Rd:])
+    print(f"TunerRef from row {row0}: {e:.2e}")
+    assert e <= 1e-12
+    one = TR.tuner_ref_range(y[row0:], M, D, first, there_words, h, Rd, phi=there_phi, row0=row0)
+    before = np.arange(one.shape[1]) * Rd + T - 1 < 1200 - row0
+    assert before.sum() > 10 and TR.err(one[:, before], got[:, before]) <= 1e-12
+
+
+def test_schedule_refuses_a_null_handle(pkg):
+    o = (C.c_int * 5)()
+    assert pkg.ddc_lib().pddc_tuner_schedule(None, 100, o) == pkg.PDDC_EINVAL
+    assert pkg.ddc_lib().pddc_tuner_schedule(None, 100, None) == pkg.PDDC_EINVAL
+
+
+def test_float32_model_on_the_shape_cases():
+    """The measurement that sets TOL_TUNER_SHAPES, on the inputs of tests/test_gpu_tuner_shapes.py: the float32 model
+    against the double reference on the same complex64 rows (seeded Gaussian, seed 99).  (a) 8300 rows of the wrapped
+    64-channel range of M = 1024, hop 512, the 1024 receivers of receiver_set_in, every (T, R) of CASES_TR_SHAPES, Kaiser
+    and random h; (b) the deep windows: M = 4096, hop 4096 and 2048, 16 receivers on the wrapped 4-channel range, 4096
+    rows from row0 = v - 2048 and w - 2048 (s D passes 2^31 at v, 2^32 at w), (T, R) of CASES_DEEP.  A re-measurement may
+    not exceed the written worst case by more than 0.5 %."""
+    worst = 0.0
+    M, D, first, count, S = TR.SHAPES_GRID
+    y64 = TR.gaussian_rows(S, count)
+    words = TR.receiver_set_in(M, first, count, 1024)
+    res = [TR.channel_of(M, f)[1] for f in words]
+    phi = [0] * len(words)
+    ycols = y64[:, TR.columns_of(M, first, words)]
+    z = TR.mix(ycols.astype(np.complex128), res, phi, D)
+    for T, Rd in TR.CASES_TR_SHAPES:
+        for name, h in (("kaiser", TR.kaiser_lowpass(T, Rd)), ("random", TR.random_lowpass(T))):
+            e = TR.err(TR.tuner_model_f32(ycols, res, phi, D, h, Rd), TR.fir_decim_mm(z, h, Rd).T)
+            print(f"T {T} R {Rd} {name}: {e:.3e}")
+            worst = max(worst, e)
+    M, first, count = TR.DEEP_GRID
+    words = TR.receiver_set_in(M, first, count, 16)
+    res = [TR.channel_of(M, f)[1] for f in words]
+    phi = [0] * len(words)
+    for D in (4096, 2048):
+        w = (1 << 32) // D
+        rows = TR.gaussian_rows(w + 4096, count)
+        for row0 in (w // 2 - 2048, w - 2048):
+            ycols = rows[row0:row0 + 4096][:, TR.columns_of(M, first, words)]
+            z = TR.mix(ycols.astype(np.complex128), res, phi, D, row0)
+            for T, Rd in TR.CASES_DEEP:
+                for name, h in (("kaiser", TR.kaiser_lowpass(T, Rd)), ("random", TR.random_lowpass(T))):
+                    e = TR.err(TR.tuner_model_f32(ycols, res, phi, D, h, Rd, row0), TR.fir_decim_mm(z, h, Rd).T)
+                    print(f"deep D {D} row0 {row0} T {T} R {Rd} {name}: {e:.3e}")
+                    worst = max(worst, e)
+    print(f"worst: {worst:.3e} (MODEL_WORST_TUNER_SHAPES {TR.MODEL_WORST_TUNER_SHAPES:.3e}, TOL {TR.TOL_TUNER_SHAPES:.3e})")
+    assert worst <= 1.005 * TR.MODEL_WORST_TUNER_SHAPES
+    assert TR.TOL_TUNER_SHAPES == 7 * TR.MODEL_WORST_TUNER_SHAPES
