@@ -638,6 +638,47 @@ int pddc_demod_process(pddc_demod *d, const void *d_z, size_t n, size_t z_stride
 /* outputs per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_demod_tile_outputs(void);
 
+/* ---- audio: the receivers' audio at a standard rate, float32 or int16 PCM -----
+ * nrx receivers, each a real float32 series x_j[i] such as the demodulator writes, give nrx real
+ * series y_j[k] at L/M times the input rate: 9765.625 Hz -> 48 kHz is 3072/625.  i and k count since
+ * create / reset and go on across batches; x_j[i] = 0 for i < 0.  Fixed at create, common to all
+ * receivers: the ratio L/M (1 <= L, M <= 2^24, M <= 16 L; given reduced or not, stored reduced), P
+ * phases (a power of two, 32 .. 1024), T taps per phase (1 .. 64, P T <= 8192), the real prototype
+ * g[0 .. P T) (copied; g[P T] := 0) and scale (finite, > 0; 32767 maps +-1 to full-scale PCM).
+ * Position of output k, in exact integers: v = k M, n_k = v div L, r_k = v mod L; u = r_k P,
+ * q = u div L, alpha = float(u mod L) / float(L), one correctly rounded float32 division.
+ * Value, float32 with floating-point contraction off, the same operation sequence for every caller
+ * and every cut: acc = 0; for t = 0 .. T-1 ascending: g0 = g[t P + q], g1 = g[t P + q + 1],
+ * w = fmaf(alpha, g1 - g0, g0), acc = fmaf(w, x[n_k - t], acc); y[k] = acc.  That is x convolved with
+ * the piecewise-linear interpolation of g, sampled at n_k + r_k / L; no input after n_k is used.
+ * Output k exists once input n_k is in the stream: ceil(N L / M) outputs after N inputs, so a batch's
+ * count follows from sizes alone (pddc_audio_next_outputs; pddc_audio_outputs without an object).
+ * PCM: p = (int16) clamp(rintf(y scale), -32768, 32767), ties to even; NaN gives 0.
+ * Carried: per receiver its last T - 1 inputs; the object N and the next output's n and r, advanced
+ * batch by batch, so nothing wraps at any stream length.  The bits of y_j[k] depend on the receiver's
+ * series, L, M, P, T and g alone: not on the cut into batches (0 inputs and 0 outputs included), nrx,
+ * j's index, the other receivers, strides, grid or tile sizes.
+ * process(): x is [nrx][x_stride] float32 with n values used per row (the demodulator's output view
+ * has its capacity as stride); d_f32 [nrx][f32_stride] float32 and d_i16 [nrx][i16_stride] int16 get
+ * *count values per row; either may be NULL, not both when there are outputs.  Every argument is
+ * checked before anything is queued: PDDC_EINVAL for a NULL or misaligned (4 / 4 / 2 bytes) pointer
+ * with work to do, PDDC_ECAPACITY when a stride is below what it must hold; n = 0 is valid.  State
+ * moves only after the launch was accepted.  Stream-ordered; one stream per object, one thread at a
+ * time.  create: argument errors (the limits above, a non-finite prototype value) before any device
+ * access; good arguments, no device: PDDC_ENODEV.  Another ratio or prototype: another object. */
+typedef struct pddc_audio pddc_audio;
+int pddc_audio_create(pddc_audio **out, int device, int nrx, uint32_t L, uint32_t M, int phases, int taps,
+                      const float *proto /* [phases * taps], copied */, float scale);
+int pddc_audio_destroy(pddc_audio *a);
+int pddc_audio_reset(pddc_audio *a);                  /* N, n, r, the carried inputs; synchronises the device */
+/* outputs per receiver the next process() of n inputs writes (host arithmetic) */
+int pddc_audio_next_outputs(const pddc_audio *a, size_t n, size_t *count);
+/* the same without an object (host arithmetic, no device): ceil((before + n) L / M) - ceil(before L / M);
+ * 0 for L or M outside 1 .. 2^24 */
+uint64_t pddc_audio_outputs(uint32_t L, uint32_t M, uint64_t inputs_before, size_t n);
+int pddc_audio_process(pddc_audio *a, const void *d_x, size_t n, size_t x_stride, void *d_f32, size_t f32_stride,
+                       void *d_i16, size_t i16_stride, size_t *count, void *stream);
+
 /* pinned host memory for the two calls above */
 int pddc_host_alloc(void **h_ptr, size_t nbytes);
 int pddc_host_free(void *h_ptr);

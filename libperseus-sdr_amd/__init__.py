@@ -244,6 +244,16 @@ def ddc_lib() -> C.CDLL:
     for name in ("pddc_demod_create", "pddc_demod_destroy", "pddc_demod_reset", "pddc_demod_set_rx", "pddc_demod_process",
                  "pddc_demod_tile_outputs"):
         getattr(L, name).restype = C.c_int
+    L.pddc_audio_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
+                                    C.POINTER(C.c_float), C.c_float]
+    L.pddc_audio_destroy.argtypes = [vp]
+    L.pddc_audio_reset.argtypes = [vp]
+    L.pddc_audio_next_outputs.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_audio_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, C.POINTER(sz), vp]
+    for name in ("pddc_audio_create", "pddc_audio_destroy", "pddc_audio_reset", "pddc_audio_next_outputs", "pddc_audio_process"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_audio_outputs.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, sz]
+    L.pddc_audio_outputs.restype = C.c_uint64
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
     L.pddc_pipeline_time_stage0_inline.restype = C.c_int
@@ -753,7 +763,7 @@ def _packed_arg(kind, packed, nsamples):
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner and Demod share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Demod and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1113,6 +1123,110 @@ class Demod(_StreamObject):
         """receiver rx from the next output on: another word alone goes on phase-continuously, another mode or other
         flags start that receiver's carried values afresh"""
         check(ddc_lib().pddc_demod_set_rx(self._h, rx, int(mode), int(bfo) & 0xFFFFFFFF, int(flags) & 0xFFFFFFFF))
+
+
+AUDIO_MAX_RATIO, AUDIO_MAX_DECIM = 1 << 24, 16
+
+
+def audio_outputs(L: int, M: int, inputs_before: int, n: int) -> int:
+    """pddc_audio_outputs: outputs of n inputs after inputs_before, ceil((before + n) L / M) - ceil(before L / M); host
+    arithmetic, no device"""
+    return int(ddc_lib().pddc_audio_outputs(L, M, inputs_before, n))
+
+
+def audio_ratio(fs_hz, hop: int, decim: int, out_rate):
+    """The ratio that takes the chain's rate fs_hz / (hop * decim) -- Channelizer hop, Tuner decim -- to out_rate,
+    reduced, in exact rational arithmetic: audio_ratio(80e6, 512, 16, 48000) is (3072, 625).  Raises when L or M exceeds
+    2^24 or M > 16 L (Audio's limits).  -> (L, M)"""
+    from fractions import Fraction
+    f = Fraction(out_rate) * int(hop) * int(decim) / Fraction(fs_hz)
+    if f <= 0:
+        raise PddcError(-1, "audio_ratio: the rates, hop and decim must be positive")
+    L, M = f.numerator, f.denominator
+    if L > AUDIO_MAX_RATIO or M > AUDIO_MAX_RATIO or M > AUDIO_MAX_DECIM * L:
+        raise PddcError(-1, f"audio_ratio: {L}/{M} is outside Audio's limits (1 .. 2^24 each, M <= 16 L)")
+    return L, M
+
+
+def audio_prototype(phases: int, taps: int, cutoff=None, beta: float = 9.0):
+    """Audio's prototype: a Kaiser-windowed sinc over phases * taps points, -6 dB at `cutoff` cycles per INPUT sample
+    (default 0.45; for a ratio L/M below 1 pass 0.45 * L / M, so that the band ends below the output's Nyquist
+    frequency), double, normalised so that the sum is `phases` (every phase then sums to about 1), rounded once.
+    -> numpy float32[phases * taps]."""
+    import numpy as np
+    P, T = int(phases), int(taps)
+    if P <= 0 or T <= 0:
+        raise PddcError(-1, "audio_prototype: phases and taps must be positive")
+    fc = 0.45 if cutoff is None else float(cutoff)
+    t = (np.arange(P * T, dtype=np.float64) - (P * T - 1) / 2.0) / P     # in input samples
+    g = np.sinc(2.0 * fc * t) * np.kaiser(P * T, float(beta))
+    return (g * (P / g.sum())).astype(np.float32)
+
+
+class Audio(_StreamObject):
+    """pddc_audio: the receivers' real float32 series, such as Demod.process returns, resampled by the exact ratio L/M
+    (audio_ratio) with an interpolated polyphase filter -- `phases` stored phases of `taps` taps, the prototype `proto`
+    (audio_prototype; default: one for this ratio), linear interpolation between neighbouring phases -- as float32 and /
+    or saturated int16 PCM, p = clamp(rint(y * scale)), on the device (include/perseus_ddc.h).  Feed it every batch in
+    order on one stream; outputs are bit-identical however the series is cut."""
+    _kind = "audio"
+
+    def __init__(self, nrx: int, L: int, M: int, phases: int = 128, taps: int = 32, proto=None, scale: float = 32767.0,
+                 device: int = 0):
+        import math
+        import numpy as np
+        L, M = int(L), int(M)
+        if not (0 < L < 1 << 32 and 0 < M < 1 << 32):
+            raise PddcError(-1, "audio: L and M must be in 1 .. 2^24")
+        if proto is None:
+            proto = audio_prototype(phases, taps, 0.45 * min(1.0, L / M))
+        g = np.ascontiguousarray(np.asarray(proto, dtype=np.float32).reshape(-1))
+        if g.size != int(phases) * int(taps):
+            raise PddcError(-1, "audio: the prototype must have phases * taps values")
+        d = math.gcd(L, M)
+        self.nrx, self.device, self.L, self.M = int(nrx), device, L // d, M // d
+        self.phases, self.taps, self.proto, self.scale = int(phases), int(taps), g, float(scale)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_audio_create(C.byref(h), device, self.nrx, L, M, self.phases, self.taps,
+                                          g.ctypes.data_as(C.POINTER(C.c_float)), self.scale))
+        self._h = h
+
+    def next_outputs(self, n: int) -> int:
+        """outputs per receiver the next process() of n inputs writes (known from sizes alone)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_audio_next_outputs(self._h, n, C.byref(c)))
+        return int(c.value)
+
+    def process(self, x, f32: bool = True, i16: bool = False, out_f32=None, out_i16=None, stream=None):
+        """One batch: a float32 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the view Demod.process
+        returns is fine).  -> float32 [nrx, count] if f32, int16 [nrx, count] if i16, both as a tuple if both (views of
+        `out_f32` / `out_i16`, CUDA tensors [nrx, capacity] with contiguous rows, if given; giving one asks for it)."""
+        import torch
+        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.nrx or (x.shape[1] > 1 and x.stride(1) != 1):
+            raise PddcError(-1, "audio: x must be a float32 tensor [nrx, n] with contiguous rows")
+        f32, i16 = f32 or out_f32 is not None, i16 or out_i16 is not None
+        if not (f32 or i16):
+            raise PddcError(-1, "audio: ask for float32, int16 or both")
+        n = int(x.shape[1])
+        due = self.next_outputs(n)
+        outs = []
+        for want, out, dt, name in ((f32, out_f32, torch.float32, "out_f32"), (i16, out_i16, torch.int16, "out_i16")):
+            if not want:
+                outs.append(None)
+                continue
+            if out is None:
+                out = torch.empty((self.nrx, due), dtype=dt, device=torch.device("cuda", self.device))
+            elif out.dtype != dt or out.dim() != 2 or out.shape[0] != self.nrx or (out.shape[1] > 1 and out.stride(1) != 1):
+                raise PddcError(-1, f"audio: {name} must be a {dt} tensor [nrx, capacity] with contiguous rows")
+            outs.append(out)
+        # the C ABI takes row strides; a capacity below the count must reach it as one (PDDC_ECAPACITY) whatever the view's stride
+        ptr = [o.data_ptr() if o is not None and o.numel() else None for o in outs]
+        cap = [0 if o is None else int(o.stride(0)) if o.shape[1] >= due else int(o.shape[1]) for o in outs]
+        c = C.c_size_t()
+        check(ddc_lib().pddc_audio_process(self._h, x.data_ptr() if n else None, n, int(x.stride(0)), ptr[0], cap[0], ptr[1],
+                                           cap[1], C.byref(c), self._stream(stream)))
+        views = [o[:, :c.value] for o in outs if o is not None]
+        return views[0] if len(views) == 1 else tuple(views)
 
 
 class PinnedBuffer:
