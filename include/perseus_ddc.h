@@ -638,6 +638,44 @@ int pddc_demod_process(pddc_demod *d, const void *d_z, size_t n, size_t z_stride
 /* outputs per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_demod_tile_outputs(void);
 
+/* ---- rxfilter: each receiver its own bandwidth from a filter bank ----------------
+ * A stage between the tuner and the demodulator.  Receiver j's input is z_j[i], complex float32; i
+ * counts since create / reset and goes on across batches; z_j[i] = 0 for i < 0 (zero history, as in
+ * audio).  One output per input, so the demodulator's m behind it is the same m.
+ * Fixed at create: nrx (1 .. 1024); a bank of B filters (1 .. 64) of T real float32 taps each
+ * (1 .. 256), bank[f T + t], copied, every value finite; per receiver a filter index f_j in [0, B).
+ * Value, float32 with floating-point contraction off, the same operation sequence for every caller
+ * and every cut: acc = (0, 0); for t = 0 .. T-1 ascending: acc.re = fmaf(h_f[t], z_j[m - t].re, acc.re)
+ * and the same for im; out_j[m] = acc, with f = f_j(m).  All T taps are always run: a shorter filter
+ * is padded with zeros by the caller.  Symmetric filters of one bank share the delay (T - 1) / 2, so
+ * the receivers stay aligned in time.
+ * set_rx(j, f') between two batches takes effect from the next output m0: outputs m >= m0 use h_f'
+ * over the same inputs, the carried ones before m0 included -- what is carried is inputs, not filter
+ * state, so nothing is reset and there is no gap.  f' outside [0, B) or j outside [0, nrx):
+ * PDDC_EINVAL, nothing changed.
+ * Carried per receiver: its last T - 1 inputs; the object carries m, for reporting only.  The bits of
+ * out_j[m] depend on the receiver's series, its filter history and the bank alone: not on the cut
+ * into batches (batches of 0, 1 and fewer than T - 1 inputs included), nrx, j's index, the other
+ * receivers and their filters, strides, grid or tile sizes.
+ * process(): z is [nrx][z_stride] and out [nrx][out_stride] complex float32, n values used per row
+ * (the strides in elements: the tuner's output view has its capacity as stride).  Every argument is
+ * checked before anything is queued: PDDC_EINVAL for NULL or not 8-byte aligned pointers with n > 0,
+ * PDDC_ECAPACITY when a stride is below n, PDDC_EINVAL when the input and output byte ranges overlap
+ * (tiles read their neighbours' inputs: in place is not supported); n = 0 is valid, launches nothing
+ * and changes nothing.  State moves only after the launch was accepted.  Stream-ordered; one stream
+ * per object, one thread at a time.  create: argument errors before any device access; good
+ * arguments, no device: PDDC_ENODEV. */
+typedef struct pddc_rxfilter pddc_rxfilter;
+int pddc_rxfilter_create(pddc_rxfilter **out, int device, int nrx, const float *bank /* [nfilters][ntaps], copied */,
+                         int nfilters, int ntaps, const int *sel /* [nrx] */);
+int pddc_rxfilter_destroy(pddc_rxfilter *f);
+int pddc_rxfilter_reset(pddc_rxfilter *f);            /* m and the carried inputs; synchronises the device */
+int pddc_rxfilter_set_rx(pddc_rxfilter *f, int rx, int filter);
+int pddc_rxfilter_process(pddc_rxfilter *f, const void *d_z, size_t n, size_t z_stride, void *d_out, size_t out_stride,
+                          void *stream);
+/* outputs per tile of the kernel's walk (for tests that place batch cuts on its seams) */
+int pddc_rxfilter_tile_outputs(void);
+
 /* ---- audio: the receivers' audio at a standard rate, float32 or int16 PCM -----
  * nrx receivers, each a real float32 series x_j[i] such as the demodulator writes, give nrx real
  * series y_j[k] at L/M times the input rate: 9765.625 Hz -> 48 kHz is 3072/625.  i and k count since

@@ -244,6 +244,15 @@ def ddc_lib() -> C.CDLL:
     for name in ("pddc_demod_create", "pddc_demod_destroy", "pddc_demod_reset", "pddc_demod_set_rx", "pddc_demod_process",
                  "pddc_demod_tile_outputs"):
         getattr(L, name).restype = C.c_int
+    L.pddc_rxfilter_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.pddc_rxfilter_destroy.argtypes = [vp]
+    L.pddc_rxfilter_reset.argtypes = [vp]
+    L.pddc_rxfilter_set_rx.argtypes = [vp, C.c_int, C.c_int]
+    L.pddc_rxfilter_process.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    L.pddc_rxfilter_tile_outputs.argtypes = []
+    for name in ("pddc_rxfilter_create", "pddc_rxfilter_destroy", "pddc_rxfilter_reset", "pddc_rxfilter_set_rx",
+                 "pddc_rxfilter_process", "pddc_rxfilter_tile_outputs"):
+        getattr(L, name).restype = C.c_int
     L.pddc_audio_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
                                     C.POINTER(C.c_float), C.c_float]
     L.pddc_audio_destroy.argtypes = [vp]
@@ -763,7 +772,7 @@ def _packed_arg(kind, packed, nsamples):
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Demod and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, RxFilter, Demod and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1056,6 +1065,73 @@ class Tuner(_StreamObject):
         ch, ptr = _channel_list(channels)
         check(ddc_lib().pddc_tuner_set_channels(self._h, ptr, ch.size))
         self.channels, self.first, self.count = ch, 0, int(ch.size)
+
+
+def rxfilter_tile_outputs() -> int:
+    """pddc_rxfilter_tile_outputs: outputs per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_rxfilter_tile_outputs())
+
+
+def rxfilter_bank(rate_hz: float, half_widths_hz, ntaps: int, beta: float = 8.0):
+    """A bank for RxFilter: one Kaiser-windowed sinc of ntaps taps per half width, -6 dB at half_width Hz of a series at
+    rate_hz (tuner_lowpass's formula with fc = half_width / rate_hz), double, sum 1, rounded once.  All rows have the
+    delay (ntaps - 1) / 2.  A half width <= 0 or >= rate_hz / 2 is refused.  -> numpy float32[len(half_widths_hz), ntaps]."""
+    import numpy as np
+    ntaps, rate = int(ntaps), float(rate_hz)
+    w = np.asarray(half_widths_hz, dtype=np.float64).reshape(-1)
+    if ntaps <= 0 or not rate > 0.0 or w.size == 0:
+        raise PddcError(-1, "rxfilter_bank: ntaps, the rate and the number of half widths must be positive")
+    if not np.all((w > 0.0) & (w < 0.5 * rate)):
+        raise PddcError(-1, "rxfilter_bank: every half width must lie in (0, rate / 2)")
+    t = np.arange(ntaps, dtype=np.float64) - (ntaps - 1) / 2.0
+    win = np.kaiser(ntaps, float(beta))
+    rows = [np.sinc(2.0 * (hw / rate) * t) * win for hw in w]
+    return np.stack([(h / h.sum()).astype(np.float32) for h in rows])
+
+
+class RxFilter(_StreamObject):
+    """pddc_rxfilter: every receiver's complex series, such as Tuner.process returns, through one of a bank of real FIR
+    filters -- each receiver its own bandwidth -- one output per input, on the device (include/perseus_ddc.h).  bank:
+    float32 [B, T] (rxfilter_bank), sel: one filter index per receiver.  It goes between Tuner and Demod.  Feed it
+    every batch in order on one stream; outputs are bit-identical however the series is cut."""
+    _kind = "rxfilter"
+
+    def __init__(self, bank, sel, device: int = 0):
+        import numpy as np
+        b = np.asarray(bank, dtype=np.float32)
+        if b.ndim != 2:
+            raise PddcError(-1, "rxfilter: the bank must be a float32 array [filters, taps]")
+        b = np.ascontiguousarray(b)
+        s = np.ascontiguousarray(np.asarray(sel, dtype=np.int64).reshape(-1).clip(-1, 1 << 30), dtype=np.int32)
+        self.bank, self.nrx, self.device = b, int(s.size), device
+        self.nfilters, self.taps = int(b.shape[0]), int(b.shape[1])
+        h = C.c_void_p()
+        check(ddc_lib().pddc_rxfilter_create(C.byref(h), device, self.nrx, b.ctypes.data_as(C.POINTER(C.c_float)),
+                                             self.nfilters, self.taps, s.ctypes.data_as(C.POINTER(C.c_int))))
+        self._h = h
+
+    def process(self, z, out=None, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the view Tuner.process
+        returns is fine).  -> complex64 [nrx, n] (a view of `out`, a complex64 CUDA tensor [nrx, capacity] with contiguous
+        rows, if given).  `out` must not overlap z."""
+        import torch
+        if z.dtype != torch.complex64 or z.dim() != 2 or z.shape[0] != self.nrx or (z.shape[1] > 1 and z.stride(1) != 1):
+            raise PddcError(-1, "rxfilter: z must be a complex64 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        if out is None:
+            out = torch.empty((self.nrx, n), dtype=torch.complex64, device=torch.device("cuda", self.device))
+        elif out.dtype != torch.complex64 or out.dim() != 2 or out.shape[0] != self.nrx or (out.shape[1] > 1 and out.stride(1) != 1):
+            raise PddcError(-1, "rxfilter: out must be a complex64 tensor [nrx, capacity] with contiguous rows")
+        # the C ABI takes row strides; a capacity below n must reach it as one (PDDC_ECAPACITY) whatever the view's stride
+        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        check(ddc_lib().pddc_rxfilter_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                              out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
+        return out[:, :n]
+
+    def set_rx(self, rx: int, filter: int):
+        """receiver rx from the next output on: the bank's filter `filter` over the same inputs, the carried ones
+        included -- nothing is reset"""
+        check(ddc_lib().pddc_rxfilter_set_rx(self._h, int(rx), int(filter)))
 
 
 PDDC_DEMOD_AM, PDDC_DEMOD_FM, PDDC_DEMOD_SSB = 0, 1, 2
