@@ -676,6 +676,93 @@ int pddc_rxfilter_process(pddc_rxfilter *f, const void *d_z, size_t n, size_t z_
 /* outputs per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_rxfilter_tile_outputs(void);
 
+/* ---- squelch: per-receiver level meter and gated audio ------------------------
+ * A stage between the demodulator and audio.  Per batch it reads the receivers' complex series
+ * z_j[m] (the rows the demodulator reads) and their audio a_j[m] (the demodulator's output at the
+ * same m) and gives the gated audio out_j[m], per completed metering block a level and an open /
+ * closed state, and on request a status per receiver.  m counts samples since create / reset and
+ * goes on across batches.  All arithmetic is float32 with floating-point contraction off, the same
+ * operation sequence for every caller and every cut.
+ * Fixed at create, common to all receivers: nrx (1 .. 1024); B, the block length in samples
+ * (1 .. 4096); attack and hang, the consecutive blocks to open and to close (1 .. 65535 each); R, the
+ * ramp length in samples (1 .. 65536); up, the noise floor's rise per block (finite, >= 1).
+ * invB = 1.0f / (float)B and invR = 1.0f / (float)R, one correctly rounded division each.
+ * Per receiver, changeable between batches with set_rx: open_thr and close_thr, finite,
+ * 0 <= close_thr <= open_thr; flags, a subset of PDDC_SQL_GATE | PDDC_SQL_RELATIVE.
+ * Carried per receiver, with the values at create / reset: the partial sum s = 0, the floor
+ * f = +inf, level = 0, peak = 0, open = 0, run = 0, opens = 0 (uint32 both), the ramp counter c = 0
+ * with GATE, else R.  The object carries the sample count N (uint64).
+ * Per sample m, in order:
+ *   1. p = (re re) + (im im); s = s + p.
+ *   2. the target is R if open or GATE is not set, else 0; towards R: c = min(c + 1, R), towards 0:
+ *      c = max(c - 1, 0).
+ *   3. c == R: out = a (g = 1.0f: a's bits pass unchanged); c == 0: out = +0.0f whatever a is;
+ *      otherwise g = (float)c invR and out = a g.
+ * At the end of a block, after the sample with (m + 1) mod B == 0, in order:
+ *   1. L = s invB; s = 0.
+ *   2. if !open: f = fminf(L, f up) -- the floor is frozen while open.
+ *   3. with RELATIVE: to = f open_thr, tc = f close_thr; without: the thresholds themselves.
+ *   4. if !open: run = (L >= to) ? run + 1 : 0; on run >= attack: open = 1, run = 0, ++opens.
+ *   5. else: run = !(L >= tc) ? run + 1 : 0; on run >= hang: open = 0, run = 0.
+ *   6. peak = fmaxf(peak, L); level = L.
+ * The decision of block k governs the target from the first sample of block k + 1: no look-ahead,
+ * no added delay.
+ * set_rx(j, open_thr, close_thr, flags): the thresholds take effect from the next block end, the
+ * flags from the next sample; nothing carried is reset.  An unknown flag, thresholds out of order or
+ * not finite, j outside [0, nrx): PDDC_EINVAL, nothing changed.
+ * The bits of every output and every carried value depend on the receiver's two series, its
+ * threshold and flag history and the create parameters alone: not on the cut into batches (batches of
+ * 0 and of fewer than B samples included), nrx, j's index, the other receivers, strides, grid or tile
+ * sizes.
+ * process(): z is [nrx][z_stride] complex float32, a [nrx][a_stride] and out [nrx][out_stride]
+ * float32, n values used per row; d_level float32 and d_state uint8, [nrx][blk_stride] each or NULL,
+ * get *blocks = floor((N + n) / B) - floor(N / B) values per row: entry k of a row belongs to the
+ * k-th block completed in this batch, the level L and `open` after the decision.  Every argument is
+ * checked before anything is queued: PDDC_EINVAL for a NULL (z, a, out) or misaligned (8 / 4 / 4 /
+ * 4 / 1 bytes) pointer with work to do, PDDC_ECAPACITY when a stride is below what the row must
+ * hold; d_out == d_a with equal strides is allowed (gating in place), any other overlap of out with
+ * a or z is PDDC_EINVAL; n = 0 is valid and does nothing.  State moves only after the launch was
+ * accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * read(): the status of every receiver after the batches submitted so far (it waits for them);
+ * clear_peak: peak restarts at 0 for the blocks that complete after the call.
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_SQL_GATE      0x1u
+#define PDDC_SQL_RELATIVE  0x2u
+typedef struct pddc_squelch_params {
+    int block;            /* B: samples per metering block                */
+    int attack;           /* consecutive blocks at or above open to open  */
+    int hang;             /* consecutive blocks below close to close      */
+    int ramp;             /* R: samples of the gain ramp                  */
+    float up;             /* the floor's rise per block while closed      */
+} pddc_squelch_params;
+typedef struct pddc_squelch_rx {
+    float open_thr;
+    float close_thr;
+    uint32_t flags;       /* PDDC_SQL_GATE | PDDC_SQL_RELATIVE            */
+} pddc_squelch_rx;
+typedef struct pddc_squelch_status {
+    float level, floor, peak;
+    uint32_t open, opens;
+} pddc_squelch_status;
+typedef struct pddc_squelch pddc_squelch;
+int pddc_squelch_create(pddc_squelch **out, int device, int nrx, const pddc_squelch_params *params,
+                        const pddc_squelch_rx *rx /* [nrx], copied */);
+int pddc_squelch_destroy(pddc_squelch *s);
+int pddc_squelch_reset(pddc_squelch *s);              /* N and everything carried; synchronises the device */
+int pddc_squelch_set_rx(pddc_squelch *s, int rx, float open_thr, float close_thr, uint32_t flags);
+int pddc_squelch_process(pddc_squelch *s, const void *d_z, const void *d_a, size_t n, size_t z_stride, size_t a_stride,
+                         void *d_out, size_t out_stride, void *d_level /* float [nrx][blk_stride] or NULL */,
+                         void *d_state /* uint8 [nrx][blk_stride] or NULL */, size_t blk_stride, size_t *blocks,
+                         void *stream);
+/* blocks per receiver the next process() of n samples completes (host arithmetic) */
+int pddc_squelch_next_blocks(const pddc_squelch *s, size_t n, size_t *count);
+/* the same without an object (host arithmetic, no device): floor((before + n) / B) - floor(before / B);
+ * 0 for B outside 1 .. 4096 */
+uint64_t pddc_squelch_blocks(int block, uint64_t samples_before, size_t n);
+int pddc_squelch_read(pddc_squelch *s, pddc_squelch_status *host /* [nrx] */, int clear_peak, void *stream);
+/* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
+int pddc_squelch_tile_outputs(void);
+
 /* ---- audio: the receivers' audio at a standard rate, float32 or int16 PCM -----
  * nrx receivers, each a real float32 series x_j[i] such as the demodulator writes, give nrx real
  * series y_j[k] at L/M times the input rate: 9765.625 Hz -> 48 kHz is 3072/625.  i and k count since

@@ -70,6 +70,16 @@ class DemodParams(C.Structure):
     _fields_ = [("rho", C.c_float), ("lam", C.c_float), ("target", C.c_float), ("gmax", C.c_float)]
 
 
+class SquelchParams(C.Structure):
+    """pddc_squelch_params (include/perseus_ddc.h)"""
+    _fields_ = [("block", C.c_int), ("attack", C.c_int), ("hang", C.c_int), ("ramp", C.c_int), ("up", C.c_float)]
+
+
+class SquelchRx(C.Structure):
+    """pddc_squelch_rx (include/perseus_ddc.h)"""
+    _fields_ = [("open_thr", C.c_float), ("close_thr", C.c_float), ("flags", C.c_uint32)]
+
+
 _ddc = None
 
 
@@ -253,6 +263,19 @@ def ddc_lib() -> C.CDLL:
     for name in ("pddc_rxfilter_create", "pddc_rxfilter_destroy", "pddc_rxfilter_reset", "pddc_rxfilter_set_rx",
                  "pddc_rxfilter_process", "pddc_rxfilter_tile_outputs"):
         getattr(L, name).restype = C.c_int
+    L.pddc_squelch_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(SquelchParams), C.POINTER(SquelchRx)]
+    L.pddc_squelch_destroy.argtypes = [vp]
+    L.pddc_squelch_reset.argtypes = [vp]
+    L.pddc_squelch_set_rx.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_uint32]
+    L.pddc_squelch_process.argtypes = [vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, sz, C.POINTER(sz), vp]
+    L.pddc_squelch_next_blocks.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_squelch_read.argtypes = [vp, vp, C.c_int, vp]
+    L.pddc_squelch_tile_outputs.argtypes = []
+    for name in ("pddc_squelch_create", "pddc_squelch_destroy", "pddc_squelch_reset", "pddc_squelch_set_rx",
+                 "pddc_squelch_process", "pddc_squelch_next_blocks", "pddc_squelch_read", "pddc_squelch_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_squelch_blocks.argtypes = [C.c_int, C.c_uint64, sz]
+    L.pddc_squelch_blocks.restype = C.c_uint64
     L.pddc_audio_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
                                     C.POINTER(C.c_float), C.c_float]
     L.pddc_audio_destroy.argtypes = [vp]
@@ -772,7 +795,7 @@ def _packed_arg(kind, packed, nsamples):
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, RxFilter, Demod and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, RxFilter, Demod, Squelch and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1199,6 +1222,113 @@ class Demod(_StreamObject):
         """receiver rx from the next output on: another word alone goes on phase-continuously, another mode or other
         flags start that receiver's carried values afresh"""
         check(ddc_lib().pddc_demod_set_rx(self._h, rx, int(mode), int(bfo) & 0xFFFFFFFF, int(flags) & 0xFFFFFFFF))
+
+
+PDDC_SQL_GATE, PDDC_SQL_RELATIVE = 0x1, 0x2
+
+
+def squelch_tile_outputs() -> int:
+    """pddc_squelch_tile_outputs: samples per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_squelch_tile_outputs())
+
+
+def squelch_blocks(block: int, samples_before: int, n: int) -> int:
+    """pddc_squelch_blocks: blocks of `block` samples that n samples after samples_before complete,
+    (before + n) // block - before // block; 0 for an unsupported block length; host arithmetic, no device"""
+    block = int(block)
+    return int(ddc_lib().pddc_squelch_blocks(block if -1 << 31 <= block < 1 << 31 else 0, samples_before, n))
+
+
+def squelch_status_dtype():
+    """pddc_squelch_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("level", np.float32), ("floor", np.float32), ("peak", np.float32), ("open", np.uint32),
+                     ("opens", np.uint32)])
+
+
+class Squelch(_StreamObject):
+    """pddc_squelch: a level meter and a gate per receiver, on the device (include/perseus_ddc.h).  It goes between
+    Demod and Audio and reads the complex series Demod reads together with Demod's audio: the mean power of every
+    `block` samples is a level; a receiver opens after `attack` consecutive blocks at or above its open threshold and
+    closes after `hang` consecutive blocks below its close threshold; the audio is passed through a linear gain ramp of
+    `ramp` samples.  rx: one (open_thr, close_thr, flags) per receiver, flags PDDC_SQL_GATE (without it the audio passes
+    ungated and the receiver is metered only) | PDDC_SQL_RELATIVE (the thresholds are factors of the receiver's noise
+    floor, the smallest level seen while closed, which rises by the factor `up` per block).  Feed it every batch in
+    order on one stream; all outputs are bit-identical however the series is cut."""
+    _kind = "squelch"
+
+    def __init__(self, rx, block: int, attack: int, hang: int, ramp: int, up: float = 1.0, device: int = 0):
+        rx = [tuple(r) for r in rx]
+        self.nrx, self.device = len(rx), device
+        arr = (SquelchRx * max(self.nrx, 1))()
+        for j, (open_thr, close_thr, flags) in enumerate(rx):
+            arr[j] = SquelchRx(float(open_thr), float(close_thr), int(flags) & 0xFFFFFFFF)
+        clip = lambda v: max(-1, min(int(v), 1 << 30))
+        self.block, self.attack, self.hang, self.ramp, self.up = int(block), int(attack), int(hang), int(ramp), float(up)
+        self.params = SquelchParams(clip(block), clip(attack), clip(hang), clip(ramp), up)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_squelch_create(C.byref(h), device, self.nrx, C.byref(self.params), arr))
+        self._h = h
+
+    def next_blocks(self, n: int) -> int:
+        """blocks per receiver the next process() of n samples completes (known from sizes alone)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_squelch_next_blocks(self._h, n, C.byref(c)))
+        return int(c.value)
+
+    def process(self, z, a, out=None, levels=None, states=None, stream=None):
+        """One batch: z a complex64 and a a float32 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the
+        views Tuner.process and Demod.process return are fine).  -> (out float32 [nrx, n], levels float32 [nrx, blocks],
+        states uint8 [nrx, blocks]): views of `out`, `levels`, `states`, CUDA tensors [nrx, capacity] with contiguous
+        rows, if given; levels and states must then have the same row stride.  `out` may be `a` itself (gating in place);
+        it must not overlap z or a otherwise."""
+        import torch
+        def rows(t, dt):
+            return t.dtype == dt and t.dim() == 2 and t.shape[0] == self.nrx and (t.shape[1] <= 1 or t.stride(1) == 1)
+        if not rows(z, torch.complex64) or not rows(a, torch.float32) or a.shape[1] != z.shape[1]:
+            raise PddcError(-1, "squelch: z must be a complex64 and a a float32 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        due = self.next_blocks(n)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((self.nrx, n), dtype=torch.float32, device=dev)
+        elif not rows(out, torch.float32):
+            raise PddcError(-1, "squelch: out must be a float32 tensor [nrx, capacity] with contiguous rows")
+        if levels is None and states is None:
+            # one row stride for both
+            levels = torch.empty((self.nrx, due), dtype=torch.float32, device=dev)
+            states = torch.empty((self.nrx, due), dtype=torch.uint8, device=dev)
+        elif levels is None:
+            levels = torch.empty((self.nrx, int(states.stride(0))), dtype=torch.float32, device=dev)
+        elif states is None:
+            states = torch.empty((self.nrx, int(levels.stride(0))), dtype=torch.uint8, device=dev)
+        if not rows(levels, torch.float32) or not rows(states, torch.uint8):
+            raise PddcError(-1, "squelch: levels must be a float32 and states a uint8 tensor [nrx, capacity] with contiguous rows")
+        if due and self.nrx > 1 and levels.stride(0) != states.stride(0):
+            raise PddcError(-1, "squelch: levels and states must have the same row stride")
+        # the C ABI takes row strides; a capacity below the count must reach it as one (PDDC_ECAPACITY) whatever the view's stride
+        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        bcap = int(levels.stride(0)) if min(levels.shape[1], states.shape[1]) >= due else int(min(levels.shape[1], states.shape[1]))
+        c = C.c_size_t()
+        check(ddc_lib().pddc_squelch_process(self._h, z.data_ptr() if n else None, a.data_ptr() if n else None, n,
+                                             int(z.stride(0)), int(a.stride(0)), out.data_ptr() if out.numel() else None, cap,
+                                             levels.data_ptr() if levels.numel() else None,
+                                             states.data_ptr() if states.numel() else None, bcap, C.byref(c),
+                                             self._stream(stream)))
+        return out[:, :n], levels[:, :c.value], states[:, :c.value]
+
+    def set_rx(self, rx: int, open_thr: float, close_thr: float, flags: int = 0):
+        """receiver rx: the thresholds from the next block end on, the flags from the next sample on; nothing carried
+        is reset"""
+        check(ddc_lib().pddc_squelch_set_rx(self._h, int(rx), float(open_thr), float(close_thr), int(flags) & 0xFFFFFFFF))
+
+    def read(self, clear_peak: bool = False, stream=None):
+        """-> numpy structured array [nrx] (level, floor, peak, open, opens) after the batches submitted so far (it
+        waits for them); clear_peak: peak restarts at 0 for the blocks that complete after the call"""
+        import numpy as np
+        st = np.zeros(self.nrx, dtype=squelch_status_dtype())
+        check(ddc_lib().pddc_squelch_read(self._h, st.ctypes.data, 1 if clear_peak else 0, self._stream(stream)))
+        return st
 
 
 AUDIO_MAX_RATIO, AUDIO_MAX_DECIM = 1 << 24, 16
