@@ -763,6 +763,74 @@ int pddc_squelch_read(pddc_squelch *s, pddc_squelch_status *host /* [nrx] */, in
 /* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_squelch_tile_outputs(void);
 
+/* ---- adapt: automatic notch and noise reduction per receiver -------------------
+ * A stage between the squelch (or the demodulator) and audio: an adaptive line enhancer, a leaky
+ * normalised LMS predictor over a delayed copy of the audio.  Per batch it reads the receivers' real
+ * float32 series x_j[m] (the rows the demodulator and the squelch write) and gives out_j[m]: the
+ * prediction (noise reduction: what is predictable stays), the prediction error (notch: a carrier
+ * whistle goes) or x itself.  m counts samples since create / reset and goes on across batches;
+ * x[m] = 0 for m < 0.  All arithmetic is float32 with floating-point contraction off, every division
+ * the correctly rounded one, denormals kept, the same operation sequence for every caller and cut.
+ * Fixed at create, common to all receivers: nrx (1 .. 1024); T taps (16, 32, 64 or 128); the delay
+ * D (1 .. 256); eps (finite, > 0).
+ * Per receiver, changeable between batches with set_rx: mode, PDDC_ADAPT_OFF / _NR / _NOTCH; the
+ * step mu, 0 < mu < 2; the leak, 0 <= leak < 1, from which lam = 1.0f - leak, one float32
+ * subtraction.  All finite.
+ * Carried per receiver: the weights w_0 .. w_(T-1), 0 at create / reset, and its last D + T - 1
+ * inputs.  Nothing else.
+ * The tree sum of T values v_0 .. v_(T-1): for h = T/2, T/4, .. 1: v_k = v_k + v_(k+h) for k < h;
+ * the sum is v_0.
+ * Per sample m, with u_k = x[m - D - k], k = 0 .. T-1, in order:
+ *   1. y = tree sum of (w_k u_k); P = tree sum of (u_k u_k).
+ *   2. e = x[m] - y.
+ *   3. g = (mu e) / (P + eps).
+ *   4. unless OFF: w_k = (w_k lam) + (g u_k) for every k.
+ *   5. out = y with NR, e with NOTCH; with OFF out has the bits of x[m] and the weights are not
+ *      touched -- the inputs go on being carried, so a receiver switched on again resumes with the
+ *      weights it held.
+ * set_rx(j, mode, mu, leak, flags): from the next sample on; the weights are kept unless flags has
+ * PDDC_ADAPT_RESTART, which takes that receiver's weights as 0 from the next sample on (a mark the
+ * next batch with n > 0 honours; nothing on the device is cleared from the host).  A mode, step,
+ * leak or flag outside the above, not finite, j outside [0, nrx): PDDC_EINVAL, nothing changed.
+ * The bits of every output and every weight depend on the receiver's series, its set_rx history, T,
+ * D and eps alone: not on the cut into batches (batches of 0 included), nrx, j's index, the other
+ * receivers, strides, grid or tile sizes.
+ * process(): a is [nrx][a_stride] and out [nrx][out_stride] float32, n values used per row.  Every
+ * argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned (4 bytes)
+ * pointer with work to do, PDDC_ECAPACITY when a stride is below n; d_out == d_a with equal strides
+ * is allowed (in place), any other overlap of out with a is PDDC_EINVAL; n = 0 is valid and does
+ * nothing.  State moves only after the launch was accepted.  Stream-ordered; one stream per object,
+ * one thread at a time.
+ * read_weights(): the weights [nrx][T] as the last accepted batch left them (it waits for it): the
+ * predictor's impulse response, from which a display draws the notch's frequency response.
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_ADAPT_OFF     0u
+#define PDDC_ADAPT_NR      1u
+#define PDDC_ADAPT_NOTCH   2u
+#define PDDC_ADAPT_RESTART 0x1u
+typedef struct pddc_adapt_params {
+    int taps;             /* T: 16, 32, 64 or 128                         */
+    int delay;            /* D: 1 .. 256                                  */
+    float eps;            /* added to the power before the division       */
+} pddc_adapt_params;
+typedef struct pddc_adapt_rx {
+    uint32_t mode;        /* PDDC_ADAPT_OFF, _NR, _NOTCH                  */
+    float mu;             /* step, 0 < mu < 2                             */
+    float leak;           /* 0 <= leak < 1                                */
+    uint32_t flags;       /* PDDC_ADAPT_RESTART (set_rx)                  */
+} pddc_adapt_rx;
+typedef struct pddc_adapt pddc_adapt;
+int pddc_adapt_create(pddc_adapt **out, int device, int nrx, const pddc_adapt_params *params,
+                      const pddc_adapt_rx *rx /* [nrx], copied */);
+int pddc_adapt_destroy(pddc_adapt *s);
+int pddc_adapt_reset(pddc_adapt *s);                  /* everything carried; synchronises the device */
+int pddc_adapt_set_rx(pddc_adapt *s, int rx, uint32_t mode, float mu, float leak, uint32_t flags);
+int pddc_adapt_process(pddc_adapt *s, const void *d_a, size_t n, size_t a_stride, void *d_out, size_t out_stride,
+                       void *stream);
+int pddc_adapt_read_weights(pddc_adapt *s, float *host /* [nrx][taps] */, void *stream);
+/* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
+int pddc_adapt_tile_outputs(void);
+
 /* ---- audio: the receivers' audio at a standard rate, float32 or int16 PCM -----
  * nrx receivers, each a real float32 series x_j[i] such as the demodulator writes, give nrx real
  * series y_j[k] at L/M times the input rate: 9765.625 Hz -> 48 kHz is 3072/625.  i and k count since

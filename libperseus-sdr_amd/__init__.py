@@ -80,6 +80,16 @@ class SquelchRx(C.Structure):
     _fields_ = [("open_thr", C.c_float), ("close_thr", C.c_float), ("flags", C.c_uint32)]
 
 
+class AdaptParams(C.Structure):
+    """pddc_adapt_params (include/perseus_ddc.h)"""
+    _fields_ = [("taps", C.c_int), ("delay", C.c_int), ("eps", C.c_float)]
+
+
+class AdaptRx(C.Structure):
+    """pddc_adapt_rx (include/perseus_ddc.h)"""
+    _fields_ = [("mode", C.c_uint32), ("mu", C.c_float), ("leak", C.c_float), ("flags", C.c_uint32)]
+
+
 _ddc = None
 
 
@@ -276,6 +286,16 @@ def ddc_lib() -> C.CDLL:
         getattr(L, name).restype = C.c_int
     L.pddc_squelch_blocks.argtypes = [C.c_int, C.c_uint64, sz]
     L.pddc_squelch_blocks.restype = C.c_uint64
+    L.pddc_adapt_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(AdaptParams), C.POINTER(AdaptRx)]
+    L.pddc_adapt_destroy.argtypes = [vp]
+    L.pddc_adapt_reset.argtypes = [vp]
+    L.pddc_adapt_set_rx.argtypes = [vp, C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_uint32]
+    L.pddc_adapt_process.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    L.pddc_adapt_read_weights.argtypes = [vp, vp, vp]
+    L.pddc_adapt_tile_outputs.argtypes = []
+    for name in ("pddc_adapt_create", "pddc_adapt_destroy", "pddc_adapt_reset", "pddc_adapt_set_rx", "pddc_adapt_process",
+                 "pddc_adapt_read_weights", "pddc_adapt_tile_outputs"):
+        getattr(L, name).restype = C.c_int
     L.pddc_audio_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
                                     C.POINTER(C.c_float), C.c_float]
     L.pddc_audio_destroy.argtypes = [vp]
@@ -795,7 +815,7 @@ def _packed_arg(kind, packed, nsamples):
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, RxFilter, Demod, Squelch and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, RxFilter, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1329,6 +1349,71 @@ class Squelch(_StreamObject):
         st = np.zeros(self.nrx, dtype=squelch_status_dtype())
         check(ddc_lib().pddc_squelch_read(self._h, st.ctypes.data, 1 if clear_peak else 0, self._stream(stream)))
         return st
+
+
+PDDC_ADAPT_OFF, PDDC_ADAPT_NR, PDDC_ADAPT_NOTCH = 0, 1, 2
+PDDC_ADAPT_RESTART = 0x1
+
+
+def adapt_tile_outputs() -> int:
+    """pddc_adapt_tile_outputs: samples per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_adapt_tile_outputs())
+
+
+class Adapt(_StreamObject):
+    """pddc_adapt: automatic notch and noise reduction per receiver, on the device (include/perseus_ddc.h).  It goes
+    between Squelch (or Demod) and Audio: a leaky normalised LMS predictor of `taps` taps (16, 32, 64, 128) over the audio
+    delayed by `delay` samples (1 .. 256); what it predicts is the noise-reduced audio (PDDC_ADAPT_NR), what it cannot
+    predict is the audio with carrier whistles removed (PDDC_ADAPT_NOTCH); PDDC_ADAPT_OFF passes the audio and holds the
+    weights.  rx: one (mode, mu, leak) per receiver, the step 0 < mu < 2 and the leak 0 <= leak < 1.  Feed it every
+    batch in order on one stream; all outputs are bit-identical however the series is cut."""
+    _kind = "adapt"
+
+    def __init__(self, rx, taps: int, delay: int, eps: float = 1.0e-6, device: int = 0):
+        rx = [tuple(r) for r in rx]
+        self.nrx, self.device = len(rx), device
+        arr = (AdaptRx * max(self.nrx, 1))()
+        for j, r in enumerate(rx):
+            mode, mu, leak = r[:3]
+            arr[j] = AdaptRx(int(mode) & 0xFFFFFFFF, float(mu), float(leak), (int(r[3]) if len(r) > 3 else 0) & 0xFFFFFFFF)
+        clip = lambda v: max(-1, min(int(v), 1 << 30))
+        self.taps, self.delay, self.eps = int(taps), int(delay), float(eps)
+        self.params = AdaptParams(clip(taps), clip(delay), eps)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_adapt_create(C.byref(h), device, self.nrx, C.byref(self.params), arr))
+        self._h = h
+
+    def process(self, a, out=None, stream=None):
+        """One batch: a float32 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the views Demod.process
+        and Squelch.process return are fine).  -> float32 [nrx, n] (a view of `out`, a float32 CUDA tensor [nrx,
+        capacity] with contiguous rows, if given).  `out` may be `a` itself (in place); it must not overlap a
+        otherwise."""
+        import torch
+        def rows(t):
+            return t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == self.nrx and (t.shape[1] <= 1 or t.stride(1) == 1)
+        if not rows(a):
+            raise PddcError(-1, "adapt: a must be a float32 tensor [nrx, n] with contiguous rows")
+        n = int(a.shape[1])
+        if out is None:
+            out = torch.empty((self.nrx, n), dtype=torch.float32, device=torch.device("cuda", self.device))
+        elif not rows(out):
+            raise PddcError(-1, "adapt: out must be a float32 tensor [nrx, capacity] with contiguous rows")
+        # the C ABI takes row strides; a capacity below n must reach it as one (PDDC_ECAPACITY) whatever the view's stride
+        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        check(ddc_lib().pddc_adapt_process(self._h, a.data_ptr() if n else None, n, int(a.stride(0)),
+                                           out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
+        return out[:, :n]
+
+    def set_rx(self, rx: int, mode: int, mu: float, leak: float, flags: int = 0):
+        """receiver rx from the next sample on; the weights are kept unless flags has PDDC_ADAPT_RESTART"""
+        check(ddc_lib().pddc_adapt_set_rx(self._h, int(rx), int(mode) & 0xFFFFFFFF, float(mu), float(leak), int(flags) & 0xFFFFFFFF))
+
+    def read_weights(self, stream=None):
+        """-> numpy float32 [nrx, taps]: the weights as the last batch left them (it waits for it)"""
+        import numpy as np
+        w = np.zeros((self.nrx, self.taps), dtype=np.float32)
+        check(ddc_lib().pddc_adapt_read_weights(self._h, w.ctypes.data, self._stream(stream)))
+        return w
 
 
 AUDIO_MAX_RATIO, AUDIO_MAX_DECIM = 1 << 24, 16
