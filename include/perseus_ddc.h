@@ -831,6 +831,84 @@ int pddc_adapt_read_weights(pddc_adapt *s, float *host /* [nrx][taps] */, void *
 /* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_adapt_tile_outputs(void);
 
+/* ---- blanker: impulse noise blanker per receiver ------------------------------
+ * A stage between the tuner and the receiver filter, the only place where an impulse is still a few
+ * samples long.  Per batch it reads the receivers' complex float32 rows z_j[m] (the tuner's output
+ * view, whose stride is its capacity) and gives out_j[m]: the same series delayed by D samples, with
+ * the neighbourhood of every detected impulse taken to zero through a linear ramp.  m counts input
+ * samples since create / reset and goes on across batches; z[m] = 0 for m < 0.  All arithmetic is
+ * float32 with floating-point contraction off, the same operation sequence for every caller and cut.
+ * Fixed at create, common to all receivers: nrx (1 .. 1024); B, samples per metering block
+ * (1 .. 4096); W, the guard half-width (0 .. 128); R, the ramp length (0 .. 128); beta, the
+ * reference's smoothing (finite, 0 < beta <= 1); cap, the reference's largest rise per block (finite,
+ * >= 1).  D = W + R (0 .. 256); invB = 1.0f / (float)B and invR1 = 1.0f / (float)(R + 1), one
+ * correctly rounded division each.
+ * Per receiver, changeable between batches with set_rx: thr, finite and > 0, a power ratio; flags, a
+ * subset of PDDC_NB_ON.
+ * Carried per receiver, with the values at create / reset: the partial sum s = 0, the reference
+ * ref = 0, the counters triggers = 0 and blanked = 0 (uint32, modulo 2^32), the last D inputs and the
+ * trigger bits of the last 2 D inputs (all clear).  The object carries the sample count N (uint64).
+ * Per input sample m, in order:
+ *   1. p = (re re) + (im im); s = s + p.
+ *   2. t[m] = ON && (ref > 0) && (p > ref thr): the product is one float32 multiply, ref the value
+ *      after the last completed block, a comparison with a NaN is false.  On t[m]: ++triggers.
+ *   3. after the sample with (m + 1) mod B == 0: L = s invB; s = 0; if ref > 0: x = fminf(L, ref cap),
+ *      d = x - ref, ref = ref + (beta d); otherwise ref = L.  There are no other special cases: what a
+ *      non-finite input does follows from these operations.
+ * The gate, for every m (m < 0 included): dist[m] is the smallest |m - u| over all u with t[u] set and
+ * |m - u| <= D; g = 0 when dist <= W; g = (float)(dist - W) invR1 when W < dist <= D; g = 1 when no
+ * trigger is that near.
+ * Output n, one per input, at the same index of the batch: c = n - D; with g[c] == 1 out has the bits
+ * of z[c] (+0 + 0i for c < 0); with g[c] == 0 both parts are +0.0f whatever z is; otherwise
+ * out.re = re g and out.im = im g, one multiply each.  ++blanked for every output with g[c] != 1.
+ * A trigger at u touches outputs u .. u + 2 D only, so everything is causal.  The last D inputs of a
+ * stream come out when the caller feeds D more samples: there is no flush call.
+ * set_rx(j, thr, flags): from the next input sample on; nothing carried is reset -- triggers already
+ * taken stay, and receivers that are off go on being metered and delayed.  An unknown flag, a thr that
+ * is not finite or <= 0, j outside [0, nrx): PDDC_EINVAL, nothing changed.
+ * The bits of every output, of ref and of the counters depend on the receiver's series, its set_rx
+ * history and the create parameters alone: not on the cut into batches (batches of 0, of fewer than D
+ * and of fewer than B samples included), nrx, j's index, the other receivers, strides, grid or tile
+ * sizes.
+ * process(): z is [nrx][z_stride] and out [nrx][out_stride] complex float32, n values used per row.
+ * Every argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned (8 bytes)
+ * pointer with work to do, PDDC_ECAPACITY when a stride is below n; ANY overlap of out with z is
+ * PDDC_EINVAL -- there is no in-place form, out[n] is made from z[n - D]; n = 0 is valid and does
+ * nothing.  State moves only after the launch was accepted.  Stream-ordered; one stream per object,
+ * one thread at a time.
+ * read(): ref and the counters of every receiver after the batches submitted so far (it waits for
+ * them).
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_NB_ON 0x1u
+typedef struct pddc_blanker_params {
+    int block;            /* B: samples per metering block                */
+    int guard;            /* W: samples zeroed on either side of a trigger */
+    int ramp;             /* R: samples of the ramp on either side        */
+    float beta;           /* the reference's smoothing per block          */
+    float cap;            /* the reference's largest rise per block       */
+} pddc_blanker_params;
+typedef struct pddc_blanker_rx {
+    float thr;            /* trigger at p > ref thr                       */
+    uint32_t flags;       /* PDDC_NB_ON                                   */
+} pddc_blanker_rx;
+typedef struct pddc_blanker_status {
+    float ref;
+    uint32_t triggers, blanked;
+} pddc_blanker_status;
+typedef struct pddc_blanker pddc_blanker;
+int pddc_blanker_create(pddc_blanker **out, int device, int nrx, const pddc_blanker_params *params,
+                        const pddc_blanker_rx *rx /* [nrx], copied */);
+int pddc_blanker_destroy(pddc_blanker *b);
+int pddc_blanker_reset(pddc_blanker *b);              /* N and everything carried; synchronises the device */
+int pddc_blanker_set_rx(pddc_blanker *b, int rx, float thr, uint32_t flags);
+int pddc_blanker_process(pddc_blanker *b, const void *d_z, size_t n, size_t z_stride, void *d_out, size_t out_stride,
+                         void *stream);
+int pddc_blanker_read(pddc_blanker *b, pddc_blanker_status *host /* [nrx] */, void *stream);
+/* D = W + R: output n is input n - D */
+int pddc_blanker_delay(const pddc_blanker *b);
+/* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
+int pddc_blanker_tile_outputs(void);
+
 /* ---- audio: the receivers' audio at a standard rate, float32 or int16 PCM -----
  * nrx receivers, each a real float32 series x_j[i] such as the demodulator writes, give nrx real
  * series y_j[k] at L/M times the input rate: 9765.625 Hz -> 48 kHz is 3072/625.  i and k count since

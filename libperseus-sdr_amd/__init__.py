@@ -90,6 +90,16 @@ class AdaptRx(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("mu", C.c_float), ("leak", C.c_float), ("flags", C.c_uint32)]
 
 
+class BlankerParams(C.Structure):
+    """pddc_blanker_params (include/perseus_ddc.h)"""
+    _fields_ = [("block", C.c_int), ("guard", C.c_int), ("ramp", C.c_int), ("beta", C.c_float), ("cap", C.c_float)]
+
+
+class BlankerRx(C.Structure):
+    """pddc_blanker_rx (include/perseus_ddc.h)"""
+    _fields_ = [("thr", C.c_float), ("flags", C.c_uint32)]
+
+
 _ddc = None
 
 
@@ -295,6 +305,17 @@ def ddc_lib() -> C.CDLL:
     L.pddc_adapt_tile_outputs.argtypes = []
     for name in ("pddc_adapt_create", "pddc_adapt_destroy", "pddc_adapt_reset", "pddc_adapt_set_rx", "pddc_adapt_process",
                  "pddc_adapt_read_weights", "pddc_adapt_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_blanker_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(BlankerParams), C.POINTER(BlankerRx)]
+    L.pddc_blanker_destroy.argtypes = [vp]
+    L.pddc_blanker_reset.argtypes = [vp]
+    L.pddc_blanker_set_rx.argtypes = [vp, C.c_int, C.c_float, C.c_uint32]
+    L.pddc_blanker_process.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    L.pddc_blanker_read.argtypes = [vp, vp, vp]
+    L.pddc_blanker_delay.argtypes = [vp]
+    L.pddc_blanker_tile_outputs.argtypes = []
+    for name in ("pddc_blanker_create", "pddc_blanker_destroy", "pddc_blanker_reset", "pddc_blanker_set_rx",
+                 "pddc_blanker_process", "pddc_blanker_read", "pddc_blanker_delay", "pddc_blanker_tile_outputs"):
         getattr(L, name).restype = C.c_int
     L.pddc_audio_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
                                     C.POINTER(C.c_float), C.c_float]
@@ -815,7 +836,7 @@ def _packed_arg(kind, packed, nsamples):
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, RxFilter, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1414,6 +1435,78 @@ class Adapt(_StreamObject):
         w = np.zeros((self.nrx, self.taps), dtype=np.float32)
         check(ddc_lib().pddc_adapt_read_weights(self._h, w.ctypes.data, self._stream(stream)))
         return w
+
+
+PDDC_NB_ON = 0x1
+
+
+def blanker_tile_outputs() -> int:
+    """pddc_blanker_tile_outputs: samples per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_blanker_tile_outputs())
+
+
+def blanker_status_dtype():
+    """pddc_blanker_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("ref", np.float32), ("triggers", np.uint32), ("blanked", np.uint32)])
+
+
+class Blanker(_StreamObject):
+    """pddc_blanker: an impulse noise blanker per receiver, on the device (include/perseus_ddc.h).  It goes between Tuner
+    and RxFilter, where an impulse is still a few samples long: the mean power of every `block` samples moves a
+    reference (smoothing `beta`, at most the factor `cap` up per block); a sample whose power exceeds the reference times
+    the receiver's threshold is a trigger; the output is the input delayed by `delay` = guard + ramp samples, zero
+    within `guard` samples of a trigger and brought back through a linear ramp of `ramp` samples on either side.  rx: one
+    (thr, flags) per receiver, flags PDDC_NB_ON (without it the receiver is delayed and metered only).  Feed it every
+    batch in order on one stream; all outputs are bit-identical however the series is cut.  The last `delay` inputs
+    of a stream come out when `delay` more samples are fed."""
+    _kind = "blanker"
+
+    def __init__(self, rx, block: int, guard: int, ramp: int, beta: float = 0.25, cap: float = 2.0, device: int = 0):
+        rx = [tuple(r) for r in rx]
+        self.nrx, self.device = len(rx), device
+        arr = (BlankerRx * max(self.nrx, 1))()
+        for j, (thr, flags) in enumerate(rx):
+            arr[j] = BlankerRx(float(thr), int(flags) & 0xFFFFFFFF)
+        clip = lambda v: max(-1, min(int(v), 1 << 30))
+        self.block, self.guard, self.ramp, self.beta, self.cap = int(block), int(guard), int(ramp), float(beta), float(cap)
+        self.params = BlankerParams(clip(block), clip(guard), clip(ramp), beta, cap)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_blanker_create(C.byref(h), device, self.nrx, C.byref(self.params), arr))
+        self._h = h
+        self.delay = int(ddc_lib().pddc_blanker_delay(h))
+
+    def process(self, z, out=None, stream=None):
+        """One batch: z a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the view
+        Tuner.process returns is fine).  -> complex64 [nrx, n] (a view of `out`, a complex64 CUDA tensor [nrx, capacity]
+        with contiguous rows, if given): output i is input i - delay of the stream.  `out` must not overlap z."""
+        import torch
+        def rows(t):
+            return t.dtype == torch.complex64 and t.dim() == 2 and t.shape[0] == self.nrx and (t.shape[1] <= 1 or t.stride(1) == 1)
+        if not rows(z):
+            raise PddcError(-1, "blanker: z must be a complex64 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        if out is None:
+            out = torch.empty((self.nrx, n), dtype=torch.complex64, device=torch.device("cuda", self.device))
+        elif not rows(out):
+            raise PddcError(-1, "blanker: out must be a complex64 tensor [nrx, capacity] with contiguous rows")
+        # the C ABI takes row strides; a capacity below n must reach it as one (PDDC_ECAPACITY) whatever the view's stride
+        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        check(ddc_lib().pddc_blanker_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                             out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
+        return out[:, :n]
+
+    def set_rx(self, rx: int, thr: float, flags: int = 0):
+        """receiver rx from the next input sample on; nothing carried is reset"""
+        check(ddc_lib().pddc_blanker_set_rx(self._h, int(rx), float(thr), int(flags) & 0xFFFFFFFF))
+
+    def read(self, stream=None):
+        """-> numpy structured array [nrx] (ref, triggers, blanked) after the batches submitted so far (it waits for
+        them)"""
+        import numpy as np
+        st = np.zeros(self.nrx, dtype=blanker_status_dtype())
+        check(ddc_lib().pddc_blanker_read(self._h, st.ctypes.data, self._stream(stream)))
+        return st
 
 
 AUDIO_MAX_RATIO, AUDIO_MAX_DECIM = 1 << 24, 16
