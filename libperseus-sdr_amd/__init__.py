@@ -835,6 +835,11 @@ def _packed_arg(kind, packed, nsamples):
     return int(packed), nsamples
 
 
+def _clip(v) -> int:
+    """an integer parameter as a C int: out of range stays out of range"""
+    return max(-1, min(int(v), 1 << 30))
+
+
 class _StreamObject:
     """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
@@ -842,6 +847,21 @@ class _StreamObject:
     def _stream(self, stream):
         import torch
         return stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+
+    def _rows(self, t, dtype) -> bool:
+        """t is what the per-receiver stages read and write: a `dtype` tensor [nrx, any] whose rows are contiguous"""
+        return t.dtype == dtype and t.dim() == 2 and t.shape[0] == self.nrx and (t.shape[1] <= 1 or t.stride(1) == 1)
+
+    def _out(self, out, count: int, dtype, what: str):
+        """An output of `count` items per receiver: `out` if given (refused as "<kind>: <what> tensor [nrx, capacity] ..."
+        unless it is such rows), a new tensor otherwise.  -> (out, the capacity for the C ABI).  The ABI takes row
+        strides; a capacity below `count` must reach it as one (PDDC_ECAPACITY) whatever the view's stride."""
+        if out is None:
+            import torch
+            out = torch.empty((self.nrx, count), dtype=dtype, device=torch.device("cuda", self.device))
+        elif not self._rows(out, dtype):
+            raise PddcError(-1, f"{self._kind}: {what} tensor [nrx, capacity] with contiguous rows")
+        return out, int(out.stride(0)) if out.shape[1] >= count else int(out.shape[1])
 
     def reset(self):
         check(getattr(ddc_lib(), f"pddc_{self._kind}_reset")(self._h))
@@ -1179,15 +1199,10 @@ class RxFilter(_StreamObject):
         returns is fine).  -> complex64 [nrx, n] (a view of `out`, a complex64 CUDA tensor [nrx, capacity] with contiguous
         rows, if given).  `out` must not overlap z."""
         import torch
-        if z.dtype != torch.complex64 or z.dim() != 2 or z.shape[0] != self.nrx or (z.shape[1] > 1 and z.stride(1) != 1):
+        if not self._rows(z, torch.complex64):
             raise PddcError(-1, "rxfilter: z must be a complex64 tensor [nrx, n] with contiguous rows")
         n = int(z.shape[1])
-        if out is None:
-            out = torch.empty((self.nrx, n), dtype=torch.complex64, device=torch.device("cuda", self.device))
-        elif out.dtype != torch.complex64 or out.dim() != 2 or out.shape[0] != self.nrx or (out.shape[1] > 1 and out.stride(1) != 1):
-            raise PddcError(-1, "rxfilter: out must be a complex64 tensor [nrx, capacity] with contiguous rows")
-        # the C ABI takes row strides; a capacity below n must reach it as one (PDDC_ECAPACITY) whatever the view's stride
-        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        out, cap = self._out(out, n, torch.complex64, "out must be a complex64")
         check(ddc_lib().pddc_rxfilter_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
                                               out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
         return out[:, :n]
@@ -1246,15 +1261,10 @@ class Demod(_StreamObject):
         returns is fine).  -> float32 [nrx, n] (a view of `out`, a float32 CUDA tensor [nrx, capacity] with contiguous
         rows, if given)."""
         import torch
-        if z.dtype != torch.complex64 or z.dim() != 2 or z.shape[0] != self.nrx or (z.shape[1] > 1 and z.stride(1) != 1):
+        if not self._rows(z, torch.complex64):
             raise PddcError(-1, "demod: z must be a complex64 tensor [nrx, n] with contiguous rows")
         n = int(z.shape[1])
-        if out is None:
-            out = torch.empty((self.nrx, n), dtype=torch.float32, device=torch.device("cuda", self.device))
-        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != self.nrx or (out.shape[1] > 1 and out.stride(1) != 1):
-            raise PddcError(-1, "demod: out must be a float32 tensor [nrx, capacity] with contiguous rows")
-        # the C ABI takes row strides; a capacity below n must reach it as one (PDDC_ECAPACITY) whatever the view's stride
-        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        out, cap = self._out(out, n, torch.float32, "out must be a float32")
         check(ddc_lib().pddc_demod_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
                                            out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
         return out[:, :n]
@@ -1304,9 +1314,8 @@ class Squelch(_StreamObject):
         arr = (SquelchRx * max(self.nrx, 1))()
         for j, (open_thr, close_thr, flags) in enumerate(rx):
             arr[j] = SquelchRx(float(open_thr), float(close_thr), int(flags) & 0xFFFFFFFF)
-        clip = lambda v: max(-1, min(int(v), 1 << 30))
         self.block, self.attack, self.hang, self.ramp, self.up = int(block), int(attack), int(hang), int(ramp), float(up)
-        self.params = SquelchParams(clip(block), clip(attack), clip(hang), clip(ramp), up)
+        self.params = SquelchParams(_clip(block), _clip(attack), _clip(hang), _clip(ramp), up)
         h = C.c_void_p()
         check(ddc_lib().pddc_squelch_create(C.byref(h), device, self.nrx, C.byref(self.params), arr))
         self._h = h
@@ -1324,32 +1333,24 @@ class Squelch(_StreamObject):
         rows, if given; levels and states must then have the same row stride.  `out` may be `a` itself (gating in place);
         it must not overlap z or a otherwise."""
         import torch
-        def rows(t, dt):
-            return t.dtype == dt and t.dim() == 2 and t.shape[0] == self.nrx and (t.shape[1] <= 1 or t.stride(1) == 1)
-        if not rows(z, torch.complex64) or not rows(a, torch.float32) or a.shape[1] != z.shape[1]:
+        if not self._rows(z, torch.complex64) or not self._rows(a, torch.float32) or a.shape[1] != z.shape[1]:
             raise PddcError(-1, "squelch: z must be a complex64 and a a float32 tensor [nrx, n] with contiguous rows")
         n = int(z.shape[1])
         due = self.next_blocks(n)
+        out, cap = self._out(out, n, torch.float32, "out must be a float32")
+        # one row stride for both: one that is not given gets the other's
+        both = "levels must be a float32 and states a uint8"
         dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty((self.nrx, n), dtype=torch.float32, device=dev)
-        elif not rows(out, torch.float32):
-            raise PddcError(-1, "squelch: out must be a float32 tensor [nrx, capacity] with contiguous rows")
-        if levels is None and states is None:
-            # one row stride for both
-            levels = torch.empty((self.nrx, due), dtype=torch.float32, device=dev)
-            states = torch.empty((self.nrx, due), dtype=torch.uint8, device=dev)
-        elif levels is None:
+        if levels is None and states is not None:
             levels = torch.empty((self.nrx, int(states.stride(0))), dtype=torch.float32, device=dev)
-        elif states is None:
+        elif states is None and levels is not None:
             states = torch.empty((self.nrx, int(levels.stride(0))), dtype=torch.uint8, device=dev)
-        if not rows(levels, torch.float32) or not rows(states, torch.uint8):
-            raise PddcError(-1, "squelch: levels must be a float32 and states a uint8 tensor [nrx, capacity] with contiguous rows")
+        levels, lcap = self._out(levels, due, torch.float32, both)
+        states, _ = self._out(states, due, torch.uint8, both)
         if due and self.nrx > 1 and levels.stride(0) != states.stride(0):
             raise PddcError(-1, "squelch: levels and states must have the same row stride")
-        # the C ABI takes row strides; a capacity below the count must reach it as one (PDDC_ECAPACITY) whatever the view's stride
-        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
-        bcap = int(levels.stride(0)) if min(levels.shape[1], states.shape[1]) >= due else int(min(levels.shape[1], states.shape[1]))
+        # the shorter of the two is the capacity when one is too short, levels' stride otherwise
+        bcap = lcap if states.shape[1] >= due else min(int(levels.shape[1]), int(states.shape[1]))
         c = C.c_size_t()
         check(ddc_lib().pddc_squelch_process(self._h, z.data_ptr() if n else None, a.data_ptr() if n else None, n,
                                              int(z.stride(0)), int(a.stride(0)), out.data_ptr() if out.numel() else None, cap,
@@ -1397,9 +1398,8 @@ class Adapt(_StreamObject):
         for j, r in enumerate(rx):
             mode, mu, leak = r[:3]
             arr[j] = AdaptRx(int(mode) & 0xFFFFFFFF, float(mu), float(leak), (int(r[3]) if len(r) > 3 else 0) & 0xFFFFFFFF)
-        clip = lambda v: max(-1, min(int(v), 1 << 30))
         self.taps, self.delay, self.eps = int(taps), int(delay), float(eps)
-        self.params = AdaptParams(clip(taps), clip(delay), eps)
+        self.params = AdaptParams(_clip(taps), _clip(delay), eps)
         h = C.c_void_p()
         check(ddc_lib().pddc_adapt_create(C.byref(h), device, self.nrx, C.byref(self.params), arr))
         self._h = h
@@ -1410,17 +1410,10 @@ class Adapt(_StreamObject):
         capacity] with contiguous rows, if given).  `out` may be `a` itself (in place); it must not overlap a
         otherwise."""
         import torch
-        def rows(t):
-            return t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == self.nrx and (t.shape[1] <= 1 or t.stride(1) == 1)
-        if not rows(a):
+        if not self._rows(a, torch.float32):
             raise PddcError(-1, "adapt: a must be a float32 tensor [nrx, n] with contiguous rows")
         n = int(a.shape[1])
-        if out is None:
-            out = torch.empty((self.nrx, n), dtype=torch.float32, device=torch.device("cuda", self.device))
-        elif not rows(out):
-            raise PddcError(-1, "adapt: out must be a float32 tensor [nrx, capacity] with contiguous rows")
-        # the C ABI takes row strides; a capacity below n must reach it as one (PDDC_ECAPACITY) whatever the view's stride
-        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        out, cap = self._out(out, n, torch.float32, "out must be a float32")
         check(ddc_lib().pddc_adapt_process(self._h, a.data_ptr() if n else None, n, int(a.stride(0)),
                                            out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
         return out[:, :n]
@@ -1468,9 +1461,8 @@ class Blanker(_StreamObject):
         arr = (BlankerRx * max(self.nrx, 1))()
         for j, (thr, flags) in enumerate(rx):
             arr[j] = BlankerRx(float(thr), int(flags) & 0xFFFFFFFF)
-        clip = lambda v: max(-1, min(int(v), 1 << 30))
         self.block, self.guard, self.ramp, self.beta, self.cap = int(block), int(guard), int(ramp), float(beta), float(cap)
-        self.params = BlankerParams(clip(block), clip(guard), clip(ramp), beta, cap)
+        self.params = BlankerParams(_clip(block), _clip(guard), _clip(ramp), beta, cap)
         h = C.c_void_p()
         check(ddc_lib().pddc_blanker_create(C.byref(h), device, self.nrx, C.byref(self.params), arr))
         self._h = h
@@ -1481,17 +1473,10 @@ class Blanker(_StreamObject):
         Tuner.process returns is fine).  -> complex64 [nrx, n] (a view of `out`, a complex64 CUDA tensor [nrx, capacity]
         with contiguous rows, if given): output i is input i - delay of the stream.  `out` must not overlap z."""
         import torch
-        def rows(t):
-            return t.dtype == torch.complex64 and t.dim() == 2 and t.shape[0] == self.nrx and (t.shape[1] <= 1 or t.stride(1) == 1)
-        if not rows(z):
+        if not self._rows(z, torch.complex64):
             raise PddcError(-1, "blanker: z must be a complex64 tensor [nrx, n] with contiguous rows")
         n = int(z.shape[1])
-        if out is None:
-            out = torch.empty((self.nrx, n), dtype=torch.complex64, device=torch.device("cuda", self.device))
-        elif not rows(out):
-            raise PddcError(-1, "blanker: out must be a complex64 tensor [nrx, capacity] with contiguous rows")
-        # the C ABI takes row strides; a capacity below n must reach it as one (PDDC_ECAPACITY) whatever the view's stride
-        cap = int(out.stride(0)) if out.shape[1] >= n else int(out.shape[1])
+        out, cap = self._out(out, n, torch.complex64, "out must be a complex64")
         check(ddc_lib().pddc_blanker_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
                                              out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
         return out[:, :n]
@@ -1586,26 +1571,19 @@ class Audio(_StreamObject):
         returns is fine).  -> float32 [nrx, count] if f32, int16 [nrx, count] if i16, both as a tuple if both (views of
         `out_f32` / `out_i16`, CUDA tensors [nrx, capacity] with contiguous rows, if given; giving one asks for it)."""
         import torch
-        if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.nrx or (x.shape[1] > 1 and x.stride(1) != 1):
+        if not self._rows(x, torch.float32):
             raise PddcError(-1, "audio: x must be a float32 tensor [nrx, n] with contiguous rows")
         f32, i16 = f32 or out_f32 is not None, i16 or out_i16 is not None
         if not (f32 or i16):
             raise PddcError(-1, "audio: ask for float32, int16 or both")
         n = int(x.shape[1])
         due = self.next_outputs(n)
-        outs = []
-        for want, out, dt, name in ((f32, out_f32, torch.float32, "out_f32"), (i16, out_i16, torch.int16, "out_i16")):
-            if not want:
-                outs.append(None)
-                continue
-            if out is None:
-                out = torch.empty((self.nrx, due), dtype=dt, device=torch.device("cuda", self.device))
-            elif out.dtype != dt or out.dim() != 2 or out.shape[0] != self.nrx or (out.shape[1] > 1 and out.stride(1) != 1):
-                raise PddcError(-1, f"audio: {name} must be a {dt} tensor [nrx, capacity] with contiguous rows")
-            outs.append(out)
-        # the C ABI takes row strides; a capacity below the count must reach it as one (PDDC_ECAPACITY) whatever the view's stride
+        outs, cap = [None, None], [0, 0]
+        for i, (want, out, dt, what) in enumerate(((f32, out_f32, torch.float32, "out_f32 must be a torch.float32"),
+                                                   (i16, out_i16, torch.int16, "out_i16 must be a torch.int16"))):
+            if want:
+                outs[i], cap[i] = self._out(out, due, dt, what)
         ptr = [o.data_ptr() if o is not None and o.numel() else None for o in outs]
-        cap = [0 if o is None else int(o.stride(0)) if o.shape[1] >= due else int(o.shape[1]) for o in outs]
         c = C.c_size_t()
         check(ddc_lib().pddc_audio_process(self._h, x.data_ptr() if n else None, n, int(x.stride(0)), ptr[0], cap[0], ptr[1],
                                            cap[1], C.byref(c), self._stream(stream)))

@@ -5,27 +5,23 @@
  * the input counter N, the next output's input n and remainder r, and the "fresh" mark (create, reset: the record is not
  * read, its values are zero) live here.  The prototype is uploaded once, at create.
  */
-#include "ddc_host.h"
+#include "ddc_stage.h"
 #include "ddc_audio.h"
 
 #include <cmath>
-#include <new>
 #include <numeric>
-#include <vector>
 
 using namespace pddc;
 
 typedef unsigned __int128 u128;
 
-struct pddc_audio {
-    int device = 0;
-    int nrx = 0;
+struct pddc_audio : StageBase {
+    PDDC_LOCAL ~pddc_audio() = default;
     uint32_t L = 1, M = 1;                          /* reduced                                                    */
     int phases = 0, taps = 0;
     float scale = 32767.0f;
-    float *d_proto = nullptr;                       /* g[0 .. P T], g[P T] = 0                                    */
-    float *d_state[2] = { nullptr, nullptr };       /* [nrx][T - 1]; process() reads [cur] and writes [cur ^ 1]   */
-    int cur = 0;
+    DevBuf<float> proto;                            /* g[0 .. P T], g[P T] = 0                                    */
+    Carried<float> state;                           /* [nrx][T - 1]                                               */
     bool fresh = true;
     uint64_t N = 0;                                 /* inputs per receiver since create / reset                   */
     uint64_t n = 0;                                 /* the next output's input, n >= N, and                       */
@@ -53,27 +49,6 @@ static u128 audio_due(const pddc_audio *a, size_t n)
     return (avail * a->L - a->r + (a->M - 1)) / a->M;
 }
 
-static void audio_free(pddc_audio *a)
-{
-    hipFree(a->d_proto);
-    hipFree(a->d_state[0]);
-    hipFree(a->d_state[1]);
-    delete a;
-}
-
-static int audio_alloc(pddc_audio *a, const std::vector<float> &g)
-{
-    PDDC_HIP_TRY(hipSetDevice(a->device));
-    const size_t bytes = sizeof(float) * (size_t)a->nrx * (size_t)(a->taps > 1 ? a->taps - 1 : 1);
-    PDDC_HIP_TRY(hipMalloc(&a->d_proto, sizeof(float) * g.size()));
-    PDDC_HIP_TRY(hipMalloc(&a->d_state[0], bytes));
-    PDDC_HIP_TRY(hipMalloc(&a->d_state[1], bytes));
-    PDDC_HIP_TRY(hipMemcpy(a->d_proto, g.data(), sizeof(float) * g.size(), hipMemcpyHostToDevice));
-    PDDC_HIP_TRY(hipMemset(a->d_state[0], 0, bytes));
-    PDDC_HIP_TRY(hipMemset(a->d_state[1], 0, bytes));
-    return PDDC_OK;
-}
-
 extern "C" {
 
 uint64_t pddc_audio_outputs(uint32_t L, uint32_t M, uint64_t inputs_before, size_t n)
@@ -88,7 +63,7 @@ int pddc_audio_create(pddc_audio **out, int device, int nrx, uint32_t L, uint32_
                       float scale)
 {
     if (!out)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
+        return null_argument();
     *out = nullptr;
     if (nrx < 1 || nrx > kAudioMaxRx)
         return pddc_set_error_(PDDC_EINVAL, "audio: %d receivers (1 .. %d)", nrx, kAudioMaxRx);
@@ -106,46 +81,25 @@ int pddc_audio_create(pddc_audio **out, int device, int nrx, uint32_t L, uint32_
     /* written so that a NaN fails it */
     if (!(scale > 0.0f && scale <= 3.0e38f))
         return pddc_set_error_(PDDC_EINVAL, "audio: scale %g (finite, > 0)", (double)scale);
-    if (const int rc = pddc_check_device_(device))
-        return rc;
-    pddc_audio *a = new (std::nothrow) pddc_audio;
-    if (!a)
-        return pddc_set_error_(PDDC_ENOMEM, "out of memory");
     const uint32_t d = std::gcd(L, M);
-    a->device = device;
-    a->nrx = nrx;
-    a->L = L / d;
-    a->M = M / d;
-    a->phases = phases;
-    a->taps = taps;
-    a->scale = scale;
     std::vector<float> g(proto, proto + (size_t)phases * (size_t)taps);
     g.push_back(0.0f);
-    const int rc = audio_alloc(a, g);
-    if (rc) {
-        audio_free(a);
-        return rc;
-    }
-    *out = a;
-    return PDDC_OK;
+    return stage_create(out, device, nrx, [&](pddc_audio &a) {
+        a.L = L / d;
+        a.M = M / d;
+        a.phases = phases;
+        a.taps = taps;
+        a.scale = scale;
+        PDDC_TRY(a.proto.alloc_copy(g));
+        return a.state.alloc((size_t)nrx * (size_t)(taps > 1 ? taps - 1 : 1));
+    });
 }
 
-int pddc_audio_destroy(pddc_audio *a)
-{
-    if (!a)
-        return PDDC_OK;
-    (void)hipSetDevice(a->device);
-    (void)hipDeviceSynchronize();
-    audio_free(a);
-    return PDDC_OK;
-}
+int pddc_audio_destroy(pddc_audio *a) { return stage_destroy(a); }
 
 int pddc_audio_reset(pddc_audio *a)
 {
-    if (!a)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
-    PDDC_HIP_TRY(hipSetDevice(a->device));
-    PDDC_HIP_TRY(hipDeviceSynchronize());
+    PDDC_TRY(stage_quiesce(a));
     a->N = 0;
     a->n = 0;
     a->r = 0;
@@ -156,7 +110,7 @@ int pddc_audio_reset(pddc_audio *a)
 int pddc_audio_next_outputs(const pddc_audio *a, size_t n, size_t *count)
 {
     if (!a || !count)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
+        return null_argument();
     const u128 c = audio_due(a, n);
     if (c > (u128)(SIZE_MAX >> 1))
         return pddc_set_error_(PDDC_EINVAL, "audio: %zu inputs per receiver are too many for one batch", n);
@@ -168,16 +122,16 @@ int pddc_audio_process(pddc_audio *a, const void *d_x, size_t n, size_t x_stride
                        size_t i16_stride, size_t *count, void *stream)
 {
     if (!a)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
+        return null_argument();
     /* the kernel's 64-bit r + k M: the batch's inputs times L stay below 2^62 */
     if ((u128)n * a->L >> 62)
         return pddc_set_error_(PDDC_EINVAL, "audio: %zu inputs per receiver are too many for one batch", n);
     const size_t c = (size_t)audio_due(a, n);
-    if (n && (!d_x || ((uintptr_t)d_x & 3)))
-        return pddc_set_error_(PDDC_EINVAL, "d_x must be a 4-byte aligned device pointer");
+    if (n)
+        PDDC_TRY(device_ptr_ok(d_x, 4, "d_x"));
     if (c && !d_f32 && !d_i16)
         return pddc_set_error_(PDDC_EINVAL, "audio: one of d_f32 and d_i16 must be given");
-    if (c && (((uintptr_t)d_f32 & 3) || ((uintptr_t)d_i16 & 1)))
+    if (c && !(aligned_or_null(d_f32, 4) && aligned_or_null(d_i16, 2)))
         return pddc_set_error_(PDDC_EINVAL, "d_f32 must be a 4-byte, d_i16 a 2-byte aligned device pointer");
     if (n > x_stride || (d_f32 && c > f32_stride) || (d_i16 && c > i16_stride))
         return pddc_set_error_(PDDC_ECAPACITY, "audio: %zu inputs and %zu outputs per receiver, x_stride %zu, f32_stride %zu, "
@@ -187,7 +141,7 @@ int pddc_audio_process(pddc_audio *a, const void *d_x, size_t n, size_t x_stride
             *count = 0;
         return PDDC_OK;
     }
-    PDDC_HIP_TRY(hipSetDevice(a->device));
+    PDDC_TRY(set_device(a->device));
     AudioArgs k{};
     k.x = static_cast<const float *>(d_x);
     k.x_stride = (long long)x_stride;
@@ -197,9 +151,9 @@ int pddc_audio_process(pddc_audio *a, const void *d_x, size_t n, size_t x_stride
     k.i16_stride = (long long)i16_stride;
     k.n = (long long)n;
     k.count = (long long)c;
-    k.proto = a->d_proto;
-    k.state = a->d_state[a->cur];
-    k.new_state = a->d_state[a->cur ^ 1];
+    k.proto = a->proto.get();
+    k.state = a->state.old();
+    k.new_state = a->state.next();
     k.nrx = a->nrx;
     k.fresh = a->fresh ? 1 : 0;
     k.L = a->L;
@@ -216,7 +170,7 @@ int pddc_audio_process(pddc_audio *a, const void *d_x, size_t n, size_t x_stride
     a->n += (uint64_t)(v / a->L);
     a->r = (uint32_t)(v % a->L);
     a->N += n;
-    a->cur ^= 1;
+    a->state.turn();
     a->fresh = false;
     if (count)
         *count = c;

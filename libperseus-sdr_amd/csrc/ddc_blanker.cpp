@@ -7,30 +7,23 @@
  * records, their values are the create values).  Thresholds and flags live in the table, which is uploaded in stream
  * order when it changed.
  */
-#include "ddc_host.h"
+#include "ddc_stage.h"
 #include "ddc_blanker.h"
 
 #include <cmath>
-#include <new>
-#include <vector>
 
 using namespace pddc;
 
-struct pddc_blanker {
-    int device = 0;
-    int nrx = 0;
+struct pddc_blanker : StageBase {
+    PDDC_LOCAL ~pddc_blanker() = default;
     pddc_blanker_params par{};
     float invB = 0.0f, invR1 = 0.0f;
-    std::vector<BlankerRx> table;                   /* uploaded when `dirty`                                       */
-    std::vector<BlankerRx> staged;                  /* the copy an upload reads: touched by the next upload only   */
+    RxTable<BlankerRx> table;
     std::vector<BlankerState> host_state;           /* where read() lands the records                              */
-    bool dirty = true;
     bool fresh = true;                              /* no launch since create / reset                              */
-    BlankerRx *d_table = nullptr;
-    BlankerState *d_state[2] = { nullptr, nullptr };/* process() reads [cur] and writes [cur ^ 1]                  */
-    float2 *d_hist[2] = { nullptr, nullptr };
-    unsigned long long *d_bits[2] = { nullptr, nullptr };
-    int cur = 0;
+    Carried<BlankerState> state;                    /* [nrx]                                                       */
+    Carried<float2> hist;                           /* [nrx][kBlankerMaxDelay]                                     */
+    Carried<unsigned long long> bits;               /* [nrx][kBlankerCarryWords]                                   */
     uint64_t N = 0;                                 /* samples per receiver since create / reset                   */
 };
 
@@ -43,42 +36,6 @@ static bool blanker_rx_ok(float thr, uint32_t flags)
     return !(flags & ~kBlankerOn) && thr > 0.0f && thr <= 3.4028234e38f;
 }
 
-static void blanker_free(pddc_blanker *b)
-{
-    hipFree(b->d_table);
-    for (int i = 0; i < 2; ++i) {
-        hipFree(b->d_state[i]);
-        hipFree(b->d_hist[i]);
-        hipFree(b->d_bits[i]);
-    }
-    delete b;
-}
-
-static int blanker_alloc(pddc_blanker *b)
-{
-    PDDC_HIP_TRY(hipSetDevice(b->device));
-    const size_t rows = (size_t)b->nrx;
-    const size_t sb = sizeof(BlankerState) * rows, hb = sizeof(float2) * kBlankerMaxDelay * rows,
-                 bb = sizeof(unsigned long long) * kBlankerCarryWords * rows;
-    PDDC_HIP_TRY(hipMalloc(&b->d_table, sizeof(BlankerRx) * rows));
-    for (int i = 0; i < 2; ++i) {
-        PDDC_HIP_TRY(hipMalloc(&b->d_state[i], sb));
-        PDDC_HIP_TRY(hipMalloc(&b->d_hist[i], hb));
-        PDDC_HIP_TRY(hipMalloc(&b->d_bits[i], bb));
-        PDDC_HIP_TRY(hipMemset(b->d_state[i], 0, sb));
-        PDDC_HIP_TRY(hipMemset(b->d_hist[i], 0, hb));
-        PDDC_HIP_TRY(hipMemset(b->d_bits[i], 0, bb));
-    }
-    return PDDC_OK;
-}
-
-/* byte ranges [p, p + bytes) and [q, q + qbytes) share a byte */
-static bool ranges_overlap(const void *p, size_t bytes, const void *q, size_t qbytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qbytes && b < a + bytes;
-}
-
 extern "C" {
 
 int pddc_blanker_tile_outputs(void) { return kBlankerTile; }
@@ -86,7 +43,7 @@ int pddc_blanker_tile_outputs(void) { return kBlankerTile; }
 int pddc_blanker_create(pddc_blanker **out, int device, int nrx, const pddc_blanker_params *par, const pddc_blanker_rx *rx)
 {
     if (!out)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
+        return null_argument();
     *out = nullptr;
     if (nrx < 1 || nrx > kBlankerMaxRx || !rx)
         return pddc_set_error_(PDDC_EINVAL, "blanker: %d receivers (1 .. %d) and their thresholds", nrx, kBlankerMaxRx);
@@ -103,45 +60,25 @@ int pddc_blanker_create(pddc_blanker **out, int device, int nrx, const pddc_blan
         if (!blanker_rx_ok(rx[j].thr, rx[j].flags))
             return pddc_set_error_(PDDC_EINVAL, "blanker: receiver %d: threshold %g (finite, > 0), flags 0x%x", j,
                                    (double)rx[j].thr, rx[j].flags);
-    if (const int rc = pddc_check_device_(device))
-        return rc;
-    pddc_blanker *b = new (std::nothrow) pddc_blanker;
-    if (!b)
-        return pddc_set_error_(PDDC_ENOMEM, "out of memory");
-    b->device = device;
-    b->nrx = nrx;
-    b->par = *par;
-    b->invB = 1.0f / (float)par->block;
-    b->invR1 = 1.0f / (float)(par->ramp + 1);
-    b->table.resize((size_t)nrx);
-    b->host_state.resize((size_t)nrx);
-    for (int j = 0; j < nrx; ++j)
-        b->table[(size_t)j] = BlankerRx{ rx[j].thr, rx[j].flags };
-    const int rc = blanker_alloc(b);
-    if (rc) {
-        blanker_free(b);
-        return rc;
-    }
-    *out = b;
-    return PDDC_OK;
+    return stage_create(out, device, nrx, [&](pddc_blanker &b) {
+        b.par = *par;
+        b.invB = 1.0f / (float)par->block;
+        b.invR1 = 1.0f / (float)(par->ramp + 1);
+        b.host_state.resize((size_t)nrx);
+        for (int j = 0; j < nrx; ++j)
+            b.table.host.push_back(BlankerRx{ rx[j].thr, rx[j].flags });
+        PDDC_TRY(b.table.alloc());
+        PDDC_TRY(b.state.alloc((size_t)nrx));
+        PDDC_TRY(b.hist.alloc((size_t)nrx * kBlankerMaxDelay));
+        return b.bits.alloc((size_t)nrx * kBlankerCarryWords);
+    });
 }
 
-int pddc_blanker_destroy(pddc_blanker *b)
-{
-    if (!b)
-        return PDDC_OK;
-    (void)hipSetDevice(b->device);
-    (void)hipDeviceSynchronize();
-    blanker_free(b);
-    return PDDC_OK;
-}
+int pddc_blanker_destroy(pddc_blanker *b) { return stage_destroy(b); }
 
 int pddc_blanker_reset(pddc_blanker *b)
 {
-    if (!b)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
-    PDDC_HIP_TRY(hipSetDevice(b->device));
-    PDDC_HIP_TRY(hipDeviceSynchronize());
+    PDDC_TRY(stage_quiesce(b));
     b->N = 0;
     b->fresh = true;
     return PDDC_OK;
@@ -149,22 +86,19 @@ int pddc_blanker_reset(pddc_blanker *b)
 
 int pddc_blanker_set_rx(pddc_blanker *b, int rx, float thr, uint32_t flags)
 {
-    if (!b)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
-    if (rx < 0 || rx >= b->nrx)
-        return pddc_set_error_(PDDC_EINVAL, "blanker: receiver %d (0 .. %d)", rx, b->nrx - 1);
+    PDDC_TRY(stage_rx_ok(b, "blanker", rx));
     if (!blanker_rx_ok(thr, flags))
         return pddc_set_error_(PDDC_EINVAL, "blanker: threshold %g (finite, > 0), flags 0x%x", (double)thr, flags);
     /* nothing carried is reset */
-    b->table[(size_t)rx] = BlankerRx{ thr, flags };
-    b->dirty = true;
+    b->table.host[(size_t)rx] = BlankerRx{ thr, flags };
+    b->table.dirty = true;
     return PDDC_OK;
 }
 
 int pddc_blanker_delay(const pddc_blanker *b)
 {
     if (!b)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
+        return null_argument();
     return b->par.guard + b->par.ramp;
 }
 
@@ -172,40 +106,35 @@ int pddc_blanker_process(pddc_blanker *b, const void *d_z, size_t n, size_t z_st
                          void *stream)
 {
     if (!b)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
-    if (n && (!d_z || ((uintptr_t)d_z & 7)))
-        return pddc_set_error_(PDDC_EINVAL, "d_z must be an 8-byte aligned device pointer");
-    if (n && (!d_out || ((uintptr_t)d_out & 7)))
-        return pddc_set_error_(PDDC_EINVAL, "d_out must be an 8-byte aligned device pointer");
-    if (n > z_stride || n > out_stride)
+        return null_argument();
+    if (n) {
+        PDDC_TRY(device_ptr_ok(d_z, 8, "d_z"));
+        PDDC_TRY(device_ptr_ok(d_out, 8, "d_out"));
+    }
+    if (over_capacity(n, z_stride, out_stride))
         return pddc_set_error_(PDDC_ECAPACITY, "blanker: %zu samples per receiver, z_stride %zu, out_stride %zu", n, z_stride,
                                out_stride);
     if (!n)
         return PDDC_OK;
-    const size_t rows = (size_t)b->nrx - 1;
-    if (ranges_overlap(d_out, (rows * out_stride + n) * 8, d_z, (rows * z_stride + n) * 8))
+    if (ranges_overlap(d_out, rows_extent(b->nrx, n, out_stride, 8), d_z, rows_extent(b->nrx, n, z_stride, 8)))
         return pddc_set_error_(PDDC_EINVAL, "blanker: out overlaps z (there is no in-place form: out[n] is made from z[n - D])");
-    PDDC_HIP_TRY(hipSetDevice(b->device));
+    PDDC_TRY(set_device(b->device));
     hipStream_t st = (hipStream_t)stream;
-    if (b->dirty) {
-        b->staged = b->table;
-        PDDC_HIP_TRY(hipMemcpyAsync(b->d_table, b->staged.data(), sizeof(BlankerRx) * (size_t)b->nrx, hipMemcpyHostToDevice, st));
-        b->dirty = false;
-    }
+    PDDC_TRY(b->table.upload(st));
     BlankerArgs a{};
     a.z = static_cast<const float2 *>(d_z);
     a.z_stride = (long long)z_stride;
     a.out = static_cast<float2 *>(d_out);
     a.out_stride = (long long)out_stride;
     a.n = (long long)n;
-    a.rx = b->d_table;
+    a.rx = b->table.dev();
     a.nrx = b->nrx;
-    a.old = b->d_state[b->cur];
-    a.new_state = b->d_state[b->cur ^ 1];
-    a.old_hist = b->d_hist[b->cur];
-    a.new_hist = b->d_hist[b->cur ^ 1];
-    a.old_bits = b->d_bits[b->cur];
-    a.new_bits = b->d_bits[b->cur ^ 1];
+    a.old = b->state.old();
+    a.new_state = b->state.next();
+    a.old_hist = b->hist.old();
+    a.new_hist = b->hist.next();
+    a.old_bits = b->bits.old();
+    a.new_bits = b->bits.next();
     a.B = (uint32_t)b->par.block;
     a.W = (uint32_t)b->par.guard;
     a.D = (uint32_t)(b->par.guard + b->par.ramp);
@@ -218,7 +147,9 @@ int pddc_blanker_process(pddc_blanker *b, const void *d_z, size_t n, size_t z_st
     a.fresh = b->fresh ? 1u : 0u;
     PDDC_HIP_TRY(launch_blanker(a, st));
     /* the launch was accepted: only now do the host-side counters move */
-    b->cur ^= 1;
+    b->state.turn();
+    b->hist.turn();
+    b->bits.turn();
     b->N += n;
     b->fresh = false;
     return PDDC_OK;
@@ -227,13 +158,9 @@ int pddc_blanker_process(pddc_blanker *b, const void *d_z, size_t n, size_t z_st
 int pddc_blanker_read(pddc_blanker *b, pddc_blanker_status *host, void *stream)
 {
     if (!b || !host)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
-    PDDC_HIP_TRY(hipSetDevice(b->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (!b->fresh)
-        PDDC_HIP_TRY(hipMemcpyAsync(b->host_state.data(), b->d_state[b->cur], sizeof(BlankerState) * (size_t)b->nrx,
-                                    hipMemcpyDeviceToHost, st));
-    PDDC_HIP_TRY(hipStreamSynchronize(st));
+        return null_argument();
+    PDDC_TRY(set_device(b->device));
+    PDDC_TRY(read_back(b->host_state.data(), b->fresh ? nullptr : b->state.old(), (size_t)b->nrx, (hipStream_t)stream));
     for (int j = 0; j < b->nrx; ++j) {
         const BlankerState &r = b->host_state[(size_t)j];
         host[j] = b->fresh ? pddc_blanker_status{ 0.0f, 0u, 0u } : pddc_blanker_status{ r.ref, r.triggers, r.blanked };

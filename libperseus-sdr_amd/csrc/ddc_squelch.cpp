@@ -7,30 +7,23 @@
  * next launch takes the carried peak as 0).  Thresholds and flags live in the table, which is uploaded in stream order
  * when it changed.
  */
-#include "ddc_host.h"
+#include "ddc_stage.h"
 #include "ddc_squelch.h"
 
 #include <cmath>
 #include <limits>
-#include <new>
-#include <vector>
 
 using namespace pddc;
 
-struct pddc_squelch {
-    int device = 0;
-    int nrx = 0;
+struct pddc_squelch : StageBase {
+    PDDC_LOCAL ~pddc_squelch() = default;
     pddc_squelch_params par{};
     float invB = 0.0f, invR = 0.0f;
-    std::vector<SquelchRx> table;                   /* uploaded when `dirty`                                       */
-    std::vector<SquelchRx> staged;                  /* the copy an upload reads: touched by the next upload only   */
+    RxTable<SquelchRx> table;
     std::vector<SquelchState> host_state;           /* where read() lands the records                              */
-    bool dirty = true;
     bool fresh = true;                              /* no launch since create / reset                              */
     bool clear_peak = false;                        /* read(clear_peak) since the last launch                      */
-    SquelchRx *d_table = nullptr;
-    SquelchState *d_state[2] = { nullptr, nullptr };/* process() reads [cur] and writes [cur ^ 1]                  */
-    int cur = 0;
+    Carried<SquelchState> state;
     uint64_t N = 0;                                 /* samples per receiver since create / reset                   */
 };
 
@@ -44,35 +37,6 @@ static bool squelch_rx_ok(float open_thr, float close_thr, uint32_t flags)
 
 static bool squelch_block_ok(int B) { return B >= 1 && B <= kSquelchMaxBlock; }
 
-static uint64_t squelch_blocks(uint64_t B, uint64_t before, uint64_t n) { return (before + n) / B - before / B; }
-
-static void squelch_free(pddc_squelch *s)
-{
-    hipFree(s->d_table);
-    hipFree(s->d_state[0]);
-    hipFree(s->d_state[1]);
-    delete s;
-}
-
-static int squelch_alloc(pddc_squelch *s)
-{
-    PDDC_HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = sizeof(SquelchState) * (size_t)s->nrx;
-    PDDC_HIP_TRY(hipMalloc(&s->d_table, sizeof(SquelchRx) * (size_t)s->nrx));
-    PDDC_HIP_TRY(hipMalloc(&s->d_state[0], bytes));
-    PDDC_HIP_TRY(hipMalloc(&s->d_state[1], bytes));
-    PDDC_HIP_TRY(hipMemset(s->d_state[0], 0, bytes));
-    PDDC_HIP_TRY(hipMemset(s->d_state[1], 0, bytes));
-    return PDDC_OK;
-}
-
-/* byte ranges [p, p + bytes) and [q, q + qbytes) share a byte */
-static bool ranges_overlap(const void *p, size_t bytes, const void *q, size_t qbytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qbytes && b < a + bytes;
-}
-
 extern "C" {
 
 int pddc_squelch_tile_outputs(void) { return kSquelchTile; }
@@ -85,7 +49,7 @@ uint64_t pddc_squelch_blocks(int block, uint64_t samples_before, size_t n)
 int pddc_squelch_create(pddc_squelch **out, int device, int nrx, const pddc_squelch_params *par, const pddc_squelch_rx *rx)
 {
     if (!out)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
+        return null_argument();
     *out = nullptr;
     if (nrx < 1 || nrx > kSquelchMaxRx || !rx)
         return pddc_set_error_(PDDC_EINVAL, "squelch: %d receivers (1 .. %d) and their thresholds", nrx, kSquelchMaxRx);
@@ -101,77 +65,52 @@ int pddc_squelch_create(pddc_squelch **out, int device, int nrx, const pddc_sque
         if (!squelch_rx_ok(rx[j].open_thr, rx[j].close_thr, rx[j].flags))
             return pddc_set_error_(PDDC_EINVAL, "squelch: receiver %d: thresholds %g, %g (finite, 0 <= close <= open), flags 0x%x",
                                    j, (double)rx[j].open_thr, (double)rx[j].close_thr, rx[j].flags);
-    if (const int rc = pddc_check_device_(device))
-        return rc;
-    pddc_squelch *s = new (std::nothrow) pddc_squelch;
-    if (!s)
-        return pddc_set_error_(PDDC_ENOMEM, "out of memory");
-    s->device = device;
-    s->nrx = nrx;
-    s->par = *par;
-    s->invB = 1.0f / (float)par->block;
-    s->invR = 1.0f / (float)par->ramp;
-    s->table.resize((size_t)nrx);
-    s->host_state.resize((size_t)nrx);
-    for (int j = 0; j < nrx; ++j)
-        s->table[(size_t)j] = SquelchRx{ rx[j].open_thr, rx[j].close_thr, rx[j].flags,
-                                         (rx[j].flags & kSquelchGate) ? 0u : (uint32_t)par->ramp };
-    const int rc = squelch_alloc(s);
-    if (rc) {
-        squelch_free(s);
-        return rc;
-    }
-    *out = s;
-    return PDDC_OK;
+    return stage_create(out, device, nrx, [&](pddc_squelch &s) {
+        s.par = *par;
+        s.invB = 1.0f / (float)par->block;
+        s.invR = 1.0f / (float)par->ramp;
+        s.host_state.resize((size_t)nrx);
+        for (int j = 0; j < nrx; ++j)
+            s.table.host.push_back(SquelchRx{ rx[j].open_thr, rx[j].close_thr, rx[j].flags,
+                                              (rx[j].flags & kSquelchGate) ? 0u : (uint32_t)par->ramp });
+        PDDC_TRY(s.table.alloc());
+        return s.state.alloc((size_t)nrx);
+    });
 }
 
-int pddc_squelch_destroy(pddc_squelch *s)
-{
-    if (!s)
-        return PDDC_OK;
-    (void)hipSetDevice(s->device);
-    (void)hipDeviceSynchronize();
-    squelch_free(s);
-    return PDDC_OK;
-}
+int pddc_squelch_destroy(pddc_squelch *s) { return stage_destroy(s); }
 
 int pddc_squelch_reset(pddc_squelch *s)
 {
-    if (!s)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
-    PDDC_HIP_TRY(hipSetDevice(s->device));
-    PDDC_HIP_TRY(hipDeviceSynchronize());
+    PDDC_TRY(stage_quiesce(s));
     s->N = 0;
     s->fresh = true;
     s->clear_peak = false;
-    for (SquelchRx &r : s->table)
+    for (SquelchRx &r : s->table.host)
         r.c0 = (r.flags & kSquelchGate) ? 0u : (uint32_t)s->par.ramp;
-    s->dirty = true;
+    s->table.dirty = true;
     return PDDC_OK;
 }
 
 int pddc_squelch_set_rx(pddc_squelch *s, int rx, float open_thr, float close_thr, uint32_t flags)
 {
-    if (!s)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
-    if (rx < 0 || rx >= s->nrx)
-        return pddc_set_error_(PDDC_EINVAL, "squelch: receiver %d (0 .. %d)", rx, s->nrx - 1);
+    PDDC_TRY(stage_rx_ok(s, "squelch", rx));
     if (!squelch_rx_ok(open_thr, close_thr, flags))
         return pddc_set_error_(PDDC_EINVAL, "squelch: thresholds %g, %g (finite, 0 <= close <= open), flags 0x%x",
                                (double)open_thr, (double)close_thr, flags);
-    SquelchRx &r = s->table[(size_t)rx];
+    SquelchRx &r = s->table.host[(size_t)rx];
     /* nothing carried is reset: c0 is what create / reset made it */
     r.open_thr = open_thr;
     r.close_thr = close_thr;
     r.flags = flags;
-    s->dirty = true;
+    s->table.dirty = true;
     return PDDC_OK;
 }
 
 int pddc_squelch_next_blocks(const pddc_squelch *s, size_t n, size_t *count)
 {
     if (!s || !count)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
+        return null_argument();
     *count = (size_t)squelch_blocks((uint64_t)s->par.block, s->N, (uint64_t)n);
     return PDDC_OK;
 }
@@ -181,24 +120,23 @@ int pddc_squelch_process(pddc_squelch *s, const void *d_z, const void *d_a, size
                          void *stream)
 {
     if (!s)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
+        return null_argument();
     const size_t nblk = (size_t)squelch_blocks((uint64_t)s->par.block, s->N, (uint64_t)n);
-    if (n && (!d_z || ((uintptr_t)d_z & 7)))
-        return pddc_set_error_(PDDC_EINVAL, "d_z must be an 8-byte aligned device pointer");
-    if (n && (!d_a || ((uintptr_t)d_a & 3)))
-        return pddc_set_error_(PDDC_EINVAL, "d_a must be a 4-byte aligned device pointer");
-    if (n && (!d_out || ((uintptr_t)d_out & 3)))
-        return pddc_set_error_(PDDC_EINVAL, "d_out must be a 4-byte aligned device pointer");
-    if (nblk && ((uintptr_t)d_level & 3))
-        return pddc_set_error_(PDDC_EINVAL, "d_level must be a 4-byte aligned device pointer or NULL");
-    if (n > z_stride || n > a_stride || n > out_stride)
+    if (n) {
+        PDDC_TRY(device_ptr_ok(d_z, 8, "d_z"));
+        PDDC_TRY(device_ptr_ok(d_a, 4, "d_a"));
+        PDDC_TRY(device_ptr_ok(d_out, 4, "d_out"));
+    }
+    if (nblk)
+        PDDC_TRY(device_ptr_ok(d_level, 4, "d_level", true));
+    if (over_capacity(n, z_stride, a_stride, out_stride))
         return pddc_set_error_(PDDC_ECAPACITY, "squelch: %zu samples per receiver, z_stride %zu, a_stride %zu, out_stride %zu", n,
                                z_stride, a_stride, out_stride);
     if ((d_level || d_state) && nblk > blk_stride)
         return pddc_set_error_(PDDC_ECAPACITY, "squelch: %zu blocks per receiver, blk_stride %zu", nblk, blk_stride);
     if (n) {
-        const size_t rows = (size_t)s->nrx - 1;
-        const size_t zb = (rows * z_stride + n) * 8, ab = (rows * a_stride + n) * 4, ob = (rows * out_stride + n) * 4;
+        const size_t zb = rows_extent(s->nrx, n, z_stride, 8), ab = rows_extent(s->nrx, n, a_stride, 4),
+                     ob = rows_extent(s->nrx, n, out_stride, 4);
         if (ranges_overlap(d_out, ob, d_z, zb))
             return pddc_set_error_(PDDC_EINVAL, "squelch: out overlaps z");
         if (!(d_out == d_a && out_stride == a_stride) && ranges_overlap(d_out, ob, d_a, ab))
@@ -209,13 +147,9 @@ int pddc_squelch_process(pddc_squelch *s, const void *d_z, const void *d_a, size
             *blocks = 0;
         return PDDC_OK;
     }
-    PDDC_HIP_TRY(hipSetDevice(s->device));
+    PDDC_TRY(set_device(s->device));
     hipStream_t st = (hipStream_t)stream;
-    if (s->dirty) {
-        s->staged = s->table;
-        PDDC_HIP_TRY(hipMemcpyAsync(s->d_table, s->staged.data(), sizeof(SquelchRx) * (size_t)s->nrx, hipMemcpyHostToDevice, st));
-        s->dirty = false;
-    }
+    PDDC_TRY(s->table.upload(st));
     SquelchArgs a{};
     a.z = static_cast<const float2 *>(d_z);
     a.z_stride = (long long)z_stride;
@@ -227,10 +161,10 @@ int pddc_squelch_process(pddc_squelch *s, const void *d_z, const void *d_a, size
     a.state = nblk ? static_cast<uint8_t *>(d_state) : nullptr;
     a.blk_stride = (long long)blk_stride;
     a.n = (long long)n;
-    a.rx = s->d_table;
+    a.rx = s->table.dev();
     a.nrx = s->nrx;
-    a.old = s->d_state[s->cur];
-    a.new_state = s->d_state[s->cur ^ 1];
+    a.old = s->state.old();
+    a.new_state = s->state.next();
     a.B = (uint32_t)s->par.block;
     a.attack = (uint32_t)s->par.attack;
     a.hang = (uint32_t)s->par.hang;
@@ -244,7 +178,7 @@ int pddc_squelch_process(pddc_squelch *s, const void *d_z, const void *d_a, size
     a.clear_peak = s->clear_peak ? 1u : 0u;
     PDDC_HIP_TRY(launch_squelch(a, st));
     /* the launch was accepted: only now do the host-side counters move */
-    s->cur ^= 1;
+    s->state.turn();
     s->N += n;
     s->fresh = false;
     s->clear_peak = false;
@@ -256,13 +190,9 @@ int pddc_squelch_process(pddc_squelch *s, const void *d_z, const void *d_a, size
 int pddc_squelch_read(pddc_squelch *s, pddc_squelch_status *host, int clear_peak, void *stream)
 {
     if (!s || !host)
-        return pddc_set_error_(PDDC_EINVAL, "null argument");
-    PDDC_HIP_TRY(hipSetDevice(s->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (!s->fresh)
-        PDDC_HIP_TRY(hipMemcpyAsync(s->host_state.data(), s->d_state[s->cur], sizeof(SquelchState) * (size_t)s->nrx,
-                                    hipMemcpyDeviceToHost, st));
-    PDDC_HIP_TRY(hipStreamSynchronize(st));
+        return null_argument();
+    PDDC_TRY(set_device(s->device));
+    PDDC_TRY(read_back(s->host_state.data(), s->fresh ? nullptr : s->state.old(), (size_t)s->nrx, (hipStream_t)stream));
     for (int j = 0; j < s->nrx; ++j) {
         const SquelchState &r = s->host_state[(size_t)j];
         pddc_squelch_status v{ 0.0f, std::numeric_limits<float>::infinity(), 0.0f, 0u, 0u };
