@@ -909,6 +909,66 @@ int pddc_blanker_delay(const pddc_blanker *b);
 /* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_blanker_tile_outputs(void);
 
+/* ---- scope: each receiver's own spectrum and waterfall lines ------------------
+ * Beside the chain, not in it: it reads any of the per-receiver complex float32 series -- the
+ * tuner's, the blanker's or the receiver filter's output, in place, with their strides -- and writes
+ * averaged power-spectrum lines per display slot.  It changes nothing it reads.
+ * Input: z[r][i], complex float32, nsrc rows (1 .. 1024); i counts since create / reset and goes on
+ * across batches; every process() supplies n new values of every row.
+ * Slots: nslots display slots (1 .. 1024); slot j watches row[j], 0 <= row[j] < nsrc, or -1: off.
+ * Several slots may watch one row.
+ * Segments: segment s of slot j is the nfft values z[row[j]][s hop .. s hop + nfft - 1], each times
+ * the caller's float32 window[nfft] (one multiply per part), transformed with an unnormalised forward
+ * DFT in float32; p_s[k] = re^2 + im^2, float32, natural bin order.  The segment grid is global -- s
+ * counts from sample 0 and is the same for every slot -- and a segment exists once its last sample is
+ * in the stream: there is no zero padding.
+ * Lines: line l is the sum of segments l A .. l A + A - 1, A = avg, added in float32 in ascending
+ * segment order from the first segment's own value (the sum register starts at +0, and +0 + p has the
+ * bits of p for every p = re^2 + im^2).  process() writes the lines that complete in this call to
+ * lines[(j line_stride + m) nfft + k], float32, m counted from 0 in every call.  The count is the
+ * same for all slots and follows from sizes alone: pddc_scope_next_lines(s, n); without an object
+ * pddc_scope_lines(nfft, hop, avg, samples_before, n) (0 for sizes create refuses).  An off slot's
+ * lines are written as zeros.
+ * PDDC_SCOPE_CENTERED: position k holds bin (k + nfft/2) mod nfft, ascending frequency; the bits
+ * are those without the flag, only the place changes.
+ * Carried per slot, in two sets of device buffers used in turn: the samples from the start of the
+ * first incomplete segment (fewer than nfft) and the partial sum of the line under way.  Nothing is
+ * cleared from the host after create.
+ * set_slot(j, row), between two batches: with the row the slot already has nothing changes; with
+ * another the slot's carried samples and partial line return to their create values -- for that slot
+ * the new row counts as zeros before the change -- while the grid and the line numbering go on.  A
+ * slot outside [0, nslots) or a row outside [-1, nsrc): PDDC_EINVAL, nothing changed.
+ * The bits of a line depend on the watched row's values, window, nfft, hop, avg and the slot's own
+ * set_slot history alone: not on the cut into batches (n = 0 and n = 1 included), nslots, the slot's
+ * index, the other slots, strides, grid or block sizes.  Every segment goes through the same
+ * arithmetic sequence wherever it lies; one that begins in the carried samples is no exception.
+ * Limits: nfft 256, 512, 1024, 2048 or 4096; nfft/16 <= hop <= nfft; 1 <= avg <= 4096; window
+ * finite; flags 0 or PDDC_SCOPE_CENTERED.
+ * process(): z is [nsrc][z_stride] complex float32 with n values used per row; *n_lines (may be NULL)
+ * gets the lines written per slot.  Every argument is checked before anything is queued: PDDC_EINVAL
+ * for a NULL or misaligned pointer (d_z: 8 bytes, with n > 0; d_lines: 16 bytes, and NULL only when
+ * no line is due) and when the lines' bytes overlap z's; PDDC_ECAPACITY when z_stride < n, when
+ * line_stride is below the lines due, or when a batch completes more lines than one launch holds
+ * (nslots times lines above 2^31).  n = 0 is valid and does nothing.  State moves only after the
+ * launch was accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_SCOPE_CENTERED 0x1u
+typedef struct pddc_scope pddc_scope;
+int pddc_scope_create(pddc_scope **out, int device, int nsrc, int nslots, const int *rows /* [nslots], copied */,
+                      int nfft, int hop, int avg, const float *window /* [nfft], copied */, uint32_t flags);
+int pddc_scope_destroy(pddc_scope *s);
+int pddc_scope_reset(pddc_scope *s);                  /* the sample count and everything carried; the slots keep their rows; synchronises the device */
+int pddc_scope_set_slot(pddc_scope *s, int slot, int row);
+int pddc_scope_process(pddc_scope *s, const void *d_z, size_t n, size_t z_stride, void *d_lines, size_t line_stride,
+                       size_t *n_lines, void *stream);
+/* lines per slot the next process() of n samples writes */
+uint64_t pddc_scope_next_lines(const pddc_scope *s, size_t n);
+/* ... and of n samples after samples_before, without an object */
+uint64_t pddc_scope_lines(int nfft, int hop, int avg, uint64_t samples_before, size_t n);
+/* (slot, line) items one block of the kernel takes side by side (for tests that choose slot counts across that seam);
+ * 0 for an nfft create refuses */
+int pddc_scope_block_items(int nfft);
+
 /* ---- audio: the receivers' audio at a standard rate, float32 or int16 PCM -----
  * nrx receivers, each a real float32 series x_j[i] such as the demodulator writes, give nrx real
  * series y_j[k] at L/M times the input rate: 9765.625 Hz -> 48 kHz is 3072/625.  i and k count since

@@ -317,6 +317,20 @@ def ddc_lib() -> C.CDLL:
     for name in ("pddc_blanker_create", "pddc_blanker_destroy", "pddc_blanker_reset", "pddc_blanker_set_rx",
                  "pddc_blanker_process", "pddc_blanker_read", "pddc_blanker_delay", "pddc_blanker_tile_outputs"):
         getattr(L, name).restype = C.c_int
+    L.pddc_scope_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_float), C.c_uint32]
+    L.pddc_scope_destroy.argtypes = [vp]
+    L.pddc_scope_reset.argtypes = [vp]
+    L.pddc_scope_set_slot.argtypes = [vp, C.c_int, C.c_int]
+    L.pddc_scope_process.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(sz), vp]
+    L.pddc_scope_block_items.argtypes = [C.c_int]
+    for name in ("pddc_scope_create", "pddc_scope_destroy", "pddc_scope_reset", "pddc_scope_set_slot", "pddc_scope_process",
+                 "pddc_scope_block_items"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_scope_next_lines.argtypes = [vp, sz]
+    L.pddc_scope_next_lines.restype = C.c_uint64
+    L.pddc_scope_lines.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, sz]
+    L.pddc_scope_lines.restype = C.c_uint64
     L.pddc_audio_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int,
                                     C.POINTER(C.c_float), C.c_float]
     L.pddc_audio_destroy.argtypes = [vp]
@@ -841,7 +855,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Scope, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1492,6 +1506,89 @@ class Blanker(_StreamObject):
         st = np.zeros(self.nrx, dtype=blanker_status_dtype())
         check(ddc_lib().pddc_blanker_read(self._h, st.ctypes.data, self._stream(stream)))
         return st
+
+
+PDDC_SCOPE_CENTERED = 0x1
+
+
+def scope_lines(nfft: int, hop: int, avg: int, samples_before: int, n: int) -> int:
+    """pddc_scope_lines: lines per slot that n samples after samples_before complete; host arithmetic, no device"""
+    return int(ddc_lib().pddc_scope_lines(nfft, hop, avg, samples_before, n))
+
+
+def scope_block_items(nfft: int) -> int:
+    """pddc_scope_block_items: (slot, line) items one block of the kernel takes side by side; host arithmetic, no device"""
+    return int(ddc_lib().pddc_scope_block_items(nfft))
+
+
+def scope_db(lines, avg: int, window):
+    """10 log10(P / (avg (sum w)^2)): a full-scale complex tone on a bin centre reads 0 dB.  `lines` a torch tensor or an
+    array (what Scope.process returns), `window` the window the scope was made with.  -> numpy float64, same shape."""
+    import numpy as np
+    p = lines.detach().cpu().numpy() if hasattr(lines, "detach") else np.asarray(lines)
+    w = np.asarray(window, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        return 10.0 * np.log10(p.astype(np.float64) / (float(avg) * w.sum() ** 2))
+
+
+class Scope(_StreamObject):
+    """pddc_scope: the receivers' own spectrum and waterfall lines, on the device (include/perseus_ddc.h).  It reads the
+    complex64 rows that Tuner, Blanker or RxFilter return, in place, and writes per display slot the power spectrum of
+    windowed segments of nfft (256 .. 4096) samples, `hop` (nfft/16 .. nfft, default nfft/2) apart, summed over `avg`
+    segments per line.  rows: per slot the watched row of z (several slots may watch one row), or -1 for off; window
+    float32[nfft] (default: periodic Hann); centered: position k holds bin (k + nfft/2) mod nfft.  Feed it every batch
+    in order on one stream; all lines are bit-identical however the series is cut."""
+    _kind = "scope"
+
+    def __init__(self, nsrc: int, rows, nfft: int, hop=None, avg: int = 1, window=None, centered: bool = False,
+                 device: int = 0):
+        import numpy as np
+        self.nsrc, self.device, self.nfft, self.avg = int(nsrc), device, int(nfft), int(avg)
+        self.hop = int(self.nfft // 2 if hop is None else hop)
+        self.centered = bool(centered)
+        if window is None:
+            if self.nfft <= 0:
+                raise PddcError(-1, "scope: nfft must be positive")
+            window = hann_window(self.nfft)
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float32).reshape(-1))
+        if w.size != self.nfft:
+            raise PddcError(-1, f"scope: window of {w.size} values for nfft {self.nfft}")
+        self.window = w
+        r = np.ascontiguousarray(np.clip(np.asarray(rows, dtype=np.int64).reshape(-1), -2, 1 << 30), dtype=np.int32)
+        self.nslots = self.nrx = int(r.size)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_scope_create(C.byref(h), device, _clip(nsrc), self.nslots, r.ctypes.data_as(C.POINTER(C.c_int)),
+                                          _clip(nfft), _clip(self.hop), _clip(avg), w.ctypes.data_as(C.POINTER(C.c_float)),
+                                          PDDC_SCOPE_CENTERED if centered else 0))
+        self._h = h
+
+    def next_lines(self, n: int) -> int:
+        """lines per slot the next process() of n samples writes (known from sizes alone)"""
+        return int(ddc_lib().pddc_scope_next_lines(self._h, n))
+
+    def process(self, z, out=None, stream=None):
+        """One batch: z a complex64 CUDA tensor [nsrc, n] whose rows are contiguous (any row stride: the views Tuner,
+        Blanker and RxFilter return are fine).  -> float32 [nslots, lines, nfft], the lines this batch completed (a view
+        of `out`, a contiguous float32 CUDA tensor [nslots, capacity, nfft], if given)."""
+        import torch
+        if not (z.dtype == torch.complex64 and z.dim() == 2 and z.shape[0] == self.nsrc and (z.shape[1] <= 1 or z.stride(1) == 1)):
+            raise PddcError(-1, "scope: z must be a complex64 tensor [nsrc, n] with contiguous rows")
+        n = int(z.shape[1])
+        due = self.next_lines(n)
+        if out is None:
+            out = torch.empty((self.nslots, due, self.nfft), dtype=torch.float32, device=torch.device("cuda", self.device))
+        elif not (out.dtype == torch.float32 and out.dim() == 3 and out.shape[0] == self.nslots and out.shape[2] == self.nfft
+                  and out.is_contiguous()):
+            raise PddcError(-1, "scope: out must be a contiguous float32 tensor [nslots, capacity, nfft]")
+        c = C.c_size_t()
+        check(ddc_lib().pddc_scope_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)) if n else 0,
+                                           out.data_ptr() if out.numel() else None, int(out.shape[1]), C.byref(c),
+                                           self._stream(stream)))
+        return out[:, :c.value]
+
+    def set_slot(self, slot: int, row: int):
+        """slot watches `row` (-1: off) from the next batch on; a new row starts from zeros, the same row changes nothing"""
+        check(ddc_lib().pddc_scope_set_slot(self._h, _clip(slot), max(-2, min(int(row), 1 << 30))))
 
 
 AUDIO_MAX_RATIO, AUDIO_MAX_DECIM = 1 << 24, 16

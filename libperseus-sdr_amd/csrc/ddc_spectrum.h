@@ -11,7 +11,8 @@ namespace pddc {
 
 static constexpr int kSpecMinN = 1024, kSpecMaxN = 8192;
 
-/* floats (re, im pairs count as two) of the twiddle table of size n: per pass after the first, [r - 1][k] for
+/* floats (re, im pairs count as two) of the twiddle table of size n (the panorama's sizes, and 256 and 512 for the
+ * scope, ddc_scope.hip): per pass after the first, [r - 1][k] for
  * r = 1 .. R-1, k = 0 .. Ns-1, holding exp(-2 pi i r k / (Ns R)) */
 int spectrum_twiddle_len(int nfft);
 /* fills tw[spectrum_twiddle_len(nfft)]: cos / sin in double, rounded once */

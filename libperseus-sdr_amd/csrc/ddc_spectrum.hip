@@ -26,13 +26,16 @@
 
 namespace pddc {
 
-/* radices of the passes of size n: 16, 16, r2[, r3] */
+/* radices of the passes of size n: 16, 16, r2[, r3]; below the panorama's sizes (the scope, ddc_scope.hip) 16, 16 and
+ * 8, 8, 8 */
 static void spec_radices(int n, int (&r)[4], int &np)
 {
     r[0] = r[1] = 16;
     r[3] = 1;
     np = 3;
     switch (n) {
+    case 256: r[2] = 1; np = 2; break;
+    case 512: r[0] = r[1] = r[2] = 8; break;
     case 1024: r[2] = 4; break;
     case 2048: r[2] = 8; break;
     case 4096: r[2] = 16; break;
@@ -42,8 +45,9 @@ static void spec_radices(int n, int (&r)[4], int &np)
 
 int spectrum_twiddle_len(int nfft)
 {
-    int r[4], np, ns = 16, len = 0;
+    int r[4], np, len = 0;
     spec_radices(nfft, r, np);
+    int ns = r[0];
     for (int p = 1; p < np; ++p) {
         len += (r[p] - 1) * ns;
         ns *= r[p];
@@ -53,8 +57,9 @@ int spectrum_twiddle_len(int nfft)
 
 void spectrum_build_twiddles(int nfft, float *tw)
 {
-    int r[4], np, ns = 16;
+    int r[4], np;
     spec_radices(nfft, r, np);
+    int ns = r[0];
     size_t o = 0;
     for (int p = 1; p < np; ++p) {
         for (int q = 1; q < r[p]; ++q)
