@@ -676,6 +676,88 @@ int pddc_rxfilter_process(pddc_rxfilter *f, const void *d_z, size_t n, size_t z_
 /* outputs per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_rxfilter_tile_outputs(void);
 
+/* ---- carrier: synchronous AM with a tracking PLL per receiver -------------------
+ * A stage between the receiver filter and the demodulator.  K receivers (1 .. 1024), each a complex
+ * float32 series z_j[m], give K complex float32 series u_j[m], one output per input, whose real part
+ * is the synchronous audio: the demodulator in PDDC_DEMOD_SSB with word 0 behind it takes that real
+ * part bit for bit (its phasor is (1, 0)) and adds DC block and AGC.  m counts since create / reset
+ * and goes on across batches.  All arithmetic is float32 with floating-point contraction off, the
+ * same operation sequence for every caller and every cut (DESIGN.md 8 spells the sequence).
+ * Per receiver and output, in this order:
+ *   1. rotation: c + i s = exp(-2 pi i theta[m] / 2^32) from the exact 32-bit word (the phasor of
+ *      pddc_nco_freg's convention); w.re = z.re c - z.im s, w.im = z.re s + z.im c (two multiplies and
+ *      one subtract / add each).
+ *   2. phase detector: e = atan2f(w.im, w.re) (1/pi), in [-1, 1] half-turns; atan2f(0, 0) = 0.
+ *   3. loop filter (PI): v[m] = fminf(vmax, fmaxf(-vmax, fmaf(ki, e, v[m-1])));
+ *      step = fmaf(kp, e, v[m]); theta[m+1] = theta[m] + (uint32_t)(int32_t)rint(step 2^31) in unsigned
+ *      32-bit arithmetic (round to nearest even); theta[0] = 0, v[-1] = 0.  With kp <= 0.5 and
+ *      vmax < 0.5, |step| < 1, so the conversion cannot overflow.
+ *   4. lock metric: q[m] = fmaf(gamma, |e| - q[m-1], q[m-1]), q[-1] = 0.
+ *   5. output by the receiver's mode; h is the caller's Hilbert filter, L taps (odd, 3 .. 255),
+ *      D = (L - 1) / 2, common to all receivers, copied at create, every value finite:
+ *      PDDC_CARRIER_DSB  u[m] = w[m], no delay.
+ *      PDDC_CARRIER_USB / _LSB  acc = 0; for k = 0 .. L-1 ascending: acc = fmaf(h[k], w[m-k].im, acc);
+ *                        u.re = w[m-D].re - acc (USB) or + acc (LSB); u.im = w[m-D].im; w[i] = 0 for
+ *                        i < 0.  All L taps are always run.
+ *      PDDC_CARRIER_OFF  the loop is not run: theta, v, q stay as they are, w = z bit for bit, u = z.
+ * Common, fixed at create: vmax in (0, 0.5), gamma in (0, 1], lock_thr > 0 (finite), h[L].
+ * Per receiver, changeable between two batches with set_rx(j, mode, kp, ki): the mode, kp in
+ * (0, 0.5], ki in [0, 0.25].  Another kp / ki alone keeps everything carried: the loop goes on without
+ * a gap.  Another mode returns that receiver's theta, v, q and its w history to their create values
+ * (0); m goes on.  An unknown mode, a value out of range, j outside [0, nrx): PDDC_EINVAL, nothing
+ * changed.
+ * Carried per receiver: theta, v, q and the last L - 1 values of w.  The bits of u_j[m] and of the
+ * carried values depend on the receiver's own series, its set_rx history and the common parameters
+ * alone: not on the cut into batches (n = 0 included), K, j's index, the other receivers, strides,
+ * grid or tile sizes.
+ * process(): z is [nrx][z_stride] and u [nrx][u_stride] complex float32, n values used per row (the
+ * strides in elements).  d_u may be d_z with the same stride (in place); any other overlap of the two
+ * byte ranges is PDDC_EINVAL.  Every argument is checked before anything is queued: PDDC_EINVAL for
+ * NULL or not 8-byte aligned pointers with n > 0, PDDC_ECAPACITY when a stride is below n; n = 0 is
+ * valid and does nothing.  State moves only after the launch was accepted.  Stream-ordered; one
+ * stream per object, one thread at a time.
+ * read(): per receiver theta (theta[m+1] behind the last output m: the word the next output is
+ * rotated by), freq (v: the carrier's offset is v rate / 2 Hz), err (q) and locked (q < lock_thr),
+ * behind the batches submitted so far (it waits for them).  AFC: add freq, turned into a tuner word,
+ * to the receiver's tuner word.  locked is the comparison and nothing else: a receiver
+ * with its create values (just created, reset or given another mode) and an OFF receiver have q = 0
+ * and read as locked with freq = 0, and q needs some 1 / gamma outputs to say anything; a caller that
+ * retunes on locked waits that long after such an event.
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_CARRIER_OFF  0
+#define PDDC_CARRIER_DSB  1
+#define PDDC_CARRIER_USB  2
+#define PDDC_CARRIER_LSB  3
+typedef struct pddc_carrier_params {
+    float vmax;           /* bound of the loop's frequency term, half-turns per output */
+    float gamma;          /* the lock metric's smoothing                  */
+    float lock_thr;       /* locked: q < lock_thr                         */
+} pddc_carrier_params;
+typedef struct pddc_carrier_rx {
+    int mode;             /* PDDC_CARRIER_OFF / _DSB / _USB / _LSB        */
+    float kp;             /* proportional gain, (0, 0.5]                  */
+    float ki;             /* integral gain, [0, 0.25]                     */
+} pddc_carrier_rx;
+typedef struct pddc_carrier_status {
+    uint32_t theta;       /* the NCO word behind the last output          */
+    float freq;           /* v: offset = freq rate / 2 Hz                 */
+    float err;            /* q: smoothed |e|                              */
+    uint32_t locked;      /* q < lock_thr                                 */
+} pddc_carrier_status;
+typedef struct pddc_carrier pddc_carrier;
+int pddc_carrier_create(pddc_carrier **out, int device, int nrx, const pddc_carrier_params *params,
+                        const pddc_carrier_rx *rx /* [nrx], copied */, const float *hilbert /* [ntaps], copied */,
+                        int ntaps);
+int pddc_carrier_destroy(pddc_carrier *c);
+int pddc_carrier_reset(pddc_carrier *c);              /* m and everything carried; synchronises the device */
+int pddc_carrier_set_rx(pddc_carrier *c, int rx, int mode, float kp, float ki);
+int pddc_carrier_process(pddc_carrier *c, const void *d_z, size_t n, size_t z_stride, void *d_u, size_t u_stride,
+                         void *stream);
+int pddc_carrier_read(pddc_carrier *c, pddc_carrier_status *host /* [nrx] */, void *stream);
+/* outputs per tile of the kernel's walk and receivers per block (for tests that place batch cuts and K on its seams) */
+int pddc_carrier_tile_outputs(void);
+int pddc_carrier_group(void);
+
 /* ---- squelch: per-receiver level meter and gated audio ------------------------
  * A stage between the demodulator and audio.  Per batch it reads the receivers' complex series
  * z_j[m] (the rows the demodulator reads) and their audio a_j[m] (the demodulator's output at the

@@ -19,6 +19,7 @@ PDDC_ENODEV and the wrappers raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -68,6 +69,16 @@ class DemodRx(C.Structure):
 class DemodParams(C.Structure):
     """pddc_demod_params (include/perseus_ddc.h)"""
     _fields_ = [("rho", C.c_float), ("lam", C.c_float), ("target", C.c_float), ("gmax", C.c_float)]
+
+
+class CarrierParams(C.Structure):
+    """pddc_carrier_params (include/perseus_ddc.h)"""
+    _fields_ = [("vmax", C.c_float), ("gamma", C.c_float), ("lock_thr", C.c_float)]
+
+
+class CarrierRx(C.Structure):
+    """pddc_carrier_rx (include/perseus_ddc.h)"""
+    _fields_ = [("mode", C.c_int), ("kp", C.c_float), ("ki", C.c_float)]
 
 
 class SquelchParams(C.Structure):
@@ -282,6 +293,18 @@ def ddc_lib() -> C.CDLL:
     L.pddc_rxfilter_tile_outputs.argtypes = []
     for name in ("pddc_rxfilter_create", "pddc_rxfilter_destroy", "pddc_rxfilter_reset", "pddc_rxfilter_set_rx",
                  "pddc_rxfilter_process", "pddc_rxfilter_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_carrier_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(CarrierParams), C.POINTER(CarrierRx),
+                                      C.POINTER(C.c_float), C.c_int]
+    L.pddc_carrier_destroy.argtypes = [vp]
+    L.pddc_carrier_reset.argtypes = [vp]
+    L.pddc_carrier_set_rx.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float]
+    L.pddc_carrier_process.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    L.pddc_carrier_read.argtypes = [vp, vp, vp]
+    L.pddc_carrier_tile_outputs.argtypes = []
+    L.pddc_carrier_group.argtypes = []
+    for name in ("pddc_carrier_create", "pddc_carrier_destroy", "pddc_carrier_reset", "pddc_carrier_set_rx",
+                 "pddc_carrier_process", "pddc_carrier_read", "pddc_carrier_tile_outputs", "pddc_carrier_group"):
         getattr(L, name).restype = C.c_int
     L.pddc_squelch_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(SquelchParams), C.POINTER(SquelchRx)]
     L.pddc_squelch_destroy.argtypes = [vp]
@@ -855,7 +878,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Scope, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1287,6 +1310,100 @@ class Demod(_StreamObject):
         """receiver rx from the next output on: another word alone goes on phase-continuously, another mode or other
         flags start that receiver's carried values afresh"""
         check(ddc_lib().pddc_demod_set_rx(self._h, rx, int(mode), int(bfo) & 0xFFFFFFFF, int(flags) & 0xFFFFFFFF))
+
+
+PDDC_CARRIER_OFF, PDDC_CARRIER_DSB, PDDC_CARRIER_USB, PDDC_CARRIER_LSB = 0, 1, 2, 3
+
+
+def carrier_tile_outputs() -> int:
+    """pddc_carrier_tile_outputs: outputs per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_carrier_tile_outputs())
+
+
+def carrier_group() -> int:
+    """pddc_carrier_group: receivers per block of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_carrier_group())
+
+
+def carrier_loop(bandwidth_hz: float, rate_hz: float, damping: float = 0.7071):
+    """The gains of Carrier's loop for a natural frequency of bandwidth_hz at rate_hz outputs per second:
+    wn = 2 pi bandwidth / rate, kp = 2 damping wn, ki = wn^2.  -> (kp, ki)"""
+    wn = 2.0 * math.pi * float(bandwidth_hz) / float(rate_hz)
+    return 2.0 * float(damping) * wn, wn * wn
+
+
+def carrier_hilbert(L: int, beta: float = 8.0):
+    """The Hilbert filter of Carrier's USB / LSB: L taps (odd), the type-III ideal 2 / (pi (k - D)) at odd k - D and 0 at
+    even, D = (L - 1) / 2, under a Kaiser window.  -> float32 [L]"""
+    import numpy as np
+    L = int(L)
+    if L < 3 or not L & 1:
+        raise ValueError("carrier_hilbert: L odd, >= 3")
+    k = np.arange(L, dtype=np.int64) - (L - 1) // 2
+    odd = (k & 1) != 0
+    h = np.where(odd, 2.0 / (np.pi * np.where(odd, k, 1)), 0.0) * np.kaiser(L, beta)
+    return h.astype(np.float32)
+
+
+def carrier_status_dtype():
+    """pddc_carrier_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("theta", np.uint32), ("freq", np.float32), ("err", np.float32), ("locked", np.uint32)])
+
+
+class Carrier(_StreamObject):
+    """pddc_carrier: synchronous AM -- a phase-locked loop on each receiver's carrier, on the device
+    (include/perseus_ddc.h).  It goes between RxFilter (or Tuner) and Demod: z, rotated by the loop's phasor, comes out
+    as a complex series whose real part is the audio of both sidebands (PDDC_CARRIER_DSB) or, through the Hilbert filter
+    `hilbert` (carrier_hilbert), of the upper or the lower one (_USB / _LSB, delayed by (L - 1) / 2 outputs); Demod in
+    PDDC_DEMOD_SSB with word 0 takes that real part and adds DC block and AGC.  rx: one (mode, kp, ki) per receiver
+    (carrier_loop gives the gains), PDDC_CARRIER_OFF passes z.  vmax bounds the loop's frequency term (half-turns per
+    output), gamma smooths the lock metric, a receiver is locked while that metric is below lock_thr.  Feed it every
+    batch in order on one stream; outputs are bit-identical however the series is cut."""
+    _kind = "carrier"
+
+    def __init__(self, rx, hilbert, vmax: float = 0.25, gamma: float = 1.0 / 64, lock_thr: float = 0.05, device: int = 0):
+        import numpy as np
+        rx = [tuple(r) for r in rx]
+        self.nrx, self.device = len(rx), device
+        arr = (CarrierRx * max(self.nrx, 1))()
+        for j, (mode, kp, ki) in enumerate(rx):
+            arr[j] = CarrierRx(_clip(mode), float(kp), float(ki))
+        h = np.ascontiguousarray(hilbert, dtype=np.float32).reshape(-1)
+        self.ntaps = int(h.size)
+        self.params = CarrierParams(vmax, gamma, lock_thr)
+        hd = C.c_void_p()
+        check(ddc_lib().pddc_carrier_create(C.byref(hd), device, self.nrx, C.byref(self.params), arr,
+                                            h.ctypes.data_as(C.POINTER(C.c_float)), _clip(h.size)))
+        self._h = hd
+
+    def process(self, z, out=None, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> complex64 [nrx, n]
+        (a view of `out`, a complex64 CUDA tensor [nrx, capacity] with contiguous rows, if given; `out` may be z itself:
+        in place)."""
+        import torch
+        if not self._rows(z, torch.complex64):
+            raise PddcError(-1, "carrier: z must be a complex64 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        out, cap = self._out(out, n, torch.complex64, "out must be a complex64")
+        check(ddc_lib().pddc_carrier_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                             out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
+        return out[:, :n]
+
+    def set_rx(self, rx: int, mode: int, kp: float, ki: float):
+        """receiver rx from the next output on: other gains alone leave the loop running, another mode starts that
+        receiver's loop and history afresh"""
+        check(ddc_lib().pddc_carrier_set_rx(self._h, int(rx), _clip(mode), float(kp), float(ki)))
+
+    def read(self, stream=None):
+        """-> numpy structured array [nrx] (theta, freq, err, locked) after the batches submitted so far (it waits for
+        them); the carrier's offset from the tuned frequency is freq * rate / 2 Hz.  A receiver just created, reset or
+        given another mode, and an OFF one, has err = 0 and reads as locked: err says something after some 1 / gamma
+        outputs"""
+        import numpy as np
+        st = np.zeros(self.nrx, dtype=carrier_status_dtype())
+        check(ddc_lib().pddc_carrier_read(self._h, st.ctypes.data, self._stream(stream)))
+        return st
 
 
 PDDC_SQL_GATE, PDDC_SQL_RELATIVE = 0x1, 0x2
