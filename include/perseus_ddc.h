@@ -605,6 +605,12 @@ int pddc_tuner_channel_list(int nchan, const uint32_t *freg, int nrx, int *chann
  * alone: phase-continuous, psi' = psi + (bfo - bfo') m0 mod 2^32 (the tuner's rule).  Another mode or
  * other flags: that receiver's carried z, d, y, e return to their create values and psi = 0; m goes on.
  * An unknown mode or flag: PDDC_EINVAL, nothing changed.
+ * Non-finite samples are data like any other: what they do follows from the operations above, in the receiver's own
+ * row alone.  The detector of a NaN sample is NaN (FM: of that output and the next).  Without a post stage that is
+ * all.  DCBLOCK: y is NaN from there on, and so is every output, until the caller acts.  AGC without DCBLOCK: one NaN
+ * output, e = fmaxf(NaN, lambda e) steps over it.  An infinite y leaves e = inf for good (lambda inf): the gain is 0
+ * and every later output 0.  The caller gets the row back with set_rx to another mode or other flags (and back), or
+ * reset.
  * process(): z is [nrx][z_stride] complex float32 and out [nrx][out_stride] float32, n values used per
  * row (the strides in elements: the tuner's output view has its capacity as stride).  Every argument
  * is checked before anything is queued: PDDC_EINVAL for NULL or misaligned (8 / 4 bytes) pointers with
@@ -657,6 +663,10 @@ int pddc_demod_tile_outputs(void);
  * out_j[m] depend on the receiver's series, its filter history and the bank alone: not on the cut
  * into batches (batches of 0, 1 and fewer than T - 1 inputs included), nrx, j's index, the other
  * receivers and their filters, strides, grid or tile sizes.
+ * Non-finite samples: transient.  A NaN in z_j[p] makes the T outputs p .. p + T - 1 of that receiver NaN, in the part
+ * (re or im) it is in, zero-valued taps included (0 NaN is NaN); every other output, and every other receiver, has
+ * the bits it has without it.  An infinity does the same with inf or, against a zero tap or an opposite infinity, NaN.
+ * Nothing is left behind once the sample has left the window: the caller does nothing.
  * process(): z is [nrx][z_stride] and out [nrx][out_stride] complex float32, n values used per row
  * (the strides in elements: the tuner's output view has its capacity as stride).  Every argument is
  * checked before anything is queued: PDDC_EINVAL for NULL or not 8-byte aligned pointers with n > 0,
@@ -710,6 +720,15 @@ int pddc_rxfilter_tile_outputs(void);
  * carried values depend on the receiver's own series, its set_rx history and the common parameters
  * alone: not on the cut into batches (n = 0 included), K, j's index, the other receivers, strides,
  * grid or tile sizes.
+ * Non-finite samples, in the receiver's own row alone.  A NaN in z[m] makes w[m] and e NaN.  v: fmaxf and fminf drop
+ * the NaN, v[m] = -vmax, and the loop goes on from there.  theta: a NaN step adds 0 to theta (C leaves that conversion
+ * undefined; this is the rule here).  q is NaN from there on, so read() gives err = NaN and locked = 0 until the caller
+ * acts.  u: NaN at m (DSB), at the L outputs m .. m + L - 1 in re and at m + D in im (USB / LSB, zero-valued taps
+ * included); later outputs are finite again.  OFF passes the sample as it is.  An infinite sample: with re and im both
+ * infinite, or one of them infinite against a phasor component that is exactly 0 (theta = 0 among others), w is NaN
+ * (inf c - inf s, inf 0) and everything is as after a NaN; with one infinite part and ordinary c and s, w is
+ * (+-inf, +-inf), whose angle is a finite number: the loop takes a wrong step and q stays finite.  The caller gets err
+ * and locked back with set_rx to another mode (and back), or reset.
  * process(): z is [nrx][z_stride] and u [nrx][u_stride] complex float32, n values used per row (the
  * strides in elements).  d_u may be d_z with the same stride (in place); any other overlap of the two
  * byte ranges is PDDC_EINVAL.  Every argument is checked before anything is queued: PDDC_EINVAL for
@@ -796,6 +815,12 @@ int pddc_carrier_group(void);
  * threshold and flag history and the create parameters alone: not on the cut into batches (batches of
  * 0 and of fewer than B samples included), nrx, j's index, the other receivers, strides, grid or tile
  * sizes.
+ * Non-finite samples, in the receiver's own row alone.  In a: out = a g wherever c > 0, so a NaN or an infinity
+ * passes (inf g is inf); with c == 0 out is +0.0f whatever a is.  Nothing is carried.  In z: the block's level is NaN
+ * or inf.  A NaN level: every comparison with it is false -- closed, the run towards attack restarts; open, the block
+ * counts towards hang --, fminf and fmaxf drop it from f and peak, level reads NaN until the next block.  An infinite
+ * level counts as a loud block; peak = inf from then on: sticky by definition, until read(clear_peak).  level and f
+ * heal by themselves with the next block: the caller does nothing.
  * process(): z is [nrx][z_stride] complex float32, a [nrx][a_stride] and out [nrx][out_stride]
  * float32, n values used per row; d_level float32 and d_state uint8, [nrx][blk_stride] each or NULL,
  * get *blocks = floor((N + n) / B) - floor(N / B) values per row: entry k of a row belongs to the
@@ -877,6 +902,13 @@ int pddc_squelch_tile_outputs(void);
  * The bits of every output and every weight depend on the receiver's series, its set_rx history, T,
  * D and eps alone: not on the cut into batches (batches of 0 included), nrx, j's index, the other
  * receivers, strides, grid or tile sizes.
+ * Non-finite samples, in the receiver's own row alone: sticky.  A NaN, an infinity or a value whose square overflows
+ * (1e25) in x[p] makes g, and with it every weight, NaN or infinite at the latest when the sample enters the window
+ * (sample p + D); weights that are not finite stay so, w lam + g u has no way back, and every NR / NOTCH output after
+ * that is not finite.  OFF passes x and holds its weights.  RESTART zeroes the weights only: the sample is still in
+ * the carried inputs for D + T - 1 samples and poisons them again.  So the caller feeds D + T - 1 good samples and
+ * then calls set_rx with PDDC_ADAPT_RESTART -- from that sample on the row is that of a receiver restarted there on
+ * the good series --, or calls reset.
  * process(): a is [nrx][a_stride] and out [nrx][out_stride] float32, n values used per row.  Every
  * argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned (4 bytes)
  * pointer with work to do, PDDC_ECAPACITY when a stride is below n; d_out == d_a with equal strides
@@ -952,6 +984,13 @@ int pddc_adapt_tile_outputs(void);
  * history and the create parameters alone: not on the cut into batches (batches of 0, of fewer than D
  * and of fewer than B samples included), nrx, j's index, the other receivers, strides, grid or tile
  * sizes.
+ * Non-finite samples, in the receiver's own row alone: healing.  A NaN sample does not trigger (p > ref thr is
+ * false) and comes out as it is, D samples later, unless a neighbouring trigger blanks it (+0.0f whatever z is); an
+ * infinite one, or one whose square overflows, triggers (once ref > 0) and is blanked with its neighbourhood, 2 D + 1
+ * finite outputs.
+ * The block it lies in has L = NaN or inf: with ref > 0, x = fminf(L, ref cap) = ref cap and ref rises by its largest
+ * step; in the first block (ref = 0) ref = L itself, then NaN for one block (inf - inf), then `ref > 0` is false and
+ * ref starts again from the next block's L.  ref is finite again within three blocks: the caller does nothing.
  * process(): z is [nrx][z_stride] and out [nrx][out_stride] complex float32, n values used per row.
  * Every argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned (8 bytes)
  * pointer with work to do, PDDC_ECAPACITY when a stride is below n; ANY overlap of out with z is
@@ -1024,6 +1063,10 @@ int pddc_blanker_tile_outputs(void);
  * set_slot history alone: not on the cut into batches (n = 0 and n = 1 included), nslots, the slot's
  * index, the other slots, strides, grid or block sizes.  Every segment goes through the same
  * arithmetic sequence wherever it lies; one that begins in the carried samples is no exception.
+ * Non-finite samples: transient.  A NaN in z[r][p] makes every bin of the segments that hold sample p NaN, and with
+ * them the lines those segments go into, in the slots that watch row r; every other line and slot has the bits it has
+ * without it.  Nothing is left behind once the sample has left the carried samples: the caller does nothing (set_slot
+ * to another row, or reset, drops it at once).
  * Limits: nfft 256, 512, 1024, 2048 or 4096; nfft/16 <= hop <= nfft; 1 <= avg <= 4096; window
  * finite; flags 0 or PDDC_SCOPE_CENTERED.
  * process(): z is [nsrc][z_stride] complex float32 with n values used per row; *n_lines (may be NULL)
@@ -1071,6 +1114,9 @@ int pddc_scope_block_items(int nfft);
  * batch by batch, so nothing wraps at any stream length.  The bits of y_j[k] depend on the receiver's
  * series, L, M, P, T and g alone: not on the cut into batches (0 inputs and 0 outputs included), nrx,
  * j's index, the other receivers, strides, grid or tile sizes.
+ * Non-finite samples: transient.  A NaN in x_j[p] makes the outputs k with n_k - T < p <= n_k NaN (PCM: 0), zero
+ * weights included; every other output, and every other receiver, has the bits it has without it.  Nothing is left
+ * behind once the sample has left the last T - 1 inputs: the caller does nothing.
  * process(): x is [nrx][x_stride] float32 with n values used per row (the demodulator's output view
  * has its capacity as stride); d_f32 [nrx][f32_stride] float32 and d_i16 [nrx][i16_stride] int16 get
  * *count values per row; either may be NULL, not both when there are outputs.  Every argument is

@@ -76,7 +76,8 @@ class AdaptRef:
         w = self.weights
         on = (self.mode != OFF)[:, None]
         mu, lam, eps = self.mu, self.lam[:, None], self.eps
-        with np.errstate(under="ignore"):
+        # non-finite samples are data like any other (include/perseus_ddc.h, "Non-finite samples"): no warnings
+        with np.errstate(under="ignore", over="ignore", invalid="ignore"):
             for i in range(n):
                 # u_k = x[m - D - k], k = 0 .. T - 1
                 u = xx[:, H + i - D - T + 1:H + i - D + 1][:, ::-1]

@@ -83,10 +83,12 @@ class AudioRef:
                 g0, g1 = self.g[t * P + q], self.g[t * P + q + 1]
                 acc += (g0 + alpha * (g1 - g0))[None, :] * xx[:, at - t]
         else:
-            for t in range(T):
-                g0, g1 = self.g[t * P + q], self.g[t * P + q + 1]
-                w = (alpha.astype(np.float64) * (g1 - g0).astype(np.float64) + g0.astype(np.float64)).astype(np.float32)
-                acc = (w.astype(np.float64)[None, :] * xx[:, at - t].astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
+            # non-finite samples are data like any other (include/perseus_ddc.h, "Non-finite samples"): no warnings
+            with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+                for t in range(T):
+                    g0, g1 = self.g[t * P + q], self.g[t * P + q + 1]
+                    w = (alpha.astype(np.float64) * (g1 - g0).astype(np.float64) + g0.astype(np.float64)).astype(np.float32)
+                    acc = (w.astype(np.float64)[None, :] * xx[:, at - t].astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
         self.hist = xx[:, xx.shape[1] - (T - 1):]
         self.N += n
         self.k += count

@@ -118,22 +118,29 @@ class CarrierRef:
         kp, ki = self.kp[on], self.ki[on]
         theta, v, q = self.theta[on], self.v[on], self.q[on]
         wr, wi, E = np.zeros(zr.shape, ft), np.zeros(zr.shape, ft), np.zeros(zr.shape, ft)
-        for m in range(n if zr.shape[0] else 0):
-            ph = np.exp(-2j * np.pi * theta.astype(np.float64) / 2.0 ** 32).astype(self.ct)
-            c, s = ph.real.astype(ft), ph.imag.astype(ft)
-            x, y = zr[:, m], zi[:, m]
-            a = x * c - y * s
-            b = x * s + y * c
-            e = (np.arctan2(b, a) * self.invpi).astype(ft)
-            v = np.minimum(self.vmax, np.maximum(-self.vmax, self._fma(ki, e, v))).astype(ft)
-            step = self._fma(kp, e, v).astype(ft)
-            theta = (theta + np.rint(step.astype(np.float64) * 2.0 ** 31).astype(np.int64)) & MASK
-            q = self._fma(self.gamma, (np.abs(e) - q).astype(ft), q).astype(ft)
-            wr[:, m], wi[:, m], E[:, m] = a, b, e
+        # non-finite samples are data like any other (include/perseus_ddc.h, "Non-finite samples"): no warnings
+        with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+            for m in range(n if zr.shape[0] else 0):
+                ph = np.exp(-2j * np.pi * theta.astype(np.float64) / 2.0 ** 32).astype(self.ct)
+                c, s = ph.real.astype(ft), ph.imag.astype(ft)
+                x, y = zr[:, m], zi[:, m]
+                a = x * c - y * s
+                b = x * s + y * c
+                e = (np.arctan2(b, a) * self.invpi).astype(ft)
+                # fminf / fmaxf, as the header spells them: a NaN operand is dropped, so a NaN e leaves v = -vmax
+                v = np.fmin(self.vmax, np.fmax(-self.vmax, self._fma(ki, e, v))).astype(ft)
+                step = self._fma(kp, e, v).astype(ft)
+                # a NaN step adds 0 to theta (the header's rule; C leaves the conversion of a NaN undefined)
+                turn = np.rint(np.where(np.isnan(step), 0.0, step.astype(np.float64)) * 2.0 ** 31).astype(np.int64)
+                theta = (theta + turn) & MASK
+                q = self._fma(self.gamma, (np.abs(e) - q).astype(ft), q).astype(ft)
+                wr[:, m], wi[:, m], E[:, m] = a, b, e
         self.theta[on], self.v[on], self.q[on] = theta, v, q
         self.e[on] = E
         w = z.copy()
-        w[on] = wr + 1j * wi
+        won = np.empty(wr.shape, self.ct)
+        won.real, won.imag = wr, wi
+        w[on] = won
         u = w.copy()
         ssb = (self.mode == USB) | (self.mode == LSB)
         if np.any(ssb):
@@ -141,13 +148,18 @@ class CarrierRef:
             ext = np.concatenate([self.hist[ssb], w[ssb]], axis=1)
             xi = np.ascontiguousarray(ext.imag, dtype=np.float64)
             acc = np.zeros((xi.shape[0], n), ft)
-            for k in range(self.L):
-                t = xi[:, H - k:H - k + n] * self.h[k]
-                t += acc
-                acc[...] = t                        # one rounding to ft: fmaf
             sign = np.where(self.mode[ssb] == USB, -1.0, 1.0).astype(ft)[:, None]
             dre = np.ascontiguousarray(ext.real[:, H - D:H - D + n], dtype=ft)
-            u[ssb] = (dre + sign * acc) + 1j * ext.imag[:, H - D:H - D + n]
+            with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+                for k in range(self.L):
+                    t = xi[:, H - k:H - k + n] * self.h[k]
+                    t += acc
+                    acc[...] = t                    # one rounding to ft: fmaf
+                re = dre + sign * acc
+            # the two parts are put side by side: x + 1j y would make a NaN of y where x is infinite
+            us = np.empty(re.shape, self.ct)
+            us.real, us.imag = re, ext.imag[:, H - D:H - D + n]
+            u[ssb] = us
         self.hist = np.concatenate([self.hist, w], axis=1)[:, n:].copy()
         self.m += n
         return u

@@ -97,24 +97,27 @@ class DemodRef:
         re, im, pre, pim = (np.ascontiguousarray(v, dtype=ft) for v in (z.real, z.imag, zprev.real, zprev.imag))
         d = np.zeros((self.K, n), ft)
         am, fm, ssb = self.mode == AM, self.mode == FM, self.mode == SSB
-        d[am] = np.sqrt(re[am] * re[am] + im[am] * im[am])
-        pr = re[fm] * pre[fm] + im[fm] * pim[fm]
-        pi = im[fm] * pre[fm] - re[fm] * pim[fm]
-        d[fm] = np.arctan2(pi, pr) * self.invpi
-        d[fm & self.fresh, 0] = 0
         ms = (np.uint64(self.m & MASK) + np.arange(n, dtype=np.uint64)) & np.uint64(MASK)
         th = (self.beta[ssb, None] * ms[None, :] + self.psi[ssb, None]) & np.uint64(MASK)
         ph = np.exp(-2j * np.pi * th.astype(np.float64) / 2.0 ** 32).astype(self.ct)
         c, s = np.ascontiguousarray(ph.real, dtype=ft), np.ascontiguousarray(ph.imag, dtype=ft)
-        d[ssb] = re[ssb] * c - im[ssb] * s
+        # non-finite samples are data like any other (include/perseus_ddc.h, "Non-finite samples"): no warnings
+        with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+            d[am] = np.sqrt(re[am] * re[am] + im[am] * im[am])
+            pr = re[fm] * pre[fm] + im[fm] * pim[fm]
+            pi = im[fm] * pre[fm] - re[fm] * pim[fm]
+            d[fm] = np.arctan2(pi, pr) * self.invpi
+            d[fm & self.fresh, 0] = 0
+            d[ssb] = re[ssb] * c - im[ssb] * s
         dc, agc = (self.flags & DC) != 0, (self.flags & AGC) != 0
         dp, yp, ep = self.dp, self.yp, self.ep
-        with np.errstate(divide="ignore"):
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
             for i in range(n):
                 di = d[:, i]
                 y = np.where(dc, self._fma(self.rho, yp, di - dp), di).astype(ft)
-                e = np.maximum(np.abs(y), self.lam * ep).astype(ft)
-                g = np.minimum(self.gmax, self.target / e).astype(ft)
+                # fmaxf / fminf, as the header spells them: a NaN operand is dropped, not passed on
+                e = np.fmax(np.abs(y), self.lam * ep).astype(ft)
+                g = np.fmin(self.gmax, self.target / e).astype(ft)
                 out[:, i] = np.where(agc, y * g, y)
                 self.e[:, i] = e
                 dp, yp, ep = di, y, e

@@ -51,18 +51,23 @@ class RxFilterRef:
         n = z.shape[1]
         zz = np.concatenate([self.hist, z], axis=1)                    # zz[:, T - 1 + i] = z[m + i]
         h = self.bank[self.sel]                                        # [nrx, T]
-        if self.f32:
-            re = np.zeros((self.nrx, n), np.float32)
-            im = np.zeros((self.nrx, n), np.float32)
-            for t in range(T):
-                seg = zz[:, T - 1 - t:T - 1 - t + n]
-                re = (h[:, t:t + 1] * seg.real + re.astype(np.float64)).astype(np.float32)
-                im = (h[:, t:t + 1] * seg.imag + im.astype(np.float64)).astype(np.float32)
-            out = re.astype(np.float64) + 1j * im.astype(np.float64)
-        else:
-            out = np.zeros((self.nrx, n), np.complex128)
-            for t in range(T):
-                out += h[:, t:t + 1] * zz[:, T - 1 - t:T - 1 - t + n]
+        # non-finite samples are data like any other (include/perseus_ddc.h, "Non-finite samples"): no warnings
+        with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+            if self.f32:
+                re = np.zeros((self.nrx, n), np.float32)
+                im = np.zeros((self.nrx, n), np.float32)
+                for t in range(T):
+                    seg = zz[:, T - 1 - t:T - 1 - t + n]
+                    re = (h[:, t:t + 1] * seg.real + re.astype(np.float64)).astype(np.float32)
+                    im = (h[:, t:t + 1] * seg.imag + im.astype(np.float64)).astype(np.float32)
+                # the taps are real, so the two parts never mix: side by side (re + 1j im would make a NaN of re
+                # where im is not finite, and +0 of a re that is -0: the model now keeps that sign, as the device does)
+                out = np.empty((self.nrx, n), np.complex128)
+                out.real, out.imag = re, im
+            else:
+                out = np.zeros((self.nrx, n), np.complex128)
+                for t in range(T):
+                    out += h[:, t:t + 1] * zz[:, T - 1 - t:T - 1 - t + n]
         self.hist = zz[:, zz.shape[1] - (T - 1):]
         self.m += n
         return out

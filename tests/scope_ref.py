@@ -88,9 +88,10 @@ def scope_ref(z, nfft, hop, avg, window, first_segment=0, nsegments=None):
     segs = segs[:, first_segment:segs.shape[1] if nsegments is None else first_segment + nsegments]
     L = segs.shape[1] // avg
     out = np.zeros((z.shape[0], L, nfft))
-    for l in range(L):
-        X = np.fft.fft(segs[:, l * avg:(l + 1) * avg] * w, axis=-1)
-        out[:, l] = (X.real ** 2 + X.imag ** 2).sum(axis=1)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):     # non-finite samples are data: no warnings
+        for l in range(L):
+            X = np.fft.fft(segs[:, l * avg:(l + 1) * avg] * w, axis=-1)
+            out[:, l] = (X.real ** 2 + X.imag ** 2).sum(axis=1)
     return out
 
 
@@ -102,12 +103,13 @@ def scope_model_f32(z, nfft, hop, avg, window):
     segs = segments_view(z, nfft, hop)
     L = segs.shape[1] // avg
     out = np.zeros((z.shape[0], L, nfft), F32)
-    for l in range(L):
-        for i in range(avg):
-            X = scipy.fft.fft(segs[:, l * avg + i] * w, axis=-1)
-            assert X.dtype == np.complex64
-            p = (X.real * X.real + X.imag * X.imag).astype(F32)
-            out[:, l] = p if i == 0 else out[:, l] + p
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):     # non-finite samples are data: no warnings
+        for l in range(L):
+            for i in range(avg):
+                X = scipy.fft.fft(segs[:, l * avg + i] * w, axis=-1)
+                assert X.dtype == np.complex64
+                p = (X.real * X.real + X.imag * X.imag).astype(F32)
+                out[:, l] = p if i == 0 else out[:, l] + p
     return out
 
 

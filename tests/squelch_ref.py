@@ -90,14 +90,16 @@ class SquelchRef:
         assert z.dtype == np.complex64 and a.dtype == F32 and z.shape == a.shape and z.shape[0] == self.K
         n = z.shape[1]
         re, im = np.ascontiguousarray(z.real), np.ascontiguousarray(z.imag)
-        p = (re * re) + (im * im)                                   # float32 products, one float32 sum
+        with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+            p = (re * re) + (im * im)                               # float32 products, one float32 sum
         assert p.dtype == F32
         out = np.empty((self.K, n), F32)
         levels, states = [], []
         gated = (self.flags & GATE) != 0
         zero = np.zeros(self.K, F32)
         for i in range(n):
-            self.s = self.s + p[:, i]
+            with np.errstate(invalid="ignore", over="ignore"):
+                self.s = self.s + p[:, i]
             rise = self.open | ~gated
             self.c = np.where(rise, np.minimum(self.c + 1, self.R), np.maximum(self.c - 1, 0))
             g = self.c.astype(F32) * self.invR
