@@ -1138,6 +1138,80 @@ uint64_t pddc_audio_outputs(uint32_t L, uint32_t M, uint64_t inputs_before, size
 int pddc_audio_process(pddc_audio *a, const void *d_x, size_t n, size_t x_stride, void *d_f32, size_t f32_stride,
                        void *d_i16, size_t i16_stride, size_t *count, void *stream);
 
+/* ---- mixer: receivers' audio summed into output buses, with a peak limiter -----
+ * The stage behind audio (or squelch, or the adaptive filter): nrx receivers, each a real float32
+ * series a_j[i], are summed into nbus output buses (1 .. 8) and leave as planar float32 and / or
+ * interleaved int16 frames, what a sound device takes.  Every value is float32, fmaf is one
+ * rounding, floating-point contraction is off.  i counts since create / reset across batches.
+ * Gains: receiver j has a target gain to[j][q] per bus (finite, any sign; the nrx x nbus table of
+ * create).  set_rx(rx, gains[nbus]) takes effect at the first sample of the next accepted batch:
+ * from[q] := the gain the last sample processed was given (at create: to), to[q] := the new value,
+ * the receiver's ramp counter c := 0; two calls between two batches count as one, the later wins.
+ * Per sample c = min(c + 1, R) first, then g = to if c == R, else fmaf(to - from, float(c) invR, from);
+ * R is the common ramp length (1 .. 65536), invR = 1.0f / R; c = R at create and reset.
+ * A receiver is SILENT at a sample when there c == R and every to[q] is +-0: it is not read (a NaN
+ * in it reaches no bus) and it is not in the sum.  The others are active; p numbers them in
+ * ascending j.  With C = pddc_mixer_chunk(), for bus q and sample i: chunk m takes
+ * p = m C .. m C + C - 1, s_m = +0, then s_m = fmaf(g_pq(i), a_p[i], s_m) in ascending p; y = s_0,
+ * then y = y + s_m in ascending m; no active receiver: y = +0.  The tree depends on the active set
+ * alone: not on n, the cut into batches, grid or tile.
+ * Limiter (flag PDDC_MIX_LIMIT; block Lb 8 .. 4096, ceil finite > 0, 0 < rel <= 1), per bus with
+ * the absolute block index k = i div Lb: P[k] = fmaxf over the block of fabsf(y) from +0 (a NaN is
+ * dropped); m = fmaxf(P[k], P[k+1]); t[k] = ceil / m if m > ceil else 1;
+ * E[k] = fminf(t[k], fmaf(rel, 1 - E[k-1], E[k-1])), E[-1] = 1.  Sample r of block k:
+ * g = E[k] if r = Lb - 1, else fmaf(E[k] - E[k-1], float(r + 1) invLb, E[k-1]);
+ * out = fminf(fmaxf(y g, -ceil), ceil), so |out| <= ceil exactly.  Block k is written once block
+ * k + 1 is complete: Lb max(0, N div Lb - 1) outputs after N samples, a batch's count follows from
+ * sizes alone (pddc_mixer_next_outputs; pddc_mixer_outputs without an object).  Without the flag
+ * out = y and a batch of n samples writes n outputs.
+ * +-Inf in y, in block k: m is Inf for the blocks k - 1 and k, so t = 0 and E = 0 there; the sample
+ * itself becomes Inf * 0 = NaN, which fmaxf drops: it leaves as -ceil, as does a NaN in y (which P
+ * ignores: it changes no gain).  From block k + 1 on E recovers by rel per block.  Nothing sticks.
+ * Outputs, either or both: f32[q * f32_stride + k] planar; i16[k * nbus + q] interleaved frames,
+ * p = (int16) clamp(rintf(out scale), -32768, 32767), NaN -> 0, audio's rule.
+ * Status per bus (pddc_mixer_read): peak = fmaxf of |y| over the samples processed since create or
+ * the last clear, gain = the latest E, min_gain = the smallest E since create or the last clear
+ * (1 and 1 without the limiter or before the first E).
+ * process(): a is [nrx][a_stride] float32 with n values used per row.  Every argument is checked
+ * before anything is queued: PDDC_EINVAL for a NULL or misaligned (4 / 4 / 2 bytes) pointer with
+ * work to do, for no output pointer when there are outputs, and for an output that overlaps a;
+ * PDDC_ECAPACITY when a_stride < n, f32_stride < count or i16_cap_frames < count; n = 0 is valid and
+ * changes nothing; a refused call changes nothing.  Stream-ordered; one stream per object, one
+ * thread at a time.  create: argument errors (ranges, non-finite gains, ceil, rel, scale) before
+ * any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_MIX_LIMIT     0x1u
+typedef struct pddc_mixer_params {
+    int nbus;             /* Q, 1 .. 8                                      */
+    int ramp;             /* R, 1 .. 65536 samples                          */
+    uint32_t flags;       /* PDDC_MIX_LIMIT                                 */
+    int block;            /* Lb, 8 .. 4096 (with PDDC_MIX_LIMIT)            */
+    float ceil;           /* finite, > 0 (with PDDC_MIX_LIMIT)              */
+    float rel;            /* 0 < rel <= 1 (with PDDC_MIX_LIMIT)             */
+    float scale;          /* int16 = out * scale; finite, > 0               */
+} pddc_mixer_params;
+typedef struct pddc_mixer_status {
+    float peak, gain, min_gain;
+} pddc_mixer_status;
+typedef struct pddc_mixer pddc_mixer;
+int pddc_mixer_create(pddc_mixer **out, int device, int nrx, const pddc_mixer_params *params,
+                      const float *gains /* [nrx][nbus], copied */);
+int pddc_mixer_destroy(pddc_mixer *m);
+int pddc_mixer_reset(pddc_mixer *m);                  /* N, the ramps (c = R), everything carried; synchronises the device */
+int pddc_mixer_set_rx(pddc_mixer *m, int rx, const float *gains /* [nbus] */);
+/* outputs per bus the next process() of n samples writes (host arithmetic) */
+int pddc_mixer_next_outputs(const pddc_mixer *m, size_t n, size_t *count);
+/* the limiter's count without an object (host arithmetic, no device):
+ * Lb (max(0, (before + n) div Lb - 1) - max(0, before div Lb - 1)); 0 for an unsupported block */
+uint64_t pddc_mixer_outputs(int block, uint64_t samples_before, size_t n);
+int pddc_mixer_process(pddc_mixer *m, const void *d_a, size_t n, size_t a_stride, void *d_f32, size_t f32_stride,
+                       void *d_i16, size_t i16_cap_frames, size_t *count, void *stream);
+/* status[nbus] after the batches submitted so far (it waits for them); clear: peak and min_gain restart */
+int pddc_mixer_read(pddc_mixer *m, pddc_mixer_status *host /* [nbus] */, int clear, void *stream);
+/* C, the active receivers per chunk sum (for the reference) */
+int pddc_mixer_chunk(void);
+/* samples per tile of the kernel's walk (for tests that cut batches across that seam) */
+int pddc_mixer_tile_outputs(void);
+
 /* pinned host memory for the two calls above */
 int pddc_host_alloc(void **h_ptr, size_t nbytes);
 int pddc_host_free(void *h_ptr);

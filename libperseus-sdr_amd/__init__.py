@@ -101,6 +101,12 @@ class AdaptRx(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("mu", C.c_float), ("leak", C.c_float), ("flags", C.c_uint32)]
 
 
+class MixerParams(C.Structure):
+    """pddc_mixer_params (include/perseus_ddc.h)"""
+    _fields_ = [("nbus", C.c_int), ("ramp", C.c_int), ("flags", C.c_uint32), ("block", C.c_int), ("ceil", C.c_float),
+                ("rel", C.c_float), ("scale", C.c_float)]
+
+
 class BlankerParams(C.Structure):
     """pddc_blanker_params (include/perseus_ddc.h)"""
     _fields_ = [("block", C.c_int), ("guard", C.c_int), ("ramp", C.c_int), ("beta", C.c_float), ("cap", C.c_float)]
@@ -364,6 +370,20 @@ def ddc_lib() -> C.CDLL:
         getattr(L, name).restype = C.c_int
     L.pddc_audio_outputs.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, sz]
     L.pddc_audio_outputs.restype = C.c_uint64
+    L.pddc_mixer_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(MixerParams), C.POINTER(C.c_float)]
+    L.pddc_mixer_destroy.argtypes = [vp]
+    L.pddc_mixer_reset.argtypes = [vp]
+    L.pddc_mixer_set_rx.argtypes = [vp, C.c_int, C.POINTER(C.c_float)]
+    L.pddc_mixer_next_outputs.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_mixer_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, sz, C.POINTER(sz), vp]
+    L.pddc_mixer_read.argtypes = [vp, vp, C.c_int, vp]
+    L.pddc_mixer_chunk.argtypes = []
+    L.pddc_mixer_tile_outputs.argtypes = []
+    for name in ("pddc_mixer_create", "pddc_mixer_destroy", "pddc_mixer_reset", "pddc_mixer_set_rx", "pddc_mixer_next_outputs",
+                 "pddc_mixer_process", "pddc_mixer_read", "pddc_mixer_chunk", "pddc_mixer_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_mixer_outputs.argtypes = [C.c_int, C.c_uint64, sz]
+    L.pddc_mixer_outputs.restype = C.c_uint64
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
     L.pddc_pipeline_time_stage0_inline.restype = C.c_int
@@ -878,7 +898,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt and Audio share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Audio and Mixer share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1803,6 +1823,129 @@ class Audio(_StreamObject):
                                            cap[1], C.byref(c), self._stream(stream)))
         views = [o[:, :c.value] for o in outs if o is not None]
         return views[0] if len(views) == 1 else tuple(views)
+
+
+PDDC_MIX_LIMIT = 0x1
+
+
+def mixer_chunk() -> int:
+    """pddc_mixer_chunk: C, the active receivers per chunk sum of the mixer's summation tree; host arithmetic, no device"""
+    return int(ddc_lib().pddc_mixer_chunk())
+
+
+def mixer_tile_outputs() -> int:
+    """pddc_mixer_tile_outputs: samples per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_mixer_tile_outputs())
+
+
+def mixer_outputs(block: int, samples_before: int, n: int) -> int:
+    """pddc_mixer_outputs: outputs per bus of the limiter for n samples after samples_before, block * (max(0, (before + n)
+    // block - 1) - max(0, before // block - 1)); 0 for an unsupported block length; host arithmetic, no device"""
+    block = int(block)
+    return int(ddc_lib().pddc_mixer_outputs(block if -1 << 31 <= block < 1 << 31 else 0, samples_before, n))
+
+
+def mixer_status_dtype():
+    """pddc_mixer_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("peak", np.float32), ("gain", np.float32), ("min_gain", np.float32)])
+
+
+def mixer_pan(gain_db: float, pan: float):
+    """The constant-power stereo pair of a receiver at gain_db decibels and position pan, -1 (left) .. 0 (centre) .. +1
+    (right): (g cos t, g sin t) with g = 10^(gain_db / 20) and t = (pan + 1) pi / 4, so left^2 + right^2 = g^2.
+    -> (left, right) as float32 values"""
+    import numpy as np
+    if not -1.0 <= float(pan) <= 1.0:
+        raise PddcError(-1, "mixer_pan: pan must be in -1 .. 1")
+    g, t = 10.0 ** (float(gain_db) / 20.0), (float(pan) + 1.0) * math.pi / 4.0
+    return float(np.float32(g * math.cos(t))), float(np.float32(g * math.sin(t)))
+
+
+class Mixer(_StreamObject):
+    """pddc_mixer: the receivers' real float32 series, such as Audio, Squelch and Adapt write, summed into Q output buses
+    on the device (include/perseus_ddc.h).  gains: [nrx][Q] target gains (1 <= Q <= 8; mixer_pan gives a stereo pair); a
+    change (set_rx) is ramped linearly over `ramp` samples from the next batch on; a receiver whose gains are all zero and
+    whose ramp has ended is silent: not read, not in the sum.  limit = (block, ceil, rel) puts a peak limiter on every
+    bus: the gain follows the block peaks one block ahead (the outputs come one block late), falls at once, recovers by
+    `rel` per block, and |out| <= ceil exactly.  Outputs: planar float32 [Q, count] and / or interleaved int16 frames
+    [count, Q], p = clamp(rint(out * scale)).  The sum is a fixed tree over the active receivers: feed it every batch in
+    order on one stream; outputs are bit-identical however the series is cut."""
+    _kind = "mixer"
+
+    def __init__(self, gains, ramp: int, limit=None, scale: float = 32767.0, device: int = 0):
+        import numpy as np
+        g = np.ascontiguousarray(np.asarray(gains, dtype=np.float32))
+        if g.ndim != 2:
+            raise PddcError(-1, "mixer: gains must be [nrx][nbus]")
+        self.nrx, self.nbus, self.device = int(g.shape[0]), int(g.shape[1]), device
+        self.ramp, self.limit, self.scale = int(ramp), None if limit is None else tuple(limit), float(scale)
+        block, ceil, rel = self.limit if self.limit else (0, 0.0, 0.0)
+        self.block = int(block)
+        self.params = MixerParams(_clip(self.nbus), _clip(ramp), PDDC_MIX_LIMIT if self.limit else 0, _clip(block), ceil, rel,
+                                  self.scale)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_mixer_create(C.byref(h), device, self.nrx, C.byref(self.params),
+                                          g.ctypes.data_as(C.POINTER(C.c_float)) if g.size else None))
+        self._h = h
+
+    def next_outputs(self, n: int) -> int:
+        """outputs per bus the next process() of n samples writes (known from sizes alone)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_mixer_next_outputs(self._h, n, C.byref(c)))
+        return int(c.value)
+
+    def process(self, a, f32: bool = True, i16: bool = False, out_f32=None, out_i16=None, stream=None):
+        """One batch: a float32 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the view Audio.process
+        returns is fine).  -> float32 [Q, count] if f32, int16 [count, Q] if i16, both as a tuple if both (views of
+        `out_f32`, a CUDA tensor [Q, capacity] with contiguous rows, and `out_i16`, a contiguous CUDA tensor [capacity,
+        Q], if given; giving one asks for it).  No output may overlap a."""
+        import torch
+        if not self._rows(a, torch.float32):
+            raise PddcError(-1, "mixer: a must be a float32 tensor [nrx, n] with contiguous rows")
+        f32, i16 = f32 or out_f32 is not None, i16 or out_i16 is not None
+        if not (f32 or i16):
+            raise PddcError(-1, "mixer: ask for float32, int16 or both")
+        n, Q = int(a.shape[1]), self.nbus
+        due = self.next_outputs(n)
+        dev = torch.device("cuda", self.device)
+        fcap = icap = 0
+        if f32:
+            if out_f32 is None:
+                out_f32 = torch.empty((Q, due), dtype=torch.float32, device=dev)
+            elif not (out_f32.dtype == torch.float32 and out_f32.dim() == 2 and out_f32.shape[0] == Q
+                      and (out_f32.shape[1] <= 1 or out_f32.stride(1) == 1)):
+                raise PddcError(-1, "mixer: out_f32 must be a float32 tensor [nbus, capacity] with contiguous rows")
+            fcap = int(out_f32.stride(0)) if out_f32.shape[1] >= due else int(out_f32.shape[1])
+        if i16:
+            if out_i16 is None:
+                out_i16 = torch.empty((due, Q), dtype=torch.int16, device=dev)
+            elif not (out_i16.dtype == torch.int16 and out_i16.dim() == 2 and out_i16.shape[1] == Q and out_i16.is_contiguous()):
+                raise PddcError(-1, "mixer: out_i16 must be a contiguous int16 tensor [capacity, nbus]")
+            icap = int(out_i16.shape[0])
+        ptr = [o.data_ptr() if o is not None and o.numel() else None for o in (out_f32, out_i16)]
+        c = C.c_size_t()
+        check(ddc_lib().pddc_mixer_process(self._h, a.data_ptr() if n else None, n, int(a.stride(0)), ptr[0], fcap, ptr[1], icap,
+                                           C.byref(c), self._stream(stream)))
+        views = ([out_f32[:, :c.value]] if f32 else []) + ([out_i16[:c.value]] if i16 else [])
+        return views[0] if len(views) == 1 else tuple(views)
+
+    def set_rx(self, rx: int, gains):
+        """receiver rx: new target gains [Q], reached over `ramp` samples from the first sample of the next batch on,
+        starting at the gain of the last sample processed; two calls before one batch count as one"""
+        import numpy as np
+        g = np.ascontiguousarray(np.asarray(gains, dtype=np.float32).reshape(-1))
+        if g.size != self.nbus:
+            raise PddcError(-1, "mixer: set_rx takes one gain per bus")
+        check(ddc_lib().pddc_mixer_set_rx(self._h, int(rx), g.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def read(self, clear: bool = False, stream=None):
+        """-> numpy structured array [Q] (peak, gain, min_gain) after the batches submitted so far (it waits for them);
+        clear: peak restarts at 0 and min_gain at 1 for the samples after the call"""
+        import numpy as np
+        st = np.zeros(self.nbus, dtype=mixer_status_dtype())
+        check(ddc_lib().pddc_mixer_read(self._h, st.ctypes.data, 1 if clear else 0, self._stream(stream)))
+        return st
 
 
 class PinnedBuffer:

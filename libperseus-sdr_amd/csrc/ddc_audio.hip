@@ -43,13 +43,6 @@ __device__ __forceinline__ float audio_input(const float *xr, const float *old, 
     return idx < n ? xr[idx] : 0.0f;
 }
 
-__device__ __forceinline__ int16_t audio_pcm(float y, float scale)
-{
-    const float s = y * scale;
-    const float c = fminf(fmaxf(rintf(s), -32768.0f), 32767.0f);
-    return s != s ? (int16_t)0 : (int16_t)(int)c;
-}
-
 __global__ __launch_bounds__(kAudioThreads) void k_audio(AudioArgs a)
 {
     constexpr int G = kAudioGroup, TT = kAudioTile;
@@ -112,7 +105,7 @@ __global__ __launch_bounds__(kAudioThreads) void k_audio(AudioArgs a)
                     if (a.f32)
                         a.f32[(long long)(g0 + g) * a.f32_stride + k] = acc[g];
                     if (a.i16)
-                        a.i16[(long long)(g0 + g) * a.i16_stride + k] = audio_pcm(acc[g], a.scale);
+                        a.i16[(long long)(g0 + g) * a.i16_stride + k] = pcm16(acc[g], a.scale);
                 }
             }
         }

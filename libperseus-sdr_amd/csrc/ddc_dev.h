@@ -52,5 +52,13 @@ __device__ __forceinline__ void nco_lo(uint32_t phase, float &c, float &s)
     s = __uint_as_float(__float_as_uint(ss) ^ neg_s);
 }
 
+/* float32 audio to saturated int16 PCM (k_audio, the mixer): clamp(rintf(y scale), -32768, 32767), ties to even; NaN -> 0 */
+__device__ __forceinline__ int16_t pcm16(float y, float scale)
+{
+    const float s = y * scale;
+    const float c = fminf(fmaxf(rintf(s), -32768.0f), 32767.0f);
+    return s != s ? (int16_t)0 : (int16_t)(int)c;
+}
+
 } // namespace pddc
 #endif

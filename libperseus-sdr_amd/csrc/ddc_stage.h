@@ -1,6 +1,6 @@
 /*
  * ddc_stage.h -- what the host files of the per-receiver stages (blanker, receiver filter, demodulator, squelch,
- * adaptive filter, audio) share: device buffers that free themselves, the pair of carried records a batch reads and
+ * adaptive filter, audio, and the mixer behind them) share: device buffers that free themselves, the pair of carried records a batch reads and
  * writes in turn, the receiver table with its upload, and the common ends of create / destroy / reset / set_rx /
  * process / read.  A stage's own file keeps its parameters, its table entries, its kernel arguments and its counters.
  * Host only (no kernel includes it); internal, nothing here is exported.
