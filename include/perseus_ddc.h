@@ -945,6 +945,107 @@ int pddc_adapt_read_weights(pddc_adapt *s, float *host /* [nrx][taps] */, void *
 /* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_adapt_tile_outputs(void);
 
+/* ---- denoise: spectral noise reduction per receiver ---------------------------
+ * A stage where adapt sits: behind the demodulator, the squelch or the adaptive filter, in front of
+ * audio.  Short-time transform, a noise estimate and a gain per bin, overlap-add.  Per batch it reads
+ * the receivers' real float32 rows x_j[m] and writes out_j[m], n values out per n values in, delayed
+ * by exactly nfft samples.  m counts samples since create / reset and goes on across batches;
+ * x[m] = 0 for m < 0.
+ * Fixed at create, common to all receivers: nrx (1 .. 1024); nfft (256, 512 or 1024); hop (nfft/2 or
+ * nfft/4), R = nfft / hop; a window w[nfft] (the caller's, finite, copied; used for analysis and
+ * synthesis); the tracker's constants: smooth a, up, down, each in (0, 1]; nmin in [0, 1]; eps,
+ * finite and > 0.
+ * Per receiver, changeable between batches with set_rx: mode PDDC_DENOISE_OFF or _NR; the
+ * over-subtraction beta, finite and > 0; the gain floor gmin in [0, 1]; the decision-directed weight
+ * alpha in [0, 1); flags: PDDC_DENOISE_RESTART, one-shot: the next completed frame is a first frame;
+ * PDDC_DENOISE_HOLD, lasting until a set_rx without it: S and N are not updated (a "noise profile").
+ * A set_rx governs every frame whose last sample arrives in a later batch.  A value outside the
+ * above, not finite, rx outside [0, nrx): PDDC_EINVAL, nothing changed.
+ * Frames: frame q >= 0 holds the inputs m = (q+1) hop - nfft .. (q+1) hop - 1 and is complete once
+ * (q+1) hop samples have arrived.  B = nfft/2 + 1 bins.
+ * Per completed frame and bin k, in this order; all arithmetic outside the two transforms is float32
+ * with contraction off, every division the correctly rounded one, comparisons as written:
+ *    1. f[i] = x[..] w[i]; X_k the forward transform of f.
+ *    2. P = re re + im im.
+ *    3. first frame (after create, reset or RESTART): S = P, N = P, A = 0.
+ *    4. otherwise, unless HOLD: S = S + a (P - S); if S > N: r = N + up N; r2 = nmin S; if r < r2
+ *       then r = r2; N = (r < S) ? r : S; else N = N + down (S - N).  (A smoothed periodogram and a
+ *       minimum tracker: it falls at `down`, rises by at most the factor 1 + up per frame and is
+ *       never more than nmin below S.)
+ *    5. Nb = beta N + eps.
+ *    6. t = P / Nb - 1.
+ *    7. xi = alpha (A / Nb) + (1 - alpha) (t > 0 ? t : 0).
+ *    8. g = xi / (1 + xi).
+ *    9. G = (g > gmin) ? g : gmin.
+ *   10. with OFF, G = 1: S and N go on being tracked, so switching on is seamless (OFF is unity gain
+ *       through the transforms, not a copy).
+ *   11. A = (G G) P.
+ *   12. Y_k = G X_k.
+ *   13. s = the inverse real transform of Y, scaled 1/nfft; the frame's term is t_q[i] = s[i] w[i].
+ * Overlap-add: y[m] = sum of t_q[i] over the frames that hold m, added in ascending q starting from
+ * the first term itself (at most R terms); out[m] = y[m - nfft], and 0 for m < nfft.  With this delay
+ * every value a batch emits is final however the batch is cut: out[m] needs frame floor(m / hop) - 1,
+ * which is complete before x[m] arrives.
+ * Carried per receiver: the inputs since the start of the oldest incomplete frame, the partial
+ * overlap sums, the finished y not yet emitted, S, N, A per bin, the first-frame mark.  Nothing else.
+ * The bits of every output and every N depend on the receiver's series, its set_rx history (in sample
+ * positions) and the create-time parameters alone: not on the cut into batches (batches of 0 and
+ * batches that complete no frame included), nrx, the row's index, the other receivers, strides, grid
+ * or tile sizes.  A frame's transform is a function of that frame's own nfft values alone.
+ * Non-finite samples, in the receiver's own row alone (other rows keep their bits): a NaN, an
+ * infinity or a value whose square overflows (1e25) in x[p] makes P NaN or infinite in every bin of
+ * the R frames that hold it (where w is not 0 at its place).  Those frames' terms, and the outputs
+ * they reach, are NaN or infinite (for the overflowing square finite, of the sample's size).  S, and
+ * with it N, is NaN at the latest one frame later: S + a (P - S) and both branches of the tracker have
+ * no way back, so N stays NaN (read_noise shows it) when good samples follow.  Every comparison with a
+ * NaN is false, so from the first good frame on g > gmin fails in every bin and G = gmin: the output
+ * is finite again, the input through the floor gain (through 1 with OFF), for as long as N is NaN.
+ * Under HOLD S and N are not touched and A alone is lost, for one frame.  Recovery: the caller feeds
+ * nfft good samples and then calls set_rx with PDDC_DENOISE_RESTART; the next completed frame q holds
+ * good samples only and is a first frame, and from out index q hop + nfft on (once the overlap has
+ * drained) the row is that of a receiver restarted there on the good series.  Or reset.
+ * process(): x is [nrx][x_stride] and out [nrx][out_stride] float32, n values used per row.  Every
+ * argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned (4 bytes)
+ * pointer with work to do, PDDC_ECAPACITY when a stride is below n; in place is not offered: any
+ * overlap of out with x is PDDC_EINVAL; n = 0 is valid and does nothing.  State moves only after the
+ * launch was accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * read_noise(): N [nrx][B] as the last accepted batch left it (it waits for it); zeros before the
+ * first completed frame.
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_DENOISE_OFF     0u
+#define PDDC_DENOISE_NR      1u
+#define PDDC_DENOISE_RESTART 0x1u
+#define PDDC_DENOISE_HOLD    0x2u
+typedef struct pddc_denoise_params {
+    int nfft;             /* 256, 512 or 1024                             */
+    int hop;              /* nfft/2 or nfft/4                             */
+    float smooth;         /* a: the periodogram's smoothing, (0, 1]       */
+    float up;             /* the tracker's rise per frame, (0, 1]         */
+    float down;           /* the tracker's fall, (0, 1]                   */
+    float nmin;           /* N >= nmin S while it rises, [0, 1]           */
+    float eps;            /* added to beta N before the divisions         */
+} pddc_denoise_params;
+typedef struct pddc_denoise_rx {
+    uint32_t mode;        /* PDDC_DENOISE_OFF, _NR                        */
+    float beta;           /* over-subtraction, > 0                        */
+    float gmin;           /* gain floor, 0 .. 1                           */
+    float alpha;          /* decision-directed weight, 0 <= alpha < 1     */
+    uint32_t flags;       /* PDDC_DENOISE_HOLD; _RESTART (set_rx)         */
+} pddc_denoise_rx;
+typedef struct pddc_denoise pddc_denoise;
+int pddc_denoise_create(pddc_denoise **out, int device, int nrx, const pddc_denoise_params *params,
+                        const float *window /* [nfft], copied */, const pddc_denoise_rx *rx /* [nrx], copied */);
+int pddc_denoise_destroy(pddc_denoise *s);
+int pddc_denoise_reset(pddc_denoise *s);              /* everything carried; synchronises the device */
+int pddc_denoise_set_rx(pddc_denoise *s, int rx, uint32_t mode, float beta, float gmin, float alpha, uint32_t flags);
+int pddc_denoise_process(pddc_denoise *s, const void *d_x, size_t n, size_t x_stride, void *d_out, size_t out_stride,
+                         void *stream);
+int pddc_denoise_read_noise(pddc_denoise *s, float *host /* [nrx][nfft/2 + 1] */, void *stream);
+/* the delay in samples: nfft (host arithmetic, no device); 0 for an nfft that is none of the three */
+int pddc_denoise_delay(int nfft);
+/* frames of one block pass of the kernel's walk (for tests that place batch cuts on its seams) */
+int pddc_denoise_tile_frames(void);
+
 /* ---- blanker: impulse noise blanker per receiver ------------------------------
  * A stage between the tuner and the receiver filter, the only place where an impulse is still a few
  * samples long.  Per batch it reads the receivers' complex float32 rows z_j[m] (the tuner's output

@@ -101,6 +101,17 @@ class AdaptRx(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("mu", C.c_float), ("leak", C.c_float), ("flags", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    """pddc_denoise_params (include/perseus_ddc.h)"""
+    _fields_ = [("nfft", C.c_int), ("hop", C.c_int), ("smooth", C.c_float), ("up", C.c_float), ("down", C.c_float),
+                ("nmin", C.c_float), ("eps", C.c_float)]
+
+
+class DenoiseRx(C.Structure):
+    """pddc_denoise_rx (include/perseus_ddc.h)"""
+    _fields_ = [("mode", C.c_uint32), ("beta", C.c_float), ("gmin", C.c_float), ("alpha", C.c_float), ("flags", C.c_uint32)]
+
+
 class MixerParams(C.Structure):
     """pddc_mixer_params (include/perseus_ddc.h)"""
     _fields_ = [("nbus", C.c_int), ("ramp", C.c_int), ("flags", C.c_uint32), ("block", C.c_int), ("ceil", C.c_float),
@@ -334,6 +345,17 @@ def ddc_lib() -> C.CDLL:
     L.pddc_adapt_tile_outputs.argtypes = []
     for name in ("pddc_adapt_create", "pddc_adapt_destroy", "pddc_adapt_reset", "pddc_adapt_set_rx", "pddc_adapt_process",
                  "pddc_adapt_read_weights", "pddc_adapt_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_denoise_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(DenoiseParams), vp, C.POINTER(DenoiseRx)]
+    L.pddc_denoise_destroy.argtypes = [vp]
+    L.pddc_denoise_reset.argtypes = [vp]
+    L.pddc_denoise_set_rx.argtypes = [vp, C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]
+    L.pddc_denoise_process.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    L.pddc_denoise_read_noise.argtypes = [vp, vp, vp]
+    L.pddc_denoise_delay.argtypes = [C.c_int]
+    L.pddc_denoise_tile_frames.argtypes = []
+    for name in ("pddc_denoise_create", "pddc_denoise_destroy", "pddc_denoise_reset", "pddc_denoise_set_rx",
+                 "pddc_denoise_process", "pddc_denoise_read_noise", "pddc_denoise_delay", "pddc_denoise_tile_frames"):
         getattr(L, name).restype = C.c_int
     L.pddc_blanker_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(BlankerParams), C.POINTER(BlankerRx)]
     L.pddc_blanker_destroy.argtypes = [vp]
@@ -898,7 +920,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Audio and Mixer share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Audio and Mixer share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1579,6 +1601,88 @@ class Adapt(_StreamObject):
         w = np.zeros((self.nrx, self.taps), dtype=np.float32)
         check(ddc_lib().pddc_adapt_read_weights(self._h, w.ctypes.data, self._stream(stream)))
         return w
+
+
+PDDC_DENOISE_OFF, PDDC_DENOISE_NR = 0, 1
+PDDC_DENOISE_RESTART, PDDC_DENOISE_HOLD = 0x1, 0x2
+
+
+def denoise_delay(nfft: int) -> int:
+    """pddc_denoise_delay: the stage's delay in samples (nfft); host arithmetic, no device"""
+    return int(ddc_lib().pddc_denoise_delay(_clip(nfft)))
+
+
+def denoise_tile_frames() -> int:
+    """pddc_denoise_tile_frames: frames per block pass of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_denoise_tile_frames())
+
+
+def denoise_window(nfft: int, hop: int):
+    """The square-root Hann window sqrt(0.5 - 0.5 cos(2 pi (i + 0.5) / nfft)), scaled so that the squares of the nfft / hop
+    windows that meet at a sample sum to 1: with it unity gain (PDDC_DENOISE_OFF) gives the delayed input.  -> float64 (the object takes it as float32)"""
+    import numpy as np
+    i = np.arange(nfft, dtype=np.float64)
+    w = np.sqrt(0.5 - 0.5 * np.cos(2.0 * np.pi * (i + 0.5) / nfft))
+    return w / np.sqrt(nfft / (2.0 * hop))
+
+
+class Denoise(_StreamObject):
+    """pddc_denoise: spectral noise reduction per receiver, on the device (include/perseus_ddc.h).  It goes where Adapt
+    goes, between Demod (or Squelch, or Adapt) and Audio: frames of `nfft` (256, 512, 1024) samples every `hop` (nfft/2,
+    nfft/4), a tracked noise estimate and a decision-directed gain per bin, overlap-add; the output is the input delayed
+    by nfft samples with the noise taken down to the gain floor.  rx: one (mode, beta, gmin, alpha[, flags]) per
+    receiver, or a count for the defaults.  Feed it every batch in order on one stream; all outputs are bit-identical
+    however the series is cut."""
+    _kind = "denoise"
+
+    def __init__(self, rx, nfft: int = 256, hop: int = 128, window=None, smooth: float = 0.3, up: float = 0.02,
+                 down: float = 0.3, nmin: float = 1.0e-4, eps: float = 1.0e-20, device: int = 0):
+        import numpy as np
+        if isinstance(rx, int):
+            rx = [(PDDC_DENOISE_NR, 2.0, 0.1, 0.98)] * rx
+        rx = [tuple(r) for r in rx]
+        self.nrx, self.device = len(rx), device
+        arr = (DenoiseRx * max(self.nrx, 1))()
+        for j, r in enumerate(rx):
+            mode, beta, gmin, alpha = r[:4]
+            arr[j] = DenoiseRx(int(mode) & 0xFFFFFFFF, float(beta), float(gmin), float(alpha),
+                               (int(r[4]) if len(r) > 4 else 0) & 0xFFFFFFFF)
+        self.nfft, self.hop = int(nfft), int(hop)
+        self.params = DenoiseParams(_clip(nfft), _clip(hop), smooth, up, down, nmin, eps)
+        if window is None:
+            window = denoise_window(self.nfft, self.hop)
+        w = np.ascontiguousarray(window, dtype=np.float32)
+        if w.shape != (self.nfft,):
+            raise PddcError(-1, "denoise: window must hold nfft values")
+        h = C.c_void_p()
+        check(ddc_lib().pddc_denoise_create(C.byref(h), device, self.nrx, C.byref(self.params), w.ctypes.data, arr))
+        self._h = h
+
+    def process(self, x, out=None, stream=None):
+        """One batch: a float32 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the views Demod.process,
+        Squelch.process and Adapt.process return are fine).  -> float32 [nrx, n] (a view of `out`, a float32 CUDA tensor
+        [nrx, capacity] with contiguous rows, if given): the input nfft samples ago, denoised.  `out` must not overlap x."""
+        import torch
+        if not self._rows(x, torch.float32):
+            raise PddcError(-1, "denoise: x must be a float32 tensor [nrx, n] with contiguous rows")
+        n = int(x.shape[1])
+        out, cap = self._out(out, n, torch.float32, "out must be a float32")
+        check(ddc_lib().pddc_denoise_process(self._h, x.data_ptr() if n else None, n, int(x.stride(0)),
+                                             out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
+        return out[:, :n]
+
+    def set_rx(self, rx: int, mode: int, beta: float, gmin: float, alpha: float, flags: int = 0):
+        """receiver rx, for every frame whose last sample arrives in a later batch.  flags: PDDC_DENOISE_RESTART (the next
+        completed frame is a first frame), PDDC_DENOISE_HOLD (the noise estimate stays, until a call without it)"""
+        check(ddc_lib().pddc_denoise_set_rx(self._h, int(rx), int(mode) & 0xFFFFFFFF, float(beta), float(gmin), float(alpha),
+                                            int(flags) & 0xFFFFFFFF))
+
+    def read_noise(self, stream=None):
+        """-> numpy float32 [nrx, nfft/2 + 1]: the noise estimate N as the last batch left it (it waits for it)"""
+        import numpy as np
+        nn = np.zeros((self.nrx, self.nfft // 2 + 1), dtype=np.float32)
+        check(ddc_lib().pddc_denoise_read_noise(self._h, nn.ctypes.data, self._stream(stream)))
+        return nn
 
 
 PDDC_NB_ON = 0x1
