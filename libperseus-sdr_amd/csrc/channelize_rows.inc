@@ -120,11 +120,11 @@
         if (sl + 1 < nr)
             load_unit((long long)sl + 1 + NSL);
         __syncthreads();
-        spec_pass_mid<M, NT, 16, 1, 0, 1>(buf, tw + TW1);
-        spec_pass_mid<M, NT, 16, 16, 1, 2>(buf, tw + TW1);
+        spec_pass_mid<M, NT, 16, 1, kImgLoaders, 16>(buf, tw + TW1);
+        spec_pass_mid<M, NT, 16, 16, 16, 0>(buf, tw + TW1);
         const bool neg_odd = Q == 2 && ((a.row_parity + (unsigned)(row0 + sl)) & 1u);
         f32x2 *orow = reinterpret_cast<f32x2 *>(a.out) + (size_t)(row0 + sl) * (size_t)a.count;
-        spec_pass_out<M, NT, R2, 256, 2>(buf, tw + TW2, [&](int bin, float2 v) {
+        spec_pass_out<M, NT, R2, 256, 0>(buf, tw + TW2, [&](int bin, float2 v) {
 #if PDDC_CHAN_LIST
             const int i = col_of[bin];
 #else

@@ -139,7 +139,7 @@ int pddc_blanker_process(pddc_blanker *b, const void *d_z, size_t n, size_t z_st
     a.W = (uint32_t)b->par.guard;
     a.D = (uint32_t)(b->par.guard + b->par.ramp);
     a.ph0 = (uint32_t)(b->N % (uint64_t)b->par.block);
-    a.magic = ((1u << kBlankerDivShift) + a.B - 1u) / a.B;
+    a.magic = meter_magic(a.B);
     a.invB = b->invB;
     a.invR1 = b->invR1;
     a.beta = b->par.beta;

@@ -21,7 +21,6 @@ static constexpr int kBlankerMaxDelay = kBlankerMaxGuard + kBlankerMaxRamp;    /
 static constexpr int kBlankerCarryWords = 2 * kBlankerMaxDelay / 64;           /* trigger bits carried: 2 D <= 512 */
 static constexpr int kBlankerMapWords = kBlankerCarryWords + kBlankerTile / 64;/* ... and a tile's behind them     */
 static constexpr uint32_t kBlankerOn = 1u;              /* PDDC_NB_ON                                              */
-static constexpr int kBlankerDivShift = 20;             /* x / B = (x * magic) >> 20 for x < 2 TT, B < TT          */
 
 /* one receiver as the kernel sees it */
 struct BlankerRx {
@@ -52,7 +51,7 @@ struct BlankerArgs {
     unsigned long long *new_bits;
     uint32_t B, W, D;
     uint32_t ph0;             /* N mod B: where in its block the launch's first sample lies                     */
-    uint32_t magic;           /* ceil(2^20 / B)                                                                 */
+    uint32_t magic;           /* meter_magic(B)                                                                 */
     float invB, invR1, beta, cap;
     uint32_t fresh;           /* nothing carried is read: the create values                                     */
 };

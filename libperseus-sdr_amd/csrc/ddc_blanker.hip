@@ -8,8 +8,9 @@
  *               positive; t[m] = ON && ref > 0 && p > ref thr; out[n] = z[n - D] g with g = 0 within W samples of a
  *               trigger, (dist - W) invR1 within D, else 1 (z's bits).  DESIGN.md 8 has the definition.
  *
- * Walk: k_squelch's.  A block takes G = 4 consecutive receivers and walks the whole batch tile by tile, TT = 256 samples a
- * time; the block grid B is common to the receivers, so a tile is cut into the same SEGMENTS for all of them: segment 0
+ * Walk: k_squelch's, and the same code where it is the same: the cut of a tile, step 2, the division by B and the next
+ * tile's phase are the block meter of ddc_meter_dev.h; steps 1, 3, 4 and 5 are this file's.  A block takes G = 4
+ * consecutive receivers and walks the whole batch tile by tile, TT = 256 samples a time; the block grid B is common to the receivers, so a tile is cut into the same SEGMENTS for all of them: segment 0
  * ends the block under way (or the tile), the following ones are whole blocks, the last may be the start of one.
  *   1. thread i takes sample i of the tile for one receiver after the other (coalesced 8-byte loads of z, those of the
  *      NEXT tile issued here and held in registers); p stays in a register and goes to sp[g][i] in LDS.
@@ -38,17 +39,11 @@
  * and at word 0.
  */
 #include "ddc_blanker.h"
-#include "ddc_dev.h"
+#include "ddc_meter_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace pddc {
-
-/* x / B for x < 2 TT: B >= TT has at most one whole block in reach */
-__device__ __forceinline__ uint32_t blanker_div(uint32_t x, uint32_t B, uint32_t magic)
-{
-    return B >= (uint32_t)kBlankerTile ? (x >= B ? 1u : 0u) : (x * magic) >> kBlankerDivShift;
-}
 
 __global__ __launch_bounds__(kBlankerThreads) void k_blanker(BlankerArgs a)
 {
@@ -106,14 +101,8 @@ __global__ __launch_bounds__(kBlankerThreads) void k_blanker(BlankerArgs a)
         const uint32_t cnt = (uint32_t)(a.n - o < TT ? a.n - o : TT);
         const long long m = o + tid;
         const bool in = (uint32_t)tid < cnt;
-        /* the tile's segments */
-        const uint32_t len0 = cnt < B - ph ? cnt : B - ph;
-        const uint32_t rem = cnt - len0;
-        const uint32_t full = blanker_div(rem, B, a.magic);
-        const uint32_t tail = rem - full * B;
-        const uint32_t done0 = ph + len0 == B ? 1u : 0u;
-        const uint32_t nseg = 1u + full + (tail ? 1u : 0u);
-        const uint32_t nblk = done0 + full;
+        const MeterCut cut = meter_cut<TT>(cnt, ph, B, a.magic);    /* the tile's segments */
+        const uint32_t len0 = cut.len0, nseg = cut.nseg, nblk = cut.nblk;
 
         /* 1. p of this tile; the next tile's loads */
         float pv[G];
@@ -130,33 +119,8 @@ __global__ __launch_bounds__(kBlankerThreads) void k_blanker(BlankerArgs a)
                 zc[g] = a.z[(long long)(g0 + g) * a.z_stride + mn];
         __syncthreads();
 
-        /* 2. the segment sums */
-        const bool few = nseg <= 64u;
-        for (int gg = 0; gg < (few ? 1 : ng); ++gg) {
-            const int g = few ? tid >> 6 : gg;
-            const uint32_t k = few ? (uint32_t)tid & 63u : (uint32_t)tid;
-            if (g < ng && k < nseg) {
-                const uint32_t start = k ? len0 + (k - 1u) * B : 0u;
-                const uint32_t len = k ? (cnt - start < B ? cnt - start : B) : len0;
-                float s = k ? 0.0f : ssum[par][g];
-                const float *p = sp[g] + start;
-                uint32_t i = 0;
-                for (; i + 4u <= len; i += 4u) {
-                    const float p0 = p[i], p1 = p[i + 1], p2 = p[i + 2], p3 = p[i + 3];
-                    s = s + p0;
-                    s = s + p1;
-                    s = s + p2;
-                    s = s + p3;
-                }
-                for (; i < len; ++i)
-                    s = s + p[i];
-                const bool ends = k ? len == B : done0 != 0u;
-                if (ends)
-                    sl[g][k] = s * a.invB;
-                if (k == nseg - 1u)
-                    ssum[par ^ 1][g] = ends ? 0.0f : s;
-            }
-        }
+        /* 2. the segment sums: sp -> sl, ssum */
+        meter_sums<G, TT>(cut, B, a.invB, tid, ng, par, sp, sl, ssum);
         __syncthreads();
 
         /* 3. the ref chain over the segments; the tile before's count of blanked outputs */
@@ -183,7 +147,7 @@ __global__ __launch_bounds__(kBlankerThreads) void k_blanker(BlankerArgs a)
         /* 4. the triggers: a ballot per wave is a word of the bitmap */
         {
             const uint32_t i = (uint32_t)tid;
-            const uint32_t k = !in || i < len0 ? 0u : 1u + blanker_div(i - len0, B, a.magic);
+            const uint32_t k = !in || i < len0 ? 0u : 1u + meter_div<TT>(i - len0, B, a.magic);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 if (g >= ng)
@@ -263,7 +227,7 @@ __global__ __launch_bounds__(kBlankerThreads) void k_blanker(BlankerArgs a)
             if (lane == 0)
                 sbl[g][wave] = (uint32_t)__popcll(word);
         }
-        ph = rem ? tail : (done0 ? 0u : ph + len0);
+        ph = meter_next_phase(cut, ph);
         /* the next tile's step 1 writes sp alone, which nobody reads any more; its barriers come before sl, slim, the
          * partial sums, the bitmap's other buffer and sbl are written or read again */
     }
@@ -299,7 +263,7 @@ hipError_t launch_blanker(const BlankerArgs &a, hipStream_t s)
     if (a.n <= 0 || a.nrx <= 0 || a.nrx > kBlankerMaxRx || a.z_stride < a.n || a.out_stride < a.n || !a.z || !a.out ||
         !a.rx || !a.old || !a.new_state || !a.old_hist || !a.new_hist || !a.old_bits || !a.new_bits || a.B < 1u ||
         a.B > (uint32_t)kBlankerMaxBlock || a.ph0 >= a.B || a.W > (uint32_t)kBlankerMaxGuard || a.D < a.W ||
-        a.D - a.W > (uint32_t)kBlankerMaxRamp || a.magic != ((1u << kBlankerDivShift) + a.B - 1u) / a.B)
+        a.D - a.W > (uint32_t)kBlankerMaxRamp || a.magic != meter_magic(a.B))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)((a.nrx + kBlankerGroup - 1) / kBlankerGroup));
     hipLaunchKernelGGL(k_blanker, grid, dim3(kBlankerThreads), 0, s, a);

@@ -11,9 +11,7 @@
  */
 #include "ddc_stage.h"
 #include "ddc_denoise.h"
-#include "ddc_spectrum.h"
 
-#include <cmath>
 #include <cstring>
 
 using namespace pddc;
@@ -21,7 +19,7 @@ using namespace pddc;
 struct pddc_denoise : StageBase {
     PDDC_LOCAL ~pddc_denoise() = default;
     pddc_denoise_params par{};
-    DevBuf<float> window, twiddles;
+    FrameTables tables;
     RxTable<DenoiseRx> table;                       /* flags: kDenoiseHold, and kDenoiseRestart as the first-frame mark */
     Carried<float> carry;                           /* [nrx][nfft]                                                 */
     Carried<float> pend;                            /* [nrx][hop]                                                  */
@@ -73,9 +71,8 @@ int pddc_denoise_create(pddc_denoise **out, int device, int nrx, const pddc_deno
         return pddc_set_error_(PDDC_EINVAL, "denoise: eps %g (finite, > 0)", (double)par->eps);
     if (!window)
         return pddc_set_error_(PDDC_EINVAL, "denoise: null window");
-    for (int i = 0; i < par->nfft; ++i)
-        if (!std::isfinite(window[i]))
-            return pddc_set_error_(PDDC_EINVAL, "denoise: window[%d] is not finite", i);
+    if (const int i = FrameTables::bad_window(window, par->nfft); i >= 0)
+        return pddc_set_error_(PDDC_EINVAL, "denoise: window[%d] is not finite", i);
     for (int j = 0; j < nrx; ++j)
         if (!denoise_rx_ok(rx[j].mode, rx[j].beta, rx[j].gmin, rx[j].alpha, rx[j].flags))
             return pddc_set_error_(PDDC_EINVAL, "denoise: receiver %d: mode %u, beta %g (finite, > 0), gmin %g (0 .. 1), alpha %g (0 <= alpha < 1), flags 0x%x",
@@ -86,10 +83,7 @@ int pddc_denoise_create(pddc_denoise **out, int device, int nrx, const pddc_deno
         /* every receiver's next completed frame is a first frame */
         for (int j = 0; j < nrx; ++j)
             s.table.host.push_back(DenoiseRx{ rx[j].mode, rx[j].beta, rx[j].gmin, rx[j].alpha, rx[j].flags | kDenoiseRestart });
-        std::vector<float> tw((size_t)spectrum_twiddle_len(par->nfft));
-        spectrum_build_twiddles(par->nfft, tw.data());
-        PDDC_TRY(s.window.alloc_copy(std::vector<float>(window, window + nfft)));
-        PDDC_TRY(s.twiddles.alloc_copy(tw));
+        PDDC_TRY(s.tables.alloc(par->nfft, window));
         PDDC_TRY(s.table.alloc());
         PDDC_TRY(s.carry.alloc((size_t)nrx * nfft));
         PDDC_TRY(s.pend.alloc((size_t)nrx * (size_t)par->hop));
@@ -158,8 +152,8 @@ int pddc_denoise_process(pddc_denoise *s, const void *d_x, size_t n, size_t x_st
     a.down = s->par.down;
     a.nmin = s->par.nmin;
     a.eps = s->par.eps;
-    a.window = s->window.get();
-    a.twiddles = s->twiddles.get();
+    a.window = s->tables.window.get();
+    a.twiddles = s->tables.twiddles.get();
     a.old_carry = s->carry.old();
     a.new_carry = s->carry.next();
     a.old_ola = s->ola.old();

@@ -9,7 +9,8 @@
  *                  in LDS; the hop a frame finishes goes to out.  One launch per batch; no spectrum in global memory, no
  *                  atomics, nothing cleared.
  *
- * Transform: the Stockham passes of ddc_fft_dev.h with the scope's radices (ddc_scope.hip): N = 256 is 16 x 16 with 16
+ * Transform: the Stockham passes of ddc_fft_dev.h (fft_load, fft_bfly, fft_put) with FramePlan's radices, the scope's;
+ * dn_fft below composes them.  That header stays above this file's contraction pragma.  N = 256 is 16 x 16 with 16
  * threads per receiver and four receivers per block, N = 512 is 8 x 8 x 8 and N = 1024 16 x 16 x 4 with 64 threads and
  * one receiver.  A thread's loads are its first butterfly (samples t + r TS), and the bins the last pass leaves in a
  * thread (t + m TS) are again a first butterfly's inputs: the inverse is the same passes on (im, re), its real part is
@@ -30,62 +31,29 @@
 
 namespace pddc {
 
-template <int N> struct DenoisePlan;
-template <> struct DenoisePlan<256> { static constexpr int R1 = 16, R2 = 16, R3 = 1, G = 4; };
-template <> struct DenoisePlan<512> { static constexpr int R1 = 8, R2 = 8, R3 = 8, G = 1; };
-template <> struct DenoisePlan<1024> { static constexpr int R1 = 16, R2 = 16, R3 = 4, G = 1; };
-
-/* the image the first pass (radix S) writes: the low bits of a row XOR the row's number; 0: plain */
-template <int S> __device__ __forceinline__ int dn_swz(int i) { return S ? i ^ ((i / (S ? S : 1)) & (S - 1)) : i; }
-
-/* a pass after the first: the thread's N / R / TS butterflies from the image, twiddled and transformed */
-template <int N, int TS, int R, int NS, int SWZ>
-__device__ __forceinline__ void dn_bfly(const float2 *buf, const float2 *tw, int t, float2 (&v)[N / R / TS][R])
-{
-#pragma unroll
-    for (int b = 0; b < N / R / TS; ++b) {
-        const int j = t + b * TS;
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            v[b][r] = buf[dn_swz<SWZ>(j + r * (N / R))];
-    }
-#pragma unroll
-    for (int b = 0; b < N / R / TS; ++b) {
-        const int k = (t + b * TS) & (NS - 1);
-#pragma unroll
-        for (int r = 1; r < R; ++r)
-            v[b][r] = cmulw(v[b][r], tw[(r - 1) * NS + k]);
-        fft_reg<R>(v[b]);
-    }
-}
-
 /* The N-point transform of a[r] = point t + r TS; X[m] = bin t + m TS.  It writes the group's image and ends with reads
  * of it: the caller puts a barrier in front of the next call. */
-template <int N> __device__ __forceinline__ void dn_fft(float2 (&a)[DenoisePlan<N>::R1], float2 *buf, const float2 *tw2, int t)
+template <int N> __device__ __forceinline__ void dn_fft(float2 (&a)[FramePlan<N>::R1], float2 *buf, const float2 *tw2, int t)
 {
-    using Plan = DenoisePlan<N>;
+    using Plan = FramePlan<N>;
     constexpr int R1 = Plan::R1, R2 = Plan::R2, R3 = Plan::R3, TS = N / R1;
     fft_reg<R1>(a);
 #pragma unroll
     for (int r = 0; r < R1; ++r)
-        buf[dn_swz<R1>(t * R1 + r)] = a[fft_pos<R1>(r)];
+        buf[fft_swz<R1>(t * R1 + r)] = a[fft_pos<R1>(r)];
     __syncthreads();
     float2 v[N / R2 / TS][R2];
-    dn_bfly<N, TS, R2, R1, R1>(buf, tw2, t, v);
+    fft_load<N, TS, R2, R1>(buf, t, v);
+    fft_bfly<N, TS, R2, R1>(tw2, t, v);
     if constexpr (R3 > 1) {
         constexpr int NB = N / R3 / TS;
         const float2 *tw3 = tw2 + (R2 - 1) * R1;
         __syncthreads();                          /* everybody has read */
-#pragma unroll
-        for (int b = 0; b < N / R2 / TS; ++b) {
-            const int j = t + b * TS, k = j & (R1 - 1), j0 = (j - k) * R2 + k;
-#pragma unroll
-            for (int r = 0; r < R2; ++r)
-                buf[j0 + r * R1] = v[b][fft_pos<R2>(r)];
-        }
+        fft_put<N, TS, R2, R1, 0>(buf, t, v);
         __syncthreads();
         float2 y[NB][R3];
-        dn_bfly<N, TS, R3, R1 * R2, 0>(buf, tw3, t, y);
+        fft_load<N, TS, R3, 0>(buf, t, y);
+        fft_bfly<N, TS, R3, R1 * R2>(tw3, t, y);
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -102,9 +70,9 @@ template <int N> __device__ __forceinline__ void dn_fft(float2 (&a)[DenoisePlan<
 #pragma clang fp contract(off)
 
 template <int N>
-__global__ __launch_bounds__(N / DenoisePlan<N>::R1 * DenoisePlan<N>::G) void k_denoise(DenoiseArgs p)
+__global__ __launch_bounds__(N / FramePlan<N>::R1 * FramePlan<N>::G) void k_denoise(DenoiseArgs p)
 {
-    using Plan = DenoisePlan<N>;
+    using Plan = FramePlan<N>;
     constexpr int R1 = Plan::R1, G = Plan::G;
     constexpr int TS = N / R1, STRIDE = N + (G > 1 ? 16 : 0);
     constexpr int NH = R1 / 2;                    /* a thread's bins t + m TS up to N/2: m < NH, and m == NH in thread 0 */
@@ -280,7 +248,7 @@ __global__ __launch_bounds__(N / DenoisePlan<N>::R1 * DenoisePlan<N>::G) void k_
 /* ------------------------------------------------------------------------ */
 template <int N> static hipError_t launch_denoise_t(const DenoiseArgs &a, hipStream_t s)
 {
-    constexpr int G = DenoisePlan<N>::G, NT = N / DenoisePlan<N>::R1 * G;
+    constexpr int G = FramePlan<N>::G, NT = N / FramePlan<N>::R1 * G;
     hipLaunchKernelGGL(k_denoise<N>, dim3((unsigned)((a.nrx + G - 1) / G)), dim3(NT), 0, s, a);
     return hipGetLastError();
 }

@@ -1,6 +1,9 @@
 /*
- * ddc_dev.h -- device-side helpers shared by the kernel translation units (ddc_kernels.hip, ddc_fir_i8.hip, ddc_tuner.hip,
- * ddc_demod.hip, and through ddc_packed.h the panorama and the channelizer).
+ * ddc_dev.h -- device-side helpers shared by the kernel translation units (ddc_kernels.hip, ddc_fir_i8.hip and every stage's
+ * ddc_<stage>.hip, directly or through ddc_packed.h, ddc_fft_dev.h or ddc_meter_dev.h): vector types, the packed samples'
+ * byte selectors, the NCO's sine and cosine, PCM rounding.  What only some kernels share lives beside it: the in-workgroup
+ * transform in ddc_fft_dev.h (panorama, channelizer, scope, noise reduction), the block power meter in ddc_meter_dev.h
+ * (squelch, blanker).
  * Internal; gfx950 only.
  */
 #ifndef PDDC_DDC_DEV_H

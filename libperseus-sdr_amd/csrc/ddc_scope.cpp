@@ -9,9 +9,6 @@
  */
 #include "ddc_stage.h"
 #include "ddc_scope.h"
-#include "ddc_spectrum.h"
-
-#include <cmath>
 
 using namespace pddc;
 
@@ -19,7 +16,7 @@ struct pddc_scope : StageBase {                     /* nrx: the slots */
     PDDC_LOCAL ~pddc_scope() = default;
     int nsrc = 0, nfft = 0, hop = 0, avg = 0;
     uint32_t flags = 0;
-    DevBuf<float> window, twiddles;
+    FrameTables tables;
     RxTable<ScopeSlot> table;
     Carried<float2> carry;                          /* [nslots][nfft]                                              */
     Carried<float> part;                            /* [nslots][nfft]                                              */
@@ -64,9 +61,8 @@ int pddc_scope_create(pddc_scope **out, int device, int nsrc, int nslots, const 
         return pddc_set_error_(PDDC_EINVAL, "scope: unknown flags 0x%x", flags);
     if (!window)
         return pddc_set_error_(PDDC_EINVAL, "scope: null window");
-    for (int i = 0; i < nfft; ++i)
-        if (!std::isfinite(window[i]))
-            return pddc_set_error_(PDDC_EINVAL, "scope: window[%d] is not finite", i);
+    if (const int i = FrameTables::bad_window(window, nfft); i >= 0)
+        return pddc_set_error_(PDDC_EINVAL, "scope: window[%d] is not finite", i);
     for (int j = 0; j < nslots; ++j)
         if (rows[j] < -1 || rows[j] >= nsrc)
             return pddc_set_error_(PDDC_EINVAL, "scope: slot %d: row %d (-1: off, 0 .. %d)", j, rows[j], nsrc - 1);
@@ -78,10 +74,7 @@ int pddc_scope_create(pddc_scope **out, int device, int nsrc, int nslots, const 
         s.flags = flags;
         for (int j = 0; j < nslots; ++j)
             s.table.host.push_back(ScopeSlot{ rows[j], 0u });
-        std::vector<float> tw((size_t)spectrum_twiddle_len(nfft));
-        spectrum_build_twiddles(nfft, tw.data());
-        PDDC_TRY(s.window.alloc_copy(std::vector<float>(window, window + nfft)));
-        PDDC_TRY(s.twiddles.alloc_copy(tw));
+        PDDC_TRY(s.tables.alloc(nfft, window));
         PDDC_TRY(s.table.alloc());
         PDDC_TRY(s.carry.alloc((size_t)nslots * (size_t)nfft));
         return s.part.alloc((size_t)nslots * (size_t)nfft);
@@ -152,8 +145,8 @@ int pddc_scope_process(pddc_scope *s, const void *d_z, size_t n, size_t z_stride
     a.new_carry = s->carry.next();
     a.old_part = s->part.old();
     a.new_part = s->part.next();
-    a.window = s->window.get();
-    a.twiddles = s->twiddles.get();
+    a.window = s->tables.window.get();
+    a.twiddles = s->tables.twiddles.get();
     a.hop = s->hop;
     a.avg = s->avg;
     a.clen = (int)(s->N - S0 * (uint64_t)s->hop);

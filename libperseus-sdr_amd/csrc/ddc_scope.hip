@@ -9,8 +9,10 @@
  *                carried partial line.  Behind the items' blocks one block per slot copies the carried samples.  One
  *                launch per batch; no atomics, no scratch, nothing cleared.
  *
- * Transform: the Stockham passes of ddc_fft_dev.h with the radices below; a group has N / R1 threads, so that the loads
- * of a thread ARE its first butterfly (samples t + r N/R1): the first pass reads no LDS.  N = 256 is 16 x 16 with 16
+ * Transform: the Stockham passes of ddc_fft_dev.h with FramePlan's radices, the noise reduction's too.  scope_swz,
+ * scope_bfly and scope_put below are this file's own copies of that header's fft_swz, fft_load + fft_bfly and fft_put, kept
+ * on purpose: on the shared steps k_scope gave other bits at every size with three passes (NOTEBOOK R24.1).  A group has
+ * N / R1 threads, so that the loads of a thread ARE its first butterfly (samples t + r N/R1): the first pass reads no LDS.  N = 256 is 16 x 16 with 16
  * threads per segment and N = 512 is 8 x 8 x 8 with 64; a block of N = 256 holds four items, so every wave is full;
  * from N = 512 on a block is one item of 64, 64, 128 and 256 threads.  The first pass's image is XOR-swizzled (its 16- or
  * 8-point rows would otherwise put a lane group on one bank set), the later images are plain.  Twiddles and window are
@@ -30,13 +32,6 @@
 #include "ddc_fft_dev.h"
 
 namespace pddc {
-
-template <int N> struct ScopePlan;
-template <> struct ScopePlan<256> { static constexpr int R1 = 16, R2 = 16, R3 = 1, G = 4; };
-template <> struct ScopePlan<512> { static constexpr int R1 = 8, R2 = 8, R3 = 8, G = 1; };
-template <> struct ScopePlan<1024> { static constexpr int R1 = 16, R2 = 16, R3 = 4, G = 1; };
-template <> struct ScopePlan<2048> { static constexpr int R1 = 16, R2 = 16, R3 = 8, G = 1; };
-template <> struct ScopePlan<4096> { static constexpr int R1 = 16, R2 = 16, R3 = 16, G = 1; };
 
 /* the image the first pass (radix S) writes: the low bits of a row XOR the row's number; 0: plain */
 template <int S> __device__ __forceinline__ int scope_swz(int i) { return S ? i ^ ((i / (S ? S : 1)) & (S - 1)) : i; }
@@ -91,9 +86,9 @@ __device__ __forceinline__ void scope_add(const float2 (&v)[N / R / TS][R], bool
 }
 
 template <int N>
-__global__ __launch_bounds__(N / ScopePlan<N>::R1 * ScopePlan<N>::G) void k_scope(ScopeArgs p)
+__global__ __launch_bounds__(N / FramePlan<N>::R1 * FramePlan<N>::G) void k_scope(ScopeArgs p)
 {
-    using Plan = ScopePlan<N>;
+    using Plan = FramePlan<N>;
     constexpr int R1 = Plan::R1, R2 = Plan::R2, R3 = Plan::R3, G = Plan::G;
     constexpr int TS = N / R1, NT = TS * G;
     constexpr int STRIDE = N + (G > 1 ? 16 : 0);  /* neighbouring groups of a wave on different banks */
@@ -208,7 +203,7 @@ __global__ __launch_bounds__(N / ScopePlan<N>::R1 * ScopePlan<N>::G) void k_scop
 }
 
 /* ------------------------------------------------------------------------ */
-int scope_items_per_block(int nfft) { return nfft == 256 ? ScopePlan<256>::G : 1; }
+int scope_items_per_block(int nfft) { return nfft == 256 ? FramePlan<256>::G : 1; }
 
 uint64_t scope_blocks(int nfft, int nslots, int nunits)
 {
@@ -219,7 +214,7 @@ uint64_t scope_blocks(int nfft, int nslots, int nunits)
 
 template <int N> static hipError_t launch_scope_t(const ScopeArgs &a, hipStream_t s)
 {
-    constexpr int NT = N / ScopePlan<N>::R1 * ScopePlan<N>::G;
+    constexpr int NT = N / FramePlan<N>::R1 * FramePlan<N>::G;
     const uint64_t blocks = scope_blocks(N, a.nslots, a.nunits);
     if (!blocks)
         return hipErrorInvalidValue;

@@ -26,7 +26,7 @@
 
 namespace pddc {
 
-/* radices of the passes of size n: 16, 16, r2[, r3]; below the panorama's sizes (the scope, ddc_scope.hip) 16, 16 and
+/* radices of the passes of size n: 16, 16, r2[, r3]; below the panorama's sizes (FramePlan, ddc_fft_dev.h) 16, 16 and
  * 8, 8, 8 */
 static void spec_radices(int n, int (&r)[4], int &np)
 {
@@ -145,13 +145,13 @@ __global__ __launch_bounds__(N / 16 < 256 ? N / 16 : 256) void k_spectrum(Spectr
         if (seg + gridDim.x < p.nseg)
             load_seg(seg + gridDim.x);
         __syncthreads();
-        spec_pass<N, NT, 16, 1, 0, 1, false, PEAK>(buf, tw + TW1, acc, pk);
-        spec_pass<N, NT, 16, 16, 1, 2, false, PEAK>(buf, tw + TW1, acc, pk);
+        spec_pass<N, NT, 16, 1, kImgLoaders, 16, false, PEAK>(buf, tw + TW1, acc, pk);
+        spec_pass<N, NT, 16, 16, 16, 0, false, PEAK>(buf, tw + TW1, acc, pk);
         if (R3 > 1) {
-            spec_pass<N, NT, R2, 256, 2, 2, false, PEAK>(buf, tw + TW2, acc, pk);
-            spec_pass<N, NT, (R3 > 1 ? R3 : 4), 256 * R2, 2, 2, true, PEAK>(buf, tw + TW3, acc, pk);
+            spec_pass<N, NT, R2, 256, 0, 0, false, PEAK>(buf, tw + TW2, acc, pk);
+            spec_pass<N, NT, (R3 > 1 ? R3 : 4), 256 * R2, 0, 0, true, PEAK>(buf, tw + TW3, acc, pk);
         } else {
-            spec_pass<N, NT, R2, 256, 2, 2, true, PEAK>(buf, tw + TW2, acc, pk);
+            spec_pass<N, NT, R2, 256, 0, 0, true, PEAK>(buf, tw + TW2, acc, pk);
         }
     }
     /* the block's row of partial sums: thread j's bins are j + b NT + r N/R of the last pass */

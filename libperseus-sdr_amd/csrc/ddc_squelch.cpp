@@ -170,7 +170,7 @@ int pddc_squelch_process(pddc_squelch *s, const void *d_z, const void *d_a, size
     a.hang = (uint32_t)s->par.hang;
     a.R = (uint32_t)s->par.ramp;
     a.ph0 = (uint32_t)(s->N % (uint64_t)s->par.block);
-    a.magic = ((1u << kSquelchDivShift) + a.B - 1u) / a.B;
+    a.magic = meter_magic(a.B);
     a.invB = s->invB;
     a.invR = s->invR;
     a.up = s->par.up;

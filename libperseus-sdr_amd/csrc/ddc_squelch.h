@@ -18,7 +18,6 @@ static constexpr int kSquelchMaxBlock = 4096;           /* B                    
 static constexpr int kSquelchMaxRamp = 65536;           /* R                                                       */
 static constexpr int kSquelchMaxCount = 65535;          /* attack, hang                                            */
 static constexpr uint32_t kSquelchGate = 1u, kSquelchRelative = 2u;   /* PDDC_SQL_GATE, PDDC_SQL_RELATIVE          */
-static constexpr int kSquelchDivShift = 20;             /* x / B = (x * magic) >> 20 for x < 2 TT, B < TT          */
 
 /* one receiver as the kernel sees it */
 struct SquelchRx {
@@ -53,7 +52,7 @@ struct SquelchArgs {
     SquelchState *new_state;  /* [nrx] written by this launch                                                   */
     uint32_t B, attack, hang, R;
     uint32_t ph0;             /* N mod B: where in its block the launch's first sample lies                     */
-    uint32_t magic;           /* ceil(2^20 / B)                                                                 */
+    uint32_t magic;           /* meter_magic(B)                                                                 */
     float invB, invR, up;
     uint32_t fresh;           /* the carried records are not read: the create values                            */
     uint32_t clear_peak;      /* the carried peak is taken as 0                                                 */

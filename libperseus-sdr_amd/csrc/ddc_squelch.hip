@@ -10,7 +10,7 @@
  * Walk: a block takes G = 4 consecutive receivers and walks the whole batch tile by tile, TT = 256 samples a time.  The
  * block grid B of the level meter is common to the receivers, so a tile is cut into the same SEGMENTS for all of them:
  * segment 0 ends the block under way (or the tile), the following ones are whole blocks, the last may be the start of
- * one.  At most TT segments (B = 1).
+ * one.  At most TT segments (B = 1).  The cut, step 2, the division by B and the next tile's phase: ddc_meter_dev.h.
  *   1. thread i takes sample i of the tile for one receiver after the other (coalesced 8-byte loads of z and 4-byte
  *      loads of a, those of the NEXT tile issued here and held in registers); p goes to sp[g][i] in LDS.
  *   2. one thread per receiver and segment adds the segment's p in ascending m -- segment 0 continues the carried partial
@@ -32,17 +32,11 @@
  * count, which the host checked against blk_stride; the LDS rows by samples < TT and segments < TT.
  */
 #include "ddc_squelch.h"
-#include "ddc_dev.h"
+#include "ddc_meter_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace pddc {
-
-/* x / B for x < 2 TT: B >= TT has at most one whole block in reach */
-__device__ __forceinline__ uint32_t squelch_div(uint32_t x, uint32_t B, uint32_t magic)
-{
-    return B >= (uint32_t)kSquelchTile ? (x >= B ? 1u : 0u) : (x * magic) >> kSquelchDivShift;
-}
 
 __global__ __launch_bounds__(kSquelchThreads) void k_squelch(SquelchArgs a)
 {
@@ -103,14 +97,8 @@ __global__ __launch_bounds__(kSquelchThreads) void k_squelch(SquelchArgs a)
         const uint32_t cnt = (uint32_t)(a.n - o < TT ? a.n - o : TT);
         const long long m = o + tid;
         const bool in = (uint32_t)tid < cnt;
-        /* the tile's segments */
-        const uint32_t len0 = cnt < B - ph ? cnt : B - ph;
-        const uint32_t rem = cnt - len0;
-        const uint32_t full = squelch_div(rem, B, a.magic);
-        const uint32_t tail = rem - full * B;
-        const uint32_t done0 = ph + len0 == B ? 1u : 0u;
-        const uint32_t nseg = 1u + full + (tail ? 1u : 0u);
-        const uint32_t nblk = done0 + full;
+        const MeterCut cut = meter_cut<TT>(cnt, ph, B, a.magic);    /* the tile's segments */
+        const uint32_t len0 = cut.len0, nseg = cut.nseg, nblk = cut.nblk;
 
         /* 1. p of this tile; the next tile's loads */
         float av[G];
@@ -127,33 +115,8 @@ __global__ __launch_bounds__(kSquelchThreads) void k_squelch(SquelchArgs a)
             }
         __syncthreads();
 
-        /* 2. the segment sums */
-        const bool few = nseg <= 64u;
-        for (int gg = 0; gg < (few ? 1 : ng); ++gg) {
-            const int g = few ? tid >> 6 : gg;
-            const uint32_t k = few ? (uint32_t)tid & 63u : (uint32_t)tid;
-            if (g < ng && k < nseg) {
-                const uint32_t start = k ? len0 + (k - 1u) * B : 0u;
-                const uint32_t len = k ? (cnt - start < B ? cnt - start : B) : len0;
-                float s = k ? 0.0f : ssum[par][g];
-                const float *p = sp[g] + start;
-                uint32_t i = 0;
-                for (; i + 4u <= len; i += 4u) {
-                    const float p0 = p[i], p1 = p[i + 1], p2 = p[i + 2], p3 = p[i + 3];
-                    s = s + p0;
-                    s = s + p1;
-                    s = s + p2;
-                    s = s + p3;
-                }
-                for (; i < len; ++i)
-                    s = s + p[i];
-                const bool ends = k ? len == B : done0 != 0u;
-                if (ends)
-                    sl[g][k] = s * a.invB;
-                if (k == nseg - 1u)
-                    ssum[par ^ 1][g] = ends ? 0.0f : s;
-            }
-        }
+        /* 2. the segment sums: sp -> sl, ssum */
+        meter_sums<G, TT>(cut, B, a.invB, tid, ng, par, sp, sl, ssum);
         __syncthreads();
 
         /* 3. the state machine over the segments */
@@ -195,7 +158,7 @@ __global__ __launch_bounds__(kSquelchThreads) void k_squelch(SquelchArgs a)
         /* 4. the samples' gain, the stores */
         if (in) {
             const uint32_t i = (uint32_t)tid;
-            const uint32_t k = i < len0 ? 0u : 1u + squelch_div(i - len0, B, a.magic);
+            const uint32_t k = i < len0 ? 0u : 1u + meter_div<TT>(i - len0, B, a.magic);
             const uint32_t off = k ? i - (len0 + (k - 1u) * B) + 1u : i + 1u;
             for (int g = 0; g < ng; ++g) {
                 const uint32_t w = sc[g][k];
@@ -217,7 +180,7 @@ __global__ __launch_bounds__(kSquelchThreads) void k_squelch(SquelchArgs a)
             }
         }
         kb0 += nblk;
-        ph = rem ? tail : (done0 ? 0u : ph + len0);
+        ph = meter_next_phase(cut, ph);
         /* the next tile's step 1 writes sp alone, which nobody reads any more; its barrier comes before sl, sc, so and
          * the partial sums are written again */
     }
@@ -240,7 +203,7 @@ hipError_t launch_squelch(const SquelchArgs &a, hipStream_t s)
     if (a.n <= 0 || a.nrx <= 0 || a.nrx > kSquelchMaxRx || a.z_stride < a.n || a.a_stride < a.n || a.out_stride < a.n ||
         !a.z || !a.a || !a.out || !a.rx || !a.old || !a.new_state || a.B < 1u || a.B > (uint32_t)kSquelchMaxBlock ||
         a.ph0 >= a.B || a.R < 1u || a.R > (uint32_t)kSquelchMaxRamp || a.attack < 1u || a.hang < 1u ||
-        a.magic != ((1u << kSquelchDivShift) + a.B - 1u) / a.B)
+        a.magic != meter_magic(a.B))
         return hipErrorInvalidValue;
     if ((a.level || a.state) && (unsigned long long)a.blk_stride < ((unsigned long long)a.ph0 + (unsigned long long)a.n) / a.B)
         return hipErrorInvalidValue;

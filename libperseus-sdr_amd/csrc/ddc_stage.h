@@ -1,8 +1,8 @@
 /*
  * ddc_stage.h -- what the host files of the per-receiver stages (blanker, receiver filter, demodulator, squelch,
  * adaptive filter, audio, and the mixer behind them) share: device buffers that free themselves, the pair of carried records a batch reads and
- * writes in turn, the receiver table with its upload, and the common ends of create / destroy / reset / set_rx /
- * process / read.  A stage's own file keeps its parameters, its table entries, its kernel arguments and its counters.
+ * writes in turn, the receiver table with its upload, the window and twiddles of the stages that transform frames (scope,
+ * noise reduction), and the common ends of create / destroy / reset / set_rx / process / read.  A stage's own file keeps its parameters, its table entries, its kernel arguments and its counters.
  * Host only (no kernel includes it); internal, nothing here is exported.
  */
 #ifndef PDDC_DDC_STAGE_H
@@ -11,6 +11,7 @@
 #include "ddc_host.h"
 #include "ddc_stage_checks.h"
 
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -48,6 +49,31 @@ public:
         return PDDC_OK;
     }
     T *get() const { return p_; }
+};
+
+/* The window and the twiddle table of a stage that transforms frames of nfft samples (the scope, the noise reduction:
+ * the framed transform of ddc_fft_dev.h), uploaded once, at create.  The twiddles are the panorama's, ddc_spectrum.h: */
+int spectrum_twiddle_len(int nfft);
+void spectrum_build_twiddles(int nfft, float *tw);
+
+struct FrameTables {
+    DevBuf<float> window, twiddles;
+
+    /* the first window value that is not finite, or -1: create tests it before it asks for a device, with its own message */
+    static int bad_window(const float *w, int nfft)
+    {
+        for (int i = 0; i < nfft; ++i)
+            if (!std::isfinite(w[i]))
+                return i;
+        return -1;
+    }
+    int alloc(int nfft, const float *w)
+    {
+        std::vector<float> tw((size_t)spectrum_twiddle_len(nfft));
+        spectrum_build_twiddles(nfft, tw.data());
+        PDDC_TRY(window.alloc_copy(std::vector<float>(w, w + nfft)));
+        return twiddles.alloc_copy(tw);
+    }
 };
 
 /* what a stage carries from batch to batch, twice: a launch reads old() and writes next(); once it was accepted, turn().

@@ -1,7 +1,8 @@
 /*
  * ddc_stage_checks.h -- the arithmetic behind the argument tests of the per-receiver stages' process() (ddc_stage.h):
- * pointers, capacities, the bytes a set of rows spans, whether two spans meet, and the squelch's block count.  No HIP
- * header: a host compiler builds it alone (tests/stage_checks_test.cpp).  Internal; nothing here is exported.
+ * pointers, capacities, the bytes a set of rows spans, whether two spans meet, the squelch's block count and the block
+ * meter's division constant.  No HIP header: a host compiler builds it alone (tests/stage_checks_test.cpp).  Internal;
+ * nothing here is exported.
  */
 #ifndef PDDC_DDC_STAGE_CHECKS_H
 #define PDDC_DDC_STAGE_CHECKS_H
@@ -33,6 +34,11 @@ inline bool ranges_overlap(const void *p, size_t bytes, const void *q, size_t qb
 
 /* blocks of B samples that n samples after `before` complete */
 inline uint64_t squelch_blocks(uint64_t B, uint64_t before, uint64_t n) { return (before + n) / B - before / B; }
+
+/* The block meter's division (ddc_meter_dev.h; squelch and blanker): x / B = (x * meter_magic(B)) >> kMeterDivShift for
+ * x < 512 (two tiles) and B < 256 (a tile).  Host and device; a launcher refuses arguments whose magic is another number. */
+static constexpr int kMeterDivShift = 20;
+constexpr uint32_t meter_magic(uint32_t B) { return ((1u << kMeterDivShift) + B - 1u) / B; }
 
 } // namespace pddc
 #endif

@@ -157,9 +157,10 @@ def interleaved_rx(K):
 
 
 def param_sets(TT):
-    """(B, W, R) of the GPU parity test: D = 8; B = 1 with D = 1; D = 0; no guard; the largest D; the last one completes
-    no block within 3000 samples, so nothing triggers and out is the delayed input"""
-    return [(48, 3, 5), (1, 1, 0), (TT, 0, 0), (64, 0, 7), (1000, 128, 128), (4096, 2, 2)]
+    """(B, W, R) of the GPU parity test: D = 8; B = 1 with D = 1; B = 3, which cuts a tile into more than 64 segments and
+    leaves a tail in it (no B that divides 256 does both), with D = 2; D = 0; no guard; the largest D; the last one
+    completes no block within 3000 samples, so nothing triggers and out is the delayed input"""
+    return [(48, 3, 5), (1, 1, 0), (3, 1, 1), (TT, 0, 0), (64, 0, 7), (1000, 128, 128), (4096, 2, 2)]
 
 
 # the GPU tests' inputs (tests/test_gpu_blanker.py; their preconditions are asserted in tests/test_blanker_cpu.py)

@@ -173,8 +173,9 @@ def interleaved_rx(K):
 
 
 def param_sets(TT):
-    """(B, attack, hang, R) of the GPU parity test; the last one completes no block within 3000 samples"""
-    return [(1, 1, 1, 1), (48, 2, 3, 37), (TT, 1, 2, 4096), (1000, 1, 1, 300), (4096, 1, 1, 8)]
+    """(B, attack, hang, R) of the GPU parity test; B = 3 cuts a tile into more than 64 segments and leaves a tail in it
+    (no B that divides 256 does both); the last one completes no block within 3000 samples"""
+    return [(1, 1, 1, 1), (3, 1, 2, 2), (48, 2, 3, 37), (TT, 1, 2, 4096), (1000, 1, 1, 300), (4096, 1, 1, 8)]
 
 
 def params(B, attack, hang, R, up=UP):

@@ -1,6 +1,7 @@
 /* tests/stage_checks_test.cpp -- the arithmetic behind the argument tests of the per-receiver stages' process()
  * (csrc/ddc_stage_checks.h: no HIP header, so a host compiler builds it alone): whether two byte ranges meet, the bytes a
- * set of rows spans, pointer alignment, and the squelch's completed blocks against a counting loop.
+ * set of rows spans, pointer alignment, the squelch's completed blocks against a counting loop, and the block meter's
+ * multiply-and-shift against the division.
  * usage: stage_checks_test   -> prints "ok: <checks> checks", exit 0; the first failed check is printed, exit 1 */
 #include <stdio.h>
 #include <stdlib.h>
@@ -94,6 +95,14 @@ static void test_squelch_blocks()
     }
 }
 
+/* every x a kernel divides (below two tiles of 256) by every B that takes the multiply (below a tile) */
+static void test_meter_magic()
+{
+    for (uint32_t B = 1; B < 256; ++B)
+        for (uint32_t x = 0; x < 512; ++x)
+            CHECK((x * meter_magic(B)) >> kMeterDivShift == x / B);
+}
+
 int main()
 {
     test_ranges_overlap();
@@ -101,6 +110,7 @@ int main()
     test_alignment();
     test_over_capacity();
     test_squelch_blocks();
+    test_meter_magic();
     printf("ok: %ld checks\n", checks);
     return 0;
 }

@@ -64,7 +64,7 @@ def reference(series, par):
 
 
 def test_bits_against_the_reference(pkg, dev, series):
-    """K = 1024, n = 3000, ON and OFF receivers and six thresholds interleaved; the six parameter sets (B, W, R), the last
+    """K = 1024, n = 3000, ON and OFF receivers and six thresholds interleaved; the seven parameter sets (B, W, R), the last
     of which completes no block: out and read() after the batch equal blanker_ref's."""
     TT = pkg.blanker_tile_outputs()
     for par in BR.param_sets(TT):

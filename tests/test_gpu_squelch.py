@@ -57,7 +57,7 @@ def series(dev):
 
 
 def test_bits_against_the_reference(pkg, dev, series):
-    """K = 1024, n = 3000, thresholds and flag sets interleaved receiver by receiver; the five parameter sets (B, attack,
+    """K = 1024, n = 3000, thresholds and flag sets interleaved receiver by receiver; the six parameter sets (B, attack,
     hang, R), the last of which completes no block: out, levels, states and read() after the batch equal squelch_ref's."""
     TT = pkg.squelch_tile_outputs()
     for par in SR.param_sets(TT):

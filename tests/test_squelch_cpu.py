@@ -177,7 +177,7 @@ def gpu_inputs():
 
 def test_gpu_inputs_exercise_the_gate(gpu_inputs):
     """Preconditions of tests/test_gpu_squelch.py, on the reference alone: over keyed_series(1024, 3000) every parameter
-    set that completes a block sees at least 100 open and 100 close events in total (the fifth, B = 4096, completes none
+    set that completes a block sees at least 100 open and 100 close events in total (the last, B = 4096, completes none
     and must leave everything as created), and at least one receiver's ramp is reversed before completing (0 < c < R at
     a decision change)."""
     z, a, rx = gpu_inputs
