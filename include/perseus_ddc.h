@@ -1046,6 +1046,92 @@ int pddc_denoise_delay(int nfft);
 /* frames of one block pass of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_denoise_tile_frames(void);
 
+/* ---- eq: per-receiver biquad cascades over the audio ---------------------------
+ * A stage behind the demodulator, the squelch, the adaptive filter or the noise reduction and in
+ * front of audio (it works behind audio, at 48 kHz, as well): per receiver a cascade of second-order
+ * sections that shapes the audio itself -- de-emphasis, an audio peak filter, a manual notch, hum
+ * notches, bass and treble, high and low cut.  Per batch it reads the receivers' real float32 series
+ * x_j[m] and gives out_j[m], n values out per n values in, no delay.
+ * All arithmetic is binary64: coefficients, states and every operation; input and output stay
+ * float32.  (A float32 cascade of a 20 Hz notch of Q 30 leaves a noise floor 63 dB below the
+ * output's peak; the binary64 cascade rounded once is within half a float32 ulp.)
+ * Fixed at create: nrx (1 .. 1024); S, the sections a receiver can have (1, 2, 4 or 8).
+ * Per receiver, changeable between batches with set_rx: nsec, 0 .. S, and nsec sections (b0, b1, b2,
+ * a1, a2), a0 = 1.  Each section must be stable: all five values finite, |a2| < 1 and
+ * |a1| < 1 + a2; a section that is not, nsec outside 0 .. S, an unknown flag, rx outside [0, nrx):
+ * PDDC_EINVAL with a message that names the section, nothing changed.
+ * Carried per receiver and section: two binary64 states s1, s2, 0 at create, reset and RESTART.
+ * Nothing else.
+ * Per sample m: v = (double)x[m]; for s = 0 .. nsec - 1, in this order:
+ *     y  = (b0 v) + s1
+ *     s1 = ((b1 v) - (a1 y)) + s2
+ *     s2 = (b2 v) - (a2 y)
+ *     v  = y
+ * every product and sum a separately rounded IEEE operation (no contraction, denormals kept): the
+ * transposed direct form II in the operation sequence of scipy.signal.sosfilt; out[m] = (float)v,
+ * rounded to nearest even.
+ * nsec = 0 is OFF: the output words are the input words, copied as 32-bit words without a
+ * conversion (-0.0 and NaN payloads survive).
+ * Sections s >= nsec are not run; a batch with n > 0 leaves their states 0, so a cascade that grows
+ * later starts those sections from rest.
+ * set_rx(j, nsec, sections, flags): from the next sample on, and the states are KEPT: no gap, the
+ * transient is the filter's own.  With PDDC_EQ_RESTART that receiver's states are taken as 0 (a mark
+ * the next batch with n > 0 honours; nothing on the device is cleared from the host).
+ * The bits of every output and every state depend on the receiver's series and its set_rx history
+ * alone: not on the cut into batches (batches of 0 included), nrx, j's index, the other receivers,
+ * S, strides, grid or tile sizes.  The same receiver in an S = 2 and an S = 8 object gives the same
+ * bits.
+ * Non-finite samples, in the receiver's own row alone (other rows keep their bits): sticky.  A NaN
+ * or an infinity in x[p] makes that receiver's states NaN or infinite from sample p on (an infinity
+ * turns NaN in s1 = (b1 v) - (a1 y) + s2 at the latest one sample later), states that are not finite
+ * stay so -- the recursion has no way back -- and every output after it is not finite.  OFF passes
+ * the words and has no states.  Recovery: set_rx with PDDC_EQ_RESTART in front of the first batch of
+ * good samples -- from that sample on the row is that of a receiver restarted there --, or reset.
+ * process(): a is [nrx][a_stride] and out [nrx][out_stride] float32, n values used per row.  Every
+ * argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned (4 bytes)
+ * pointer with work to do, PDDC_ECAPACITY when a stride is below n; d_out == d_a with equal strides
+ * is allowed (in place), any other overlap of out with a is PDDC_EINVAL; n = 0 is valid and does
+ * nothing.  State moves only after the launch was accepted.  Stream-ordered; one stream per object,
+ * one thread at a time.
+ * read_state(): s1, s2 [nrx][S][2] as the last accepted batch left them (it waits for it).
+ * design(): one section in double (host arithmetic, no device): the RBJ cookbook's LOWPASS, HIGHPASS,
+ * BANDPASS (0 dB peak), NOTCH, PEAK (gain_db at f), LOWSHELF and HIGHSHELF (gain_db at the far end; q
+ * is the shelf's Q), and the one-pole LOWPASS1 / HIGHPASS1 through the bilinear transform (b2 = a2 =
+ * 0, half power at f_hz; q and gain_db are not used).  De-emphasis with the time constant tau is
+ * LOWPASS1 at 1 / (2 pi tau).  f_hz outside (0, rate_hz / 2), q <= 0, anything not finite, an unknown
+ * kind, or a result that fails the stability test: PDDC_EINVAL.
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV. */
+#define PDDC_EQ_MAX_SECTIONS 8
+#define PDDC_EQ_RESTART      0x1u
+#define PDDC_EQ_LOWPASS      0
+#define PDDC_EQ_HIGHPASS     1
+#define PDDC_EQ_BANDPASS     2
+#define PDDC_EQ_NOTCH        3
+#define PDDC_EQ_PEAK         4
+#define PDDC_EQ_LOWSHELF     5
+#define PDDC_EQ_HIGHSHELF    6
+#define PDDC_EQ_LOWPASS1     7
+#define PDDC_EQ_HIGHPASS1    8
+typedef struct pddc_eq_section {
+    double b0, b1, b2, a1, a2;   /* a0 = 1                               */
+} pddc_eq_section;
+typedef struct pddc_eq_params {
+    int sections;         /* S: 1, 2, 4 or 8                              */
+} pddc_eq_params;
+typedef struct pddc_eq pddc_eq;
+int pddc_eq_create(pddc_eq **out, int device, int nrx, const pddc_eq_params *params, const int *nsec /* [nrx] */,
+                   const pddc_eq_section *sec /* [nrx][S], copied; receiver j's first nsec[j] are read */);
+int pddc_eq_destroy(pddc_eq *s);
+int pddc_eq_reset(pddc_eq *s);                        /* everything carried; synchronises the device */
+int pddc_eq_set_rx(pddc_eq *s, int rx, int nsec, const pddc_eq_section *sec /* [nsec]; NULL with nsec 0 */,
+                   uint32_t flags);
+int pddc_eq_process(pddc_eq *s, const void *d_a, size_t n, size_t a_stride, void *d_out, size_t out_stride,
+                    void *stream);
+int pddc_eq_read_state(pddc_eq *s, double *host /* [nrx][S][2] */, void *stream);
+/* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
+int pddc_eq_tile_outputs(void);
+int pddc_eq_design(int kind, double rate_hz, double f_hz, double q, double gain_db, pddc_eq_section *out);
+
 /* ---- blanker: impulse noise blanker per receiver ------------------------------
  * A stage between the tuner and the receiver filter, the only place where an impulse is still a few
  * samples long.  Per batch it reads the receivers' complex float32 rows z_j[m] (the tuner's output

@@ -112,6 +112,19 @@ class DenoiseRx(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("beta", C.c_float), ("gmin", C.c_float), ("alpha", C.c_float), ("flags", C.c_uint32)]
 
 
+class EqSection(C.Structure):
+    """pddc_eq_section (include/perseus_ddc.h): b0, b1, b2, a1, a2 with a0 = 1, binary64"""
+    _fields_ = [("b0", C.c_double), ("b1", C.c_double), ("b2", C.c_double), ("a1", C.c_double), ("a2", C.c_double)]
+
+    def __iter__(self):
+        return iter((self.b0, self.b1, self.b2, self.a1, self.a2))
+
+
+class EqParams(C.Structure):
+    """pddc_eq_params (include/perseus_ddc.h)"""
+    _fields_ = [("sections", C.c_int)]
+
+
 class MixerParams(C.Structure):
     """pddc_mixer_params (include/perseus_ddc.h)"""
     _fields_ = [("nbus", C.c_int), ("ramp", C.c_int), ("flags", C.c_uint32), ("block", C.c_int), ("ceil", C.c_float),
@@ -356,6 +369,17 @@ def ddc_lib() -> C.CDLL:
     L.pddc_denoise_tile_frames.argtypes = []
     for name in ("pddc_denoise_create", "pddc_denoise_destroy", "pddc_denoise_reset", "pddc_denoise_set_rx",
                  "pddc_denoise_process", "pddc_denoise_read_noise", "pddc_denoise_delay", "pddc_denoise_tile_frames"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_eq_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(EqParams), C.POINTER(C.c_int), C.POINTER(EqSection)]
+    L.pddc_eq_destroy.argtypes = [vp]
+    L.pddc_eq_reset.argtypes = [vp]
+    L.pddc_eq_set_rx.argtypes = [vp, C.c_int, C.c_int, C.POINTER(EqSection), C.c_uint32]
+    L.pddc_eq_process.argtypes = [vp, vp, sz, sz, vp, sz, vp]
+    L.pddc_eq_read_state.argtypes = [vp, vp, vp]
+    L.pddc_eq_tile_outputs.argtypes = []
+    L.pddc_eq_design.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(EqSection)]
+    for name in ("pddc_eq_create", "pddc_eq_destroy", "pddc_eq_reset", "pddc_eq_set_rx", "pddc_eq_process",
+                 "pddc_eq_read_state", "pddc_eq_tile_outputs", "pddc_eq_design"):
         getattr(L, name).restype = C.c_int
     L.pddc_blanker_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.POINTER(BlankerParams), C.POINTER(BlankerRx)]
     L.pddc_blanker_destroy.argtypes = [vp]
@@ -920,7 +944,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Audio and Mixer share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio and Mixer share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1683,6 +1707,105 @@ class Denoise(_StreamObject):
         nn = np.zeros((self.nrx, self.nfft // 2 + 1), dtype=np.float32)
         check(ddc_lib().pddc_denoise_read_noise(self._h, nn.ctypes.data, self._stream(stream)))
         return nn
+
+
+PDDC_EQ_MAX_SECTIONS = 8
+PDDC_EQ_RESTART = 0x1
+(PDDC_EQ_LOWPASS, PDDC_EQ_HIGHPASS, PDDC_EQ_BANDPASS, PDDC_EQ_NOTCH, PDDC_EQ_PEAK, PDDC_EQ_LOWSHELF, PDDC_EQ_HIGHSHELF,
+ PDDC_EQ_LOWPASS1, PDDC_EQ_HIGHPASS1) = range(9)
+
+
+def eq_tile_outputs() -> int:
+    """pddc_eq_tile_outputs: samples per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_eq_tile_outputs())
+
+
+def eq_section(kind: int, rate_hz: float, f_hz: float, q: float = 0.7071, gain_db: float = 0.0) -> EqSection:
+    """pddc_eq_design: one second-order section in double -- the RBJ cookbook's PDDC_EQ_LOWPASS, _HIGHPASS, _BANDPASS (0 dB
+    peak), _NOTCH, _PEAK, _LOWSHELF, _HIGHSHELF, and the one-pole _LOWPASS1 / _HIGHPASS1 (half power at f_hz; q and
+    gain_db are not used).  Host arithmetic, no device."""
+    s = EqSection()
+    check(ddc_lib().pddc_eq_design(_clip(kind), float(rate_hz), float(f_hz), float(q), float(gain_db), C.byref(s)))
+    return s
+
+
+def eq_deemphasis(rate_hz: float, tau_s: float) -> EqSection:
+    """the FM de-emphasis of time constant tau_s (50e-6, 75e-6; narrow-band FM: 750e-6 or so): PDDC_EQ_LOWPASS1 at 1 / (2 pi tau)"""
+    import math
+    tau = float(tau_s)
+    return eq_section(PDDC_EQ_LOWPASS1, rate_hz, 1.0 / (2.0 * math.pi * tau) if tau > 0.0 else float("nan"))
+
+
+def eq_response(sections, rate_hz: float, freqs):
+    """H(f) of a cascade at the frequencies `freqs` (Hz): the product of (b0 + b1 z^-1 + b2 z^-2) / (1 + a1 z^-1 + a2 z^-2),
+    z = exp(2 pi j f / rate_hz), over `sections` (EqSection or five values each).  -> numpy complex128, the shape of
+    freqs.  For a display and the tests; numpy, no device."""
+    import numpy as np
+    f = np.asarray(freqs, dtype=np.float64)
+    z1 = np.exp(-2j * np.pi * f / float(rate_hz))
+    z2 = z1 * z1
+    h = np.ones(f.shape, dtype=np.complex128)
+    for s in sections:
+        b0, b1, b2, a1, a2 = (float(v) for v in s)
+        h = h * ((b0 + b1 * z1 + b2 * z2) / (1.0 + a1 * z1 + a2 * z2))
+    return h
+
+
+def _eq_sections(sections):
+    """a cascade as the C ABI takes it: EqSection or five values each -> (count, array of at least one)"""
+    secs = [s if isinstance(s, EqSection) else EqSection(*(float(v) for v in s)) for s in sections]
+    return len(secs), (EqSection * max(len(secs), 1))(*secs)
+
+
+class Eq(_StreamObject):
+    """pddc_eq: an equaliser per receiver, on the device (include/perseus_ddc.h).  It goes behind Demod, Squelch, Adapt or
+    Denoise and in front of Audio (or behind Audio, at 48 kHz): a cascade of up to `sections` (1, 2, 4, 8) second-order
+    sections per receiver -- de-emphasis, a CW peak filter, notches, shelves, high and low cut (eq_section, eq_deemphasis)
+    -- in binary64 arithmetic on float32 audio.  rx: one list of sections (EqSection or (b0, b1, b2, a1, a2)) per
+    receiver; an empty list passes the audio word for word.  Feed it every batch in order on one stream; all outputs are
+    bit-identical however the series is cut, and whatever `sections` is."""
+    _kind = "eq"
+
+    def __init__(self, rx, sections: int = 4, device: int = 0):
+        rx = [list(r) for r in rx]
+        self.nrx, self.device, self.sections = len(rx), device, int(sections)
+        S = self.sections if self.sections in (1, 2, 4, 8) else 0
+        nsec = (C.c_int * max(self.nrx, 1))()
+        sec = (EqSection * max(self.nrx * max(S, 1), 1))()
+        for j, r in enumerate(rx):
+            nsec[j] = _clip(len(r))
+            for s, c in enumerate(r[:S]):
+                sec[j * S + s] = c if isinstance(c, EqSection) else EqSection(*(float(v) for v in c))
+        self.params = EqParams(_clip(sections))
+        h = C.c_void_p()
+        check(ddc_lib().pddc_eq_create(C.byref(h), device, self.nrx, C.byref(self.params), nsec, sec))
+        self._h = h
+
+    def process(self, a, out=None, stream=None):
+        """One batch: a float32 CUDA tensor [nrx, n] whose rows are contiguous (any row stride: the views Demod.process,
+        Squelch.process, Adapt.process and Denoise.process return are fine).  -> float32 [nrx, n] (a view of `out`, a
+        float32 CUDA tensor [nrx, capacity] with contiguous rows, if given).  `out` may be `a` itself (in place); it must
+        not overlap a otherwise."""
+        import torch
+        if not self._rows(a, torch.float32):
+            raise PddcError(-1, "eq: a must be a float32 tensor [nrx, n] with contiguous rows")
+        n = int(a.shape[1])
+        out, cap = self._out(out, n, torch.float32, "out must be a float32")
+        check(ddc_lib().pddc_eq_process(self._h, a.data_ptr() if n else None, n, int(a.stride(0)),
+                                        out.data_ptr() if out.numel() else None, cap, self._stream(stream)))
+        return out[:, :n]
+
+    def set_rx(self, rx: int, sections, flags: int = 0):
+        """receiver rx's cascade from the next sample on; the states are kept unless flags has PDDC_EQ_RESTART"""
+        n, arr = _eq_sections(sections)
+        check(ddc_lib().pddc_eq_set_rx(self._h, int(rx), _clip(n), arr, int(flags) & 0xFFFFFFFF))
+
+    def read_state(self, stream=None):
+        """-> numpy float64 [nrx, sections, 2]: s1, s2 as the last batch left them (it waits for it)"""
+        import numpy as np
+        st = np.zeros((self.nrx, self.sections, 2), dtype=np.float64)
+        check(ddc_lib().pddc_eq_read_state(self._h, st.ctypes.data, self._stream(stream)))
+        return st
 
 
 PDDC_NB_ON = 0x1
