@@ -31,8 +31,8 @@ namespace pddc {
  * balanced base-256 digits, every digit x byte-plane product sum over 256 taps stays below 2^24, so int32 accumulation is
  * EXACT; products of equal weight 256^(i+j) share an accumulator, the three lightest (i + j < 2: below 1.2e-7 of full
  * scale even if every term had the same sign, 2e-9 typical) are dropped, and the four sums are recombined in fp32 once
- * per output.  The unpack is gone: the loaders only de-interleave bytes (v_perm) into six planes (planes 0 and 1 xor
- * 0x80: unsigned -> signed, the offset comes back as one constant per filter).
+ * per output.  The unpack is gone: the loaders only de-interleave bytes (v_perm, 24 per 8 samples) into six planes (the two
+ * low bytes of each component xor 0x80: unsigned -> signed, the offset comes back as one constant per filter).
  *   out[16 n + r] = sum_c T[r][c] X[c][n],  T[r][c] = h[HIST - (c - 8 r)] (banded Toeplitz, 16 x (120 + HIST)),
  *   X[c][n] = xp[8192 tile + 128 n + c],    xp = the HIST history samples followed by the batch.
  * v_mfma_i32_16x16x64_i8: 16 output rows, 16 columns, k-steps of 64; 9 plane products per step.  LDS rows are padded (lane
@@ -42,24 +42,25 @@ typedef int v16i_t __attribute__((ext_vector_type(16)));
 namespace i8 {
 __device__ __forceinline__ int swz(int p) { return p + 16 * (p >> 7); }
 
-/* the 8 bytes at offsets 6 s + O (s = 0..7) of the 48 bytes w[0..11] */
+/* the 8 bytes at offsets 6 s + O and the 8 at 6 s + O + 1 (s = 0..7; O = 0, 2, 4) of the 48 bytes w[0..11]: planes O and
+ * O + 1, a[0] / b[0] samples 0..3, a[1] / b[1] samples 4..7.  In each 24-byte half the two planes live in the same dwords
+ * -- samples 0, 1 in dwords (O >> 2, (O + 6) >> 2), samples 2, 3 three dwords on -- so ONE perm per dword pair picks two
+ * bytes for each plane ([a0 a1 b0 b1], [a2 a3 b2 b3]) and two more put the planes' dwords together: 4 perms per plane pair
+ * and half, 24 per group (one plane at a time took 36) */
 template <int O>
-__device__ __forceinline__ void plane_bytes(const uint32_t (&w)[12], uint32_t &lo, uint32_t &hi)
+__device__ __forceinline__ void plane_pair_bytes(const uint32_t (&w)[12], uint32_t (&a)[2], uint32_t (&b)[2])
 {
-    uint32_t out[2];
+    static_assert(O == 0 || O == 2 || O == 4, "an even plane and its neighbour");
+    constexpr uint32_t sel = (uint32_t)(O & 3) | ((uint32_t)(4 + ((O + 6) & 3)) << 8) | ((uint32_t)((O + 1) & 3) << 16) |
+                             ((uint32_t)(4 + ((O + 7) & 3)) << 24);
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        uint32_t pair[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int b0 = 6 * (4 * half + 2 * q) + O, b1 = b0 + 6;
-            const uint32_t sel = (uint32_t)(b0 & 3) | ((uint32_t)(4 + (b1 & 3)) << 8) | 0x0c0c0000u;
-            pair[q] = __builtin_amdgcn_perm(w[b1 >> 2], w[b0 >> 2], sel);
-        }
-        out[half] = __builtin_amdgcn_perm(pair[1], pair[0], 0x05040100u);
+        const int d = 6 * half;
+        const uint32_t p = __builtin_amdgcn_perm(w[d + ((O + 6) >> 2)], w[d + (O >> 2)], sel);
+        const uint32_t q = __builtin_amdgcn_perm(w[d + ((O + 18) >> 2)], w[d + ((O + 12) >> 2)], sel);
+        a[half] = __builtin_amdgcn_perm(q, p, 0x05040100u);
+        b[half] = __builtin_amdgcn_perm(q, p, 0x07060302u);
     }
-    lo = out[0];
-    hi = out[1];
 }
 
 } // namespace i8
@@ -120,7 +121,7 @@ void fir_i8_taps16(const float *taps, int ntaps, int hist, uint16_t *out)
  * samples, loaded by 72 loader lanes) -- no tile depends on another block, no warm-up tile; the batch's first tile takes
  * the stream's second-stage history (the 64 mixed first-stage outputs k_fir8's fused pair keeps too) instead.        */
 namespace i8x {
-using i8::plane_bytes;
+using i8::plane_pair_bytes;
 using i8::swz;
 constexpr int TILE = 8192;
 constexpr int kTaps2Len = 68;                  /* floats per rail of the second stage's tap table (65 used) */
@@ -171,42 +172,83 @@ struct Walk {
     }
 };
 
-/* 8 samples (48 bytes) -> 8 bytes in each of the six planes at (swizzled) position `at` */
-__device__ __forceinline__ void put_planes(const uint4 (&r)[3], uint8_t *plane, int PLANE, int at)
+/* 8 samples (48 bytes) -> 8 bytes in each of the six planes; `p`: this lane's (swizzled) position in the set's plane 0 --
+ * the planes then lie at constant offsets below 64 KB, inside the LDS store's offset field */
+__device__ __forceinline__ void put_planes(const uint4 (&r)[3], uint8_t *p, int PLANE)
 {
     const uint32_t w[12] = { r[0].x, r[0].y, r[0].z, r[0].w, r[1].x, r[1].y, r[1].z, r[1].w, r[2].x, r[2].y, r[2].z, r[2].w };
-    uint32_t lo, hi;
-#define PDDC_PL(C, I, O, X)                                                                       \
-    plane_bytes<O>(w, lo, hi);                                                                    \
-    *reinterpret_cast<uint2 *>(plane + (3 * C + I) * PLANE + at) = make_uint2(lo ^ X, hi ^ X);
-    PDDC_PL(0, 0, 0, 0x80808080u)
-    PDDC_PL(0, 1, 1, 0x80808080u)
-    PDDC_PL(0, 2, 2, 0u)
-    PDDC_PL(1, 0, 3, 0x80808080u)
-    PDDC_PL(1, 1, 4, 0x80808080u)
-    PDDC_PL(1, 2, 5, 0u)
+    uint32_t lo[2], hi[2];
+    /* planes O and O + 1 of the wire = plane sets' planes PA and PB; XA / XB: unsigned -> signed for the two low bytes */
+#define PDDC_PL(O, PA, XA, PB, XB)                                                                \
+    plane_pair_bytes<O>(w, lo, hi);                                                               \
+    *reinterpret_cast<uint2 *>(p + (PA) * PLANE) = make_uint2(lo[0] ^ XA, lo[1] ^ XA);            \
+    *reinterpret_cast<uint2 *>(p + (PB) * PLANE) = make_uint2(hi[0] ^ XB, hi[1] ^ XB);
+    PDDC_PL(0, 0, 0x80808080u, 1, 0x80808080u)
+    PDDC_PL(2, 2, 0u, 3, 0x80808080u)
+    PDDC_PL(4, 4, 0x80808080u, 5, 0u)
 #undef PDDC_PL
 }
 
-/* the loads of group g = lt + 512 q (q = 0, 1) of tile t: batch samples 8192 t + 8 g .. + 8, zeros behind the batch.
- * (Plain loads: a lane's three 16-byte loads share their cache lines with its neighbours' -- as NONTEMPORAL loads the lines
+/* The main groups of a tile come through a buffer descriptor of the TILE (built from wave-uniform values: the batch, the
+ * tile): base = the tile's first sample, records = the bytes of its groups that lie WHOLLY inside the batch -- none for "no
+ * tile" (t < 0) --, so that the loads need neither a branch nor a zero fill: a group behind the batch comes back as zeros
+ * from the range check.  hipcc answers a load under a runtime condition with s_waitcnt vmcnt(0) -- with the branches the
+ * loader waves waited for every group right behind issuing it and nothing ran two tiles ahead (NOTEBOOK R26) --, loads it
+ * can count it waits for at their first use.  Rebased per tile the record count stays below 64 KB whatever the batch.
+ * (Cached loads: a lane's three 16-byte loads share their cache lines with its neighbours' -- as NONTEMPORAL loads the lines
  * are fetched again and again: 0.3205 -> 0.4293 ms for the untuned 127-tap stage, same box, tools/ab_i8x.sh.)          */
-template <int TILE_S = TILE>
-__device__ __forceinline__ void issue_group(const FirI8xArgs &a, long long t, int g, uint4 (&r)[3])
+/* a wave-uniform 64-bit value, in scalar registers for what is computed from it (the descriptors' words) */
+__device__ __forceinline__ long long uniform64(long long v)
 {
-    const long long b = t * TILE_S + 8LL * g + a.in_off;
-    if (b + 8 <= a.n_in) {
-        const uint4 *p = reinterpret_cast<const uint4 *>(static_cast<const uint8_t *>(a.in) + b * 6);
-        r[0] = p[0];
-        r[1] = p[1];
-        r[2] = p[2];
-    } else {
-        r[0] = r[1] = r[2] = make_uint4(0u, 0u, 0u, 0u);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, long long byte_off, int bytes)
+{
+    const long long p = uniform64((long long)(static_cast<const uint8_t *>(base) + byte_off));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(p), 0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+template <int TILE_S, int NGRP>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t group_rsrc(const FirI8xArgs &a, long long t)
+{
+    const long long s0 = uniform64(t < 0 ? 0 : t * TILE_S + a.in_off);
+    long long left = (uniform64(a.n_in) - s0) >> 3;                  /* (n_in and in_off are multiples of 8) */
+    left = t < 0 || left < 0 ? 0 : left > NGRP ? NGRP : left;
+    return make_rsrc(a.in, s0 * 6, 48 * (int)left);
+}
+
+/* the three 16-byte loads of the group at byte `voff` of the descriptor's range (48 g for group g) */
+__device__ __forceinline__ void issue_group(__amdgpu_buffer_rsrc_t rs, int voff, uint4 (&r)[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 16 * i, 0, 0);
+        r[i] = make_uint4(v[0], v[1], v[2], v[3]);
     }
 }
 
+/* ONE group per wave in flight: the step waits for the group it issued last before it issues the next -- behind that group's
+ * conversion time, not right behind its issue.  Measured, not designed (NOTEBOOK R26): with two groups per wave in flight --
+ * what hipcc's counted waits alone allow -- the untuned 127-tap stage at 2^28 samples takes 0.3203 ms, with one 0.3013, with
+ * the wait right behind every issue (what the branches used to force) 0.3149; same box, alternating builds.  (Supposed: the
+ * three loads of a group share every cache line, eight waves x 3 KB are 24 KB of lines in flight in a 32 KB L1, twice that
+ * evicts lines between a group's first load and its third.  Not separated from it: vmcnt counts this wave's stores too, so
+ * where the loaders finish tiles -- LAYOUT 1 -- the wait also drains their result stores.) */
+__device__ __forceinline__ void loads_landed() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+/* the descriptor of the FG front groups of tile t > 0 (all of them lie in the batch: samples TILE_S t - FRONT .. TILE_S t);
+ * no records unless the tile starts a chunk */
+template <int FRONT, int TILE_S>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t front_rsrc(const FirI8xArgs &a, long long t, bool wanted)
+{
+    const bool some = wanted && t > 0;
+    return make_rsrc(a.in, some ? (uniform64(t * TILE_S + a.in_off) - FRONT) * 6 : 0, some ? 6 * FRONT : 0);
+}
+
 /* the groups in front of a chunk's first tile t: front group g (0 .. FG) = samples 8192 t - FRONT + 8 g ..; groups below
- * `g0` are not needed (no porch columns: not FUSE2, or the batch's first tile).  From the stream's history for t = 0. */
+ * `g0` are not needed (no porch columns: not FUSE2, or the batch's first tile).  From the stream's history for t = 0.
+ * (The block's FIRST tile only, once per launch: two sources and a zero fill, under branches -- every later tile's front
+ * groups come from the batch alone, through front_rsrc.) */
 template <int HIST, int FRONT, int TILE_S = TILE>
 __device__ __forceinline__ void issue_front(const FirI8xArgs &a, long long t, int g, uint4 (&r)[3])
 {
@@ -546,7 +588,8 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
         }
     };
     if (wave >= 4) {
-        /* ---- loaders (waves 4..11): main groups two tiles ahead in two register sets, front groups one tile ahead;
+        /* ---- loaders (waves 4..11): main groups two tiles ahead in two register sets, front groups one tile ahead of their
+         * conversion in a third;
          * LAYOUT 1: they also finish the tile before the one the matrix waves are working on */
         const int lt = tid - 256;
         if (blk == 0 && a.hist_out) {             /* the next call's history: the batch's last HIST (hist_len) samples */
@@ -560,52 +603,82 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
         uint4 ra[NQ][3], rb[NQ][3], rf[3];
         Cursor c0 = cur, c1 = wk.next(c0), c2 = wk.next(c1);
         long long t = wk.tile(c0), t1 = wk.tile(c1), t2 = wk.tile(c2), tp = -1;
+        /* (the last round of a tile whose groups are no multiple of the loader threads: every lane LOADS -- its group lies
+         * behind the descriptor's range and costs no traffic --, only the lanes with a group convert) */
         auto has = [&](int q) __attribute__((always_inline)) { return !PART || q < NQ - 1 || lt + NLT * q < NGRP; };
+        /* this lane's main groups: their bytes in a tile's descriptor, and their positions in the two plane sets -- kept in
+         * registers (the second set's planes lie beyond the LDS store's 16-bit offset field: from one base per set every
+         * plane is a constant offset, from one base for both the compiler adds the rest again in front of every store) */
+        int voff[NQ];
+        uint32_t at0[NQ], at1[NQ];
 #pragma unroll
-        for (int q = 0; q < NQ; ++q)
-            if (has(q))
-                issue_group<TILE_S>(a, t, lt + NLT * q, ra[q]);
-        if (lt < G::FG && lt >= front_lo(t)) {
-            issue_front<HIST, FRONT, TILE_S>(a, t, lt, rf);
-            put_planes(rf, lds_i8x, PLANE, swz(8 * lt));
+        for (int q = 0; q < NQ; ++q) {
+            voff[q] = 48 * (lt + NLT * q);
+            at0[q] = (uint32_t)swz(FRONT + 8 * (lt + NLT * q));
+            at1[q] = at0[q] + 6 * PLANE;
+            asm volatile("" : "+v"(at0[q]), "+v"(at1[q]));
         }
+        const bool front_wave = wave < 4 + (G::FG + 63) / 64;        /* (uniform) the loader waves that hold front lanes */
+        {
+            const __amdgpu_buffer_rsrc_t rs = group_rsrc<TILE_S, NGRP>(a, t), rs1 = group_rsrc<TILE_S, NGRP>(a, t1);
 #pragma unroll
-        for (int q = 0; q < NQ; ++q)
-            if (has(q))
-                put_planes(ra[q], lds_i8x, PLANE, swz(FRONT + 8 * (lt + NLT * q)));
-        if (t1 >= 0) {
+            for (int q = 0; q < NQ; ++q)
+                issue_group(rs, voff[q], ra[q]);
+            if (lt < G::FG && lt >= front_lo(t)) {
+                issue_front<HIST, FRONT, TILE_S>(a, t, lt, rf);
+                put_planes(rf, lds_i8x + swz(8 * lt), PLANE);
+            }
 #pragma unroll
             for (int q = 0; q < NQ; ++q)
                 if (has(q))
-                    issue_group<TILE_S>(a, t1, lt + NLT * q, ra[q]);
+                    put_planes(ra[q], lds_i8x + at0[q], PLANE);
+            if (front_wave)
+                issue_group(front_rsrc<FRONT, TILE_S>(a, t1, c1.k == 0), 48 * lt, rf);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+                issue_group(rs1, voff[q], ra[q]);
         }
         __syncthreads();
-        /* one step: tile `tn` (already in `cur_r`) goes into plane set `dst` while the matrix waves work on `src`; the loads
-         * of the tile after it (`tnn`, if any) go out group by group BETWEEN the conversions (k_fir_i8's pacing) */
-        auto step = [&](long long tn, bool tn_first, long long tnn, uint4 (&nxt)[NQ][3], const uint4 (&cur_r)[NQ][3], uint8_t *dst,
-                        const uint8_t *src) {
-            const bool ff = tn_first && lt < G::FG && lt >= front_lo(tn);
-            if (ff)
-                issue_front<HIST, FRONT, TILE_S>(a, tn, lt, rf);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int g = lt + NLT * q;
-                if (!has(q))
-                    continue;
-                if (tnn >= 0)
-                    issue_group<TILE_S>(a, tnn, g, nxt[q]);
-                __builtin_amdgcn_sched_barrier(0);
-                put_planes(cur_r[q], dst, PLANE, swz(FRONT + 8 * g));
-                __builtin_amdgcn_sched_barrier(0);
-            }
+        /* one step: tile `tn` > 0 (already in `cur_r`) goes into plane set `dst` (this lane's positions in it: `at`) while the
+         * matrix waves work on `src`; the loads of the tile after it (`tnn`; no tile: a descriptor without records) go out
+         * group by group BETWEEN the conversions (k_fir_i8's pacing), all of them unconditional, each once the group before
+         * it has landed (loads_landed): a group is in flight while the group before it is converted.  The front groups of a
+         * chunk's first tile (C = 1: every tile) lie in the batch, tile 0 being a prologue's: a descriptor of their own,
+         * without records inside a chunk, loaded by every lane of the first loader wave(s) -- tn's were requested at the
+         * start of the step before (same box, same build otherwise: requested and converted inside one step, as until round
+         * 26, 0.3189 ms against 0.3011) and are converted first; tnn's follow */
+        auto step = [&](long long tn, bool tn_first, long long tnn, bool tnn_first, uint4 (&nxt)[NQ][3], const uint4 (&cur_r)[NQ][3],
+                        auto set_c) {
+            /* the plane set tn goes into (0 / 1): its base, the other set's, and this lane's main-group positions in it */
+            constexpr int SET = decltype(set_c)::value;
+            uint8_t *const dst = lds_i8x + SET * 6 * PLANE;
+            const uint8_t *const src = lds_i8x + (SET ^ 1) * 6 * PLANE;
+            const uint32_t(&at)[NQ] = SET ? at1 : at0;
+            const bool ff = tn_first && lt < G::FG;
             if (ff) {
-                put_planes(rf, dst, PLANE, swz(8 * lt));
+                put_planes(rf, dst + swz(8 * lt), PLANE);
             } else if (!tn_first && lt < G::HG) {
                 /* inside a chunk: the history comes over from the plane set of the tile before */
                 const int s_at = swz(FRONT + TILE_S - HIST + 8 * lt), d_at = swz(EXTRA + 8 * lt);
 #pragma unroll
                 for (int pl = 0; pl < 6; ++pl)
                     *reinterpret_cast<uint2 *>(dst + pl * PLANE + d_at) = *reinterpret_cast<const uint2 *>(src + pl * PLANE + s_at);
+            }
+            if (front_wave)
+                issue_group(front_rsrc<FRONT, TILE_S>(a, tnn, tnn_first), 48 * lt, rf);
+            const __amdgpu_buffer_rsrc_t rs = group_rsrc<TILE_S, NGRP>(a, tnn);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                /* (decimate by 10, three rounds of groups, the last half empty: no wait in front of the step's FIRST issue --
+                 * with it the form's 2^26-sample batches took 0.0857-0.0864 ms against 0.0809-0.0816 without and 0.0822-0.0825
+                 * before round 26; the decimate-by-8 forms were measured with it) */
+                if (D == 8 || q >= 1)
+                    loads_landed();
+                issue_group(rs, voff[q], nxt[q]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (has(q))
+                    put_planes(cur_r[q], lds_i8x + at[q], PLANE);
+                __builtin_amdgcn_sched_barrier(0);
             }
         };
         float *arr0 = arr_base, *arr1 = arr_base + NARR * AS;
@@ -614,7 +687,7 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
             /* the matrix waves compute tile t from plane set 0 into value set 0; t1 (in ra) goes to plane set 1, t2 starts
              * towards rb; the tile before t (values in set 1) is finished */
             if (t1 >= 0)
-                step(t1, c1.k == 0, t2, rb, ra, lds_i8x + 6 * PLANE, lds_i8x);
+                step(t1, c1.k == 0, t2, c2.k == 0, rb, ra, std::integral_constant<int, 1>{});
             if (LAYOUT == 1 && tp >= 0)
                 post(tp, arr1, arr0, c0.k == 0, lt, std::false_type{});
             __syncthreads();
@@ -629,7 +702,7 @@ __device__ __forceinline__ void fir_i8x_block(const FirI8xArgs &a, long long nti
             t1 = t2;
             t2 = wk.tile(c2);
             if (t1 >= 0)
-                step(t1, c1.k == 0, t2, ra, rb, lds_i8x, lds_i8x + 6 * PLANE);
+                step(t1, c1.k == 0, t2, c2.k == 0, ra, rb, std::integral_constant<int, 0>{});
             if (LAYOUT == 1)
                 post(tp, arr0, arr1, c0.k == 0, lt, std::false_type{});
             __syncthreads();

@@ -48,7 +48,7 @@ def timeit(stages, opts, ns, steps=30, mix=True, fp16=False):
     L = pkg.ddc_lib()
     if hasattr(L, "pddc_i8x_probe_dump") and os.environ.get("I8X_PROBE"):
         L.pddc_i8x_probe_dump.argtypes = [__import__("ctypes").c_int]
-        L.pddc_i8x_probe_dump(1)                 # (probe builds, tools/ubench/i8x_probe_r05.patch: clears what the warm-up left)
+        L.pddc_i8x_probe_dump(1)                 # (probe builds, tools/ubench/i8x_probe_r05.patch on the tree of fa5e245: clears what the warm-up left)
         pipe.process_ptr(d_in.data_ptr(), ns, out.data_ptr(), out.shape[0], st)
         torch.cuda.synchronize()
         print("probe of one launch:", flush=True)

@@ -1,5 +1,6 @@
 """per-role clock probe of k_fir_i8x (library built with tools/ubench/i8x_probe_r05.patch as libperseus_ddc.so):
-one launch of 2^27 samples per form, ticks per tile by wave.  waves 0..3 matrix (layout 2: 0, 1 matrix, 2, 3 finishing), 4..11 loaders"""
+one launch of 2^27 samples per form, ticks per tile by wave.  The patch applies to the tree of commit fa5e245 (tools/ubench/PATCHES.json), not to the loaders as
+they are since round 26.  waves 0..3 matrix (layout 2: 0, 1 matrix, 2, 3 finishing), 4..11 loaders"""
 import ctypes as C, importlib, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,7 @@
 """runner for tools/ubench/i8x_mixing_loaders.patch (apply, build, run on the GPU box): the mixing-loader form (option i8x_mixl,
 default 1 with the patch) against the NCO-in-the-taps form for tuned first stages of 65..256 taps: errors against the oracle on a
-ragged stream, then time at 2^28"""
+ragged stream, then time at 2^28.
+The patch applies to the tree of commit fa5e245 (tools/ubench/PATCHES.json), not to the loaders as they are since round 26."""
 import importlib, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
