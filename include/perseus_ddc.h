@@ -1403,6 +1403,103 @@ int pddc_mixer_tile_outputs(void);
 int pddc_host_alloc(void **h_ptr, size_t nbytes);
 int pddc_host_free(void *h_ptr);
 
+/* ---- fsk: start-stop FSK (RTTY) decoding per receiver ---------------------------
+ * The first stage whose output is data, not samples: two-tone FSK with start-stop characters (RTTY at
+ * 45.45 / 50 / 75 baud with 170 / 450 / 850 Hz shift, the asynchronous maritime and weather traffic).
+ * It reads the rows the tuner, blanker, receiver filter and carrier write.  K receivers (1 .. 1024), a
+ * window length W (1 .. 256), a bank of B modems (1 .. 16), copied at create.  Modem b: hm[W] and
+ * hs[W], complex float32 taps (the mark and the space matched filter, every value finite); inc,
+ * uint32 in 1 .. 2^30, the bit phase advanced per sample, 2^32 baud / rate; nbits, 5 .. 8.  Receiver j:
+ * a modem index and flags PDDC_FSK_ON, _REVERSE, _RESTART.
+ * Input per batch: z[j z_stride + i], i < n, complex float32, any row stride, n >= 0.  m counts the
+ * object's samples since create / reset (every batch adds n, for every receiver); inputs before a
+ * receiver's first are zero.
+ * Discriminator, for every sample m of an ON receiver; every operation is one float32 operation in
+ * this order, contraction off:
+ *   M = sum over t = 0 .. W-1 of hm[t] z[m - t], from (0, 0) with t ascending, per tap
+ *       re = fmaf(hr, zr, re); re = fmaf(-hi, zi, re); im = fmaf(hr, zi, im); im = fmaf(hi, zr, im);
+ *   S the same with hs.  pm = fmaf(Mi, Mi, Mr Mr), ps likewise; with REVERSE the two are exchanged.
+ *   space = (ps > pm), so a NaN reads as mark.  s = pm + ps; d = s > 0 ? (pm - ps) / s : 0, the division
+ *   correctly rounded; q = |d|.  Non-finite samples are data like any other: nothing is tested or cleaned.
+ *   Transient, in the receiver's own row alone: while a NaN is in the window, pm or ps and with it s is
+ *   NaN, so d = +0 and the sample reads mark; an infinity does the same wherever it makes a power NaN
+ *   (inf - inf, 0 inf), otherwise d is NaN and space is the plain comparison.  fminf drops a NaN q.
+ *   Nothing is left behind once the sample has left the window.
+ * Start-stop receiver, per ON receiver, sample by sample behind the discriminator.  Carried: state
+ * (IDLE, START, DATA, STOP), prev (the previous `space`, initially false), acc (uint32), k, shift,
+ * qmin, start (the uint64 sample index of the edge) and the counters.
+ *   IDLE: if space && !prev: state = START, acc = 2^31, start = m; no strobe on this sample.
+ *   Other states: a2 = acc + inc (mod 2^32); a strobe occurs iff a2 < acc; acc = a2.  On a strobe:
+ *     START: if space, DATA with k = 0, shift = 0, qmin = q; otherwise IDLE and false_starts++.
+ *     DATA:  shift |= (space ? 0 : 1) << k; qmin = fminf(qmin, q); ++k; when k == nbits, STOP.
+ *     STOP:  qmin = fminf(qmin, q); a character {start, code = shift, flags = space ?
+ *            PDDC_FSK_FRAMING : 0, quality = qmin} is emitted; chars++; framing += space; IDLE.
+ *   prev = space at the end of every sample, in every state.
+ * A stop element of 1, 1.5 or 2 bits is accepted alike; a break yields one framing-error character,
+ * then nothing until mark returns.
+ * Receiver control.  An OFF receiver is not read and does not advance: its count is 0, its d row, if
+ * one is asked for, is written +0.  set_rx(rx, modem, flags) takes effect at the next batch's first
+ * sample.  RESTART, or a change from OFF to ON, clears the receiver's carried inputs and puts the
+ * start-stop receiver in IDLE with prev = mark; the counters stay.  Another modem keeps the carried
+ * inputs and puts the start-stop receiver in IDLE: a character in progress is dropped.  reset() clears
+ * everything and m, and synchronises the device.
+ * Outputs of process(), all device memory, no host synchronisation: chars [nrx][char_stride], the
+ * characters whose STOP strobe lies in this batch, in order; counts uint32 [nrx]; d float32
+ * [nrx][d_stride] or NULL, the soft discriminator, one value per input (for a tuning display and for
+ * host decoders of the synchronous modes).
+ * Capacity: pddc_fsk_max_chars(f, n, &count) is host arithmetic, max over the bank of n div P_b + 1
+ * with P_b = ceil((nbits_b + 1.5) 2^32 / inc_b): two STOP strobes are at least 1 + P_b samples apart
+ * ("FSK decoder", derives it).  A char_stride below it is PDDC_ECAPACITY, and nothing is queued.
+ * process(): every argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned
+ * pointer (z and chars 8 bytes, counts and d 4; d may be NULL; with n = 0 z and chars are not looked at
+ * and counts may be NULL), PDDC_ECAPACITY for a stride below n or below the bound, PDDC_EINVAL when an
+ * output's byte range meets the input's.  n = 0 is valid: counts, if given, is set to 0, nothing
+ * carried moves, marks of set_rx stay for the next batch.  State moves only after the launch was
+ * accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * read(): per receiver chars, framing, false_starts (since create / reset), the state and d_last (the
+ * last d computed, 0 before the first) behind the batches submitted so far (it waits for them).
+ * Every bit of chars, counts, d and the status is independent of the cut into batches (n = 0 and n = 1
+ * included), nrx, j's index, the other receivers, strides, grid and tile sizes.
+ * create: argument errors before any device access (non-finite taps, inc or nbits out of range, a bad
+ * modem index, unknown flag bits); good arguments, no device: PDDC_ENODEV. */
+#define PDDC_FSK_ON       0x1u
+#define PDDC_FSK_REVERSE  0x2u   /* mark and space exchanged                    */
+#define PDDC_FSK_RESTART  0x4u   /* set_rx: start this receiver afresh          */
+#define PDDC_FSK_FRAMING  0x1    /* pddc_fsk_char.flags: the stop element was space */
+#define PDDC_FSK_IDLE     0      /* pddc_fsk_status.state                       */
+#define PDDC_FSK_START    1
+#define PDDC_FSK_DATA     2
+#define PDDC_FSK_STOP     3
+typedef struct pddc_fsk_rx {
+    int modem;            /* 0 .. nmodems - 1                             */
+    uint32_t flags;       /* PDDC_FSK_ON | _REVERSE | _RESTART            */
+} pddc_fsk_rx;
+typedef struct pddc_fsk_char {
+    uint64_t start;       /* sample index m of the start element's edge   */
+    uint16_t code;        /* data bit k in bit k, mark = 1                */
+    uint16_t flags;       /* PDDC_FSK_FRAMING                             */
+    float quality;        /* the least |d| at the data and stop strobes   */
+} pddc_fsk_char;
+typedef struct pddc_fsk_status {
+    uint32_t chars, framing, false_starts;
+    uint32_t state;       /* PDDC_FSK_IDLE / _START / _DATA / _STOP       */
+    float d_last;
+} pddc_fsk_status;
+typedef struct pddc_fsk pddc_fsk;
+int pddc_fsk_create(pddc_fsk **out, int device, int nrx, int window, int nmodems,
+                    const float *taps /* [nmodems][2][window] complex: hm, then hs; copied */,
+                    const uint32_t *inc /* [nmodems] */, const int *nbits /* [nmodems] */, const pddc_fsk_rx *rx /* [nrx] */);
+int pddc_fsk_destroy(pddc_fsk *f);
+int pddc_fsk_reset(pddc_fsk *f);                      /* m and everything carried; synchronises the device */
+int pddc_fsk_set_rx(pddc_fsk *f, int rx, int modem, uint32_t flags);
+int pddc_fsk_max_chars(const pddc_fsk *f, size_t n, size_t *count);
+int pddc_fsk_process(pddc_fsk *f, const void *d_z, size_t n, size_t z_stride, void *d_chars, size_t char_stride,
+                     void *d_counts, void *d_d, size_t d_stride, void *stream);
+/* status[nrx] after the batches submitted so far (it waits for them) */
+int pddc_fsk_read(pddc_fsk *f, pddc_fsk_status *host /* [nrx] */, void *stream);
+/* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
+int pddc_fsk_tile_outputs(void);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------- */
 /* Times `iters` back-to-back launches of the pipeline's stage-0 kernel alone
  * with HIP events on `stream`; returns average milliseconds per launch.

@@ -131,6 +131,11 @@ class MixerParams(C.Structure):
                 ("rel", C.c_float), ("scale", C.c_float)]
 
 
+class FskRx(C.Structure):
+    """pddc_fsk_rx"""
+    _fields_ = [("modem", C.c_int), ("flags", C.c_uint32)]
+
+
 class BlankerParams(C.Structure):
     """pddc_blanker_params (include/perseus_ddc.h)"""
     _fields_ = [("block", C.c_int), ("guard", C.c_int), ("ramp", C.c_int), ("beta", C.c_float), ("cap", C.c_float)]
@@ -430,6 +435,18 @@ def ddc_lib() -> C.CDLL:
         getattr(L, name).restype = C.c_int
     L.pddc_mixer_outputs.argtypes = [C.c_int, C.c_uint64, sz]
     L.pddc_mixer_outputs.restype = C.c_uint64
+    L.pddc_fsk_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                  C.POINTER(C.c_int), C.POINTER(FskRx)]
+    L.pddc_fsk_destroy.argtypes = [vp]
+    L.pddc_fsk_reset.argtypes = [vp]
+    L.pddc_fsk_set_rx.argtypes = [vp, C.c_int, C.c_int, C.c_uint32]
+    L.pddc_fsk_max_chars.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_fsk_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]
+    L.pddc_fsk_read.argtypes = [vp, vp, vp]
+    L.pddc_fsk_tile_outputs.argtypes = []
+    for name in ("pddc_fsk_create", "pddc_fsk_destroy", "pddc_fsk_reset", "pddc_fsk_set_rx", "pddc_fsk_max_chars",
+                 "pddc_fsk_process", "pddc_fsk_read", "pddc_fsk_tile_outputs"):
+        getattr(L, name).restype = C.c_int
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
     L.pddc_pipeline_time_stage0_inline.restype = C.c_int
@@ -944,7 +961,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio and Mixer share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer and Fsk share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -2172,6 +2189,149 @@ class Mixer(_StreamObject):
         import numpy as np
         st = np.zeros(self.nbus, dtype=mixer_status_dtype())
         check(ddc_lib().pddc_mixer_read(self._h, st.ctypes.data, 1 if clear else 0, self._stream(stream)))
+        return st
+
+
+PDDC_FSK_ON, PDDC_FSK_REVERSE, PDDC_FSK_RESTART = 0x1, 0x2, 0x4
+PDDC_FSK_FRAMING = 0x1
+PDDC_FSK_IDLE, PDDC_FSK_START, PDDC_FSK_DATA, PDDC_FSK_STOP = 0, 1, 2, 3
+
+
+def fsk_tile_outputs() -> int:
+    """pddc_fsk_tile_outputs: samples per tile of the kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_fsk_tile_outputs())
+
+
+def fsk_char_dtype():
+    """pddc_fsk_char as a numpy structured dtype (16 bytes)"""
+    import numpy as np
+    return np.dtype([("start", np.uint64), ("code", np.uint16), ("flags", np.uint16), ("quality", np.float32)])
+
+
+def fsk_status_dtype():
+    """pddc_fsk_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("chars", np.uint32), ("framing", np.uint32), ("false_starts", np.uint32), ("state", np.uint32),
+                     ("d_last", np.float32)])
+
+
+def fsk_modem(rate_hz: float, baud: float, mark_hz: float, space_hz: float, W: int, nbits: int = 5):
+    """A modem for Fsk's bank: the two matched filters h[t] = w[t] exp(+2 pi i f t / rate_hz), f = mark_hz and space_hz
+    (offsets from the receiver's tuned frequency, either sign), w a boxcar over min(W, round(rate_hz / baud)) samples
+    with sum 1 and zero beyond, computed in double and rounded once; inc = round(2^32 baud / rate_hz).
+    -> (hm complex64[W], hs complex64[W], inc, nbits)"""
+    import numpy as np
+    W, rate, baud = int(W), float(rate_hz), float(baud)
+    if W <= 0 or not rate > 0.0 or not baud > 0.0:
+        raise PddcError(-1, "fsk_modem: W, the rate and the baud rate must be positive")
+    L = min(W, max(1, int(round(rate / baud))))
+    t = np.arange(W, dtype=np.float64)
+    w = np.where(t < L, 1.0 / L, 0.0)
+    hm, hs = ((w * np.exp(2j * np.pi * float(f) * t / rate)).astype(np.complex64) for f in (mark_hz, space_hz))
+    return hm, hs, int(round(4294967296.0 * baud / rate)), int(nbits)
+
+
+_ITA2_LTRS = "\x00E\nA SIU\rDRJNFCKTZLWHYPQOBG\x0eMXV\x0f"
+_ITA2_FIGS = "\x003\n- '87\r\x054\x07,!:(5+)2#6019?&\x0e./=\x0f"
+
+
+def fsk_ita2(codes, flags=None) -> str:
+    """The text of 5-bit ITA2 codes (pddc_fsk_char.code: the first data bit in bit 0, mark = 1), host only: letters
+    and figures with the two shift codes (27 figures, 31 letters; they give no character themselves, and the text
+    starts in letters).  A character whose flags hold PDDC_FSK_FRAMING, and a code above 31, becomes U+FFFD."""
+    out, table = [], _ITA2_LTRS
+    for i, c in enumerate(codes):
+        c = int(c)
+        if (flags is not None and int(flags[i]) & PDDC_FSK_FRAMING) or not 0 <= c < 32:
+            out.append("\ufffd")
+        elif c == 27:
+            table = _ITA2_FIGS
+        elif c == 31:
+            table = _ITA2_LTRS
+        else:
+            out.append(table[c])
+    return "".join(out)
+
+
+class Fsk(_StreamObject):
+    """pddc_fsk: start-stop FSK (RTTY) decoding of every receiver's complex series, such as Tuner, Blanker, RxFilter or
+    Carrier write, on the device (include/perseus_ddc.h): two matched filters of W complex taps and a start-stop
+    receiver per receiver; the output is characters, not samples.  bank: up to 16 modems (hm, hs, inc, nbits), as
+    fsk_modem gives them, every hm and hs of W taps; sel: one (modem, flags) per receiver, flags PDDC_FSK_ON |
+    PDDC_FSK_REVERSE.  Feed it every batch in order on one stream; every output bit is the same however the series is
+    cut."""
+    _kind = "fsk"
+
+    def __init__(self, bank, sel, W: int, device: int = 0):
+        import numpy as np
+        bank = [tuple(b) for b in bank]
+        sel = [tuple(r) for r in sel]
+        self.W, self.nrx, self.nmodems, self.device = int(W), len(sel), len(bank), device
+        taps = np.zeros((max(self.nmodems, 1), 2, max(self.W, 1)), np.complex64)
+        for b, (hm, hs, _, _) in enumerate(bank):
+            for i, h in enumerate((hm, hs)):
+                h = np.asarray(h, dtype=np.complex64).reshape(-1)
+                if h.size != self.W:
+                    raise PddcError(-1, f"fsk: modem {b}: {h.size} taps for a window of {self.W}")
+                taps[b, i] = h
+        inc = np.array([max(0, min(int(b[2]), (1 << 32) - 1)) for b in bank] or [0], dtype=np.uint32)
+        nbits = np.array([_clip(b[3]) for b in bank] or [0], dtype=np.int32)
+        arr = (FskRx * max(self.nrx, 1))()
+        for j, (modem, flags) in enumerate(sel):
+            arr[j] = FskRx(_clip(modem), int(flags) & 0xFFFFFFFF)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_fsk_create(C.byref(h), device, self.nrx, _clip(W), self.nmodems,
+                                        taps.ctypes.data_as(C.POINTER(C.c_float)), inc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        nbits.ctypes.data_as(C.POINTER(C.c_int)), arr))
+        self._h = h
+
+    def max_chars(self, n: int) -> int:
+        """pddc_fsk_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_fsk_max_chars(self._h, int(n), C.byref(c)))
+        return int(c.value)
+
+    def process(self, z, chars=None, counts=None, d=None, want_d: bool = False, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (chars, counts) or,
+        with want_d or d given, (chars, counts, d): chars int32 [nrx, capacity, 4], four words per pddc_fsk_char
+        (`.cpu().numpy().view(fsk_char_dtype())[..., 0]` gives the records), of which the first counts[j] (int32 [nrx])
+        of row j are written; d float32 [nrx, n], the soft discriminator.  chars, counts and d, if given, are
+        tensors of these kinds (chars and d with any capacity that suffices); no output may overlap z."""
+        import torch
+        if not self._rows(z, torch.complex64):
+            raise PddcError(-1, "fsk: z must be a complex64 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        dev = torch.device("cuda", self.device)
+        if chars is None:
+            chars = torch.empty((self.nrx, self.max_chars(n), 4), dtype=torch.int32, device=dev)
+        elif not (chars.dtype == torch.int32 and chars.dim() == 3 and chars.shape[0] == self.nrx and chars.shape[2] == 4
+                  and chars[0].is_contiguous()):
+            raise PddcError(-1, "fsk: chars must be an int32 tensor [nrx, capacity, 4] with contiguous rows")
+        if counts is None:
+            counts = torch.empty((self.nrx,), dtype=torch.int32, device=dev)
+        elif not (counts.dtype == torch.int32 and counts.dim() == 1 and counts.shape[0] == self.nrx and counts.is_contiguous()):
+            raise PddcError(-1, "fsk: counts must be a contiguous int32 tensor [nrx]")
+        dcap = 0
+        if d is not None or want_d:
+            d, dcap = self._out(d, n, torch.float32, "d must be a float32")
+        # the ABI takes the row stride in characters; a capacity below the bound must reach it as one (PDDC_ECAPACITY)
+        ccap = int(chars.stride(0)) // 4 if chars.shape[1] >= self.max_chars(n) else int(chars.shape[1])
+        check(ddc_lib().pddc_fsk_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                         chars.data_ptr() if chars.numel() else None, ccap, counts.data_ptr(),
+                                         d.data_ptr() if d is not None and d.numel() else None, dcap, self._stream(stream)))
+        return (chars, counts) if d is None else (chars, counts, d[:, :n])
+
+    def set_rx(self, rx: int, modem: int, flags: int):
+        """receiver rx from the next batch's first sample on: PDDC_FSK_RESTART, or OFF -> ON, starts it afresh (the
+        counters stay); another modem keeps the carried inputs and drops a character in progress"""
+        check(ddc_lib().pddc_fsk_set_rx(self._h, int(rx), _clip(modem), int(flags) & 0xFFFFFFFF))
+
+    def read(self, stream=None):
+        """-> numpy structured array [nrx] (chars, framing, false_starts, state, d_last) after the batches submitted so
+        far (it waits for them)"""
+        import numpy as np
+        st = np.zeros(self.nrx, dtype=fsk_status_dtype())
+        check(ddc_lib().pddc_fsk_read(self._h, st.ctypes.data, self._stream(stream)))
         return st
 
 
