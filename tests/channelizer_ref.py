@@ -82,3 +82,46 @@ def channelizer_model_f32(x, nchan, hop, proto, chunk=512):
 
 def err(y, ref):
     return float(np.max(np.abs(np.asarray(y, np.complex128) - ref)) / np.max(np.abs(ref)))
+
+
+# The weak-channel tests: a tone of amplitude 0.7 on one channel's centre and one 80 dB below it on another's, and the
+# weak channel's error taken relative to its own reference value, row by row.  WEAK_MODEL_WORST is the independent float32
+# model's worst over every (M, P, D) and the WEAK_CASES placements (tests/test_channelizer_cpu.py::test_weak_channel_model
+# re-measures it): 1.4e-5 .. 2.67e-4, worst at M = 4096, P = 1, rounded up.  TOL_WEAK_CHAN = 7 x that, the factor of TOL,
+# for the same reason; it is never taken from k_channelize.
+WEAK_CASES = 8
+WEAK_ROWS = 41
+WEAK_MODEL_WORST = 2.8e-4
+TOL_WEAK_CHAN = 7 * WEAK_MODEL_WORST
+
+
+def weak_channels(nchan, seed=5):
+    """WEAK_CASES pairs (strong channel, weak channel), the first pair fixed, the others seeded.  At least 8 channels apart
+    as the scope's pairs are -- in fact at least 5 M / 16: with one tap per branch the Kaiser prototype's side lobes are
+    still -109 dB 57 channels from a tone, which puts 0.3 dB of the strong tone into a weak channel there; they fall with
+    the third power of the distance, and from 5 M / 16 on they move the weak channel by less than 0.005 dB at every M."""
+    rng = np.random.default_rng(seed + nchan)
+    pairs = [(nchan // 8 + 3, nchan // 2 + 9)]
+    while len(pairs) < WEAK_CASES:
+        ks = int(rng.integers(0, nchan))
+        pairs.append((ks, (ks + int(rng.integers(5 * nchan // 16, nchan - 5 * nchan // 16 + 1))) % nchan))
+    return pairs
+
+
+def far_channel(nchan, ks, kw):
+    """a channel far from both: half the band from the strong one, or a quarter where the weak one sits there"""
+    apart = lambda a, b: min((a - b) % nchan, (b - a) % nchan)
+    return next(k for k in ((ks + nchan // 2) % nchan, (ks + nchan // 4) % nchan) if apart(k, kw) >= 8)
+
+
+def weak_packed(O, nchan, taps_per_branch, hop, ks, kw):
+    """packed 24-bit samples of 0.7 exp(2 pi i ks n / M) + 0.7e-4 exp(2 pi i kw n / M), P M + 40 hop of them: WEAK_ROWS rows"""
+    import spectrum_ref
+    n = taps_per_branch * nchan + (WEAK_ROWS - 1) * hop
+    return spectrum_ref.tone_packed(O, n, nchan, [(0.7, ks), (0.7e-4, kw)])
+
+
+def weak_err(y, ref, kw):
+    """max over the rows of |y[s, kw] - ref[s, kw]| / |ref[s, kw]|"""
+    y, ref = np.asarray(y, np.complex128), np.asarray(ref, np.complex128)
+    return float(np.max(np.abs(y[:, kw] - ref[:, kw]) / np.abs(ref[:, kw])))

@@ -82,6 +82,30 @@ def dbfs(P, nseg, window):
         return 10.0 * np.log10(np.asarray(P, np.float64) / (nseg * w.sum() ** 2))
 
 
+LEVEL_CASES = 8
+
+
+def level_pairs(nfft, seed=9):
+    """The placements of the level tests: LEVEL_CASES pairs (strong bin, weak bin), at least 8 bins apart; the first is
+    (floor(0.23 N), N - floor(0.11 N)), the others are seeded"""
+    rng = np.random.default_rng(seed + nfft)
+    pairs = [(int(0.23 * nfft), nfft - int(0.11 * nfft))]
+    while len(pairs) < LEVEL_CASES:
+        k1 = int(rng.integers(0, nfft))
+        pairs.append((k1, (k1 + int(rng.integers(8, nfft - 8))) % nfft))
+    return pairs
+
+
+def levels(d, k1, k2):
+    """dBFS per bin -> (strong bin minus 20 log10(0.9), weak bin minus the level 100 dB below that, the highest bin
+    further than 3 from either)"""
+    nfft = len(d)
+    far = np.ones(nfft, bool)
+    for k in (k1, k2):
+        far[(k + np.arange(-3, 4)) % nfft] = False
+    return d[k1] - 20 * np.log10(0.9), d[k2] - (20 * np.log10(0.9) - 100.0), d[far].max()
+
+
 def ragged_cuts(total, nfft, seed):
     """batch sizes (multiples of 8) from 8 to 3 nfft samples that add up to `total`"""
     rng = np.random.default_rng(seed)

@@ -140,3 +140,29 @@ def test_float32_model_against_double(lcg19):
     print(f"worst {worst:.3e}, 7 x worst {7 * worst:.3e}, TOL {CR.TOL:.3e}")
     assert 7 * worst <= 3e-6
     assert worst <= 1.005 * CR.MODEL_WORST      # (three digits were written down)
+
+
+def test_weak_channel_model(O):
+    """A tone of 0.7 on one channel's centre and one 80 dB below it on another's (channelizer_ref.weak_channels: eight
+    placements per M), 41 rows, the Kaiser prototype, every (M, P, D): the independent float32 model's error on the weak
+    channel relative to that channel's own reference value, the worst row.  Its worst is WEAK_MODEL_WORST, which sets the
+    GPU test's TOL_WEAK_CHAN = 7 x that.  On the reference alone: the weak channel stands 80 dB below the strong one
+    within 0.01 dB in every row (the rest is the 24-bit quantisation of the two tones)."""
+    worst = 0.0
+    for M, P, D in CR.combos():
+        w = CR.kaiser_prototype(M, P)
+        e = 0.0
+        for ks, kw in CR.weak_channels(M):
+            assert min((ks - kw) % M, (kw - ks) % M) >= 8 and CR.far_channel(M, ks, kw) not in (ks, kw)
+            x = R.to_complex(O, CR.weak_packed(O, M, P, D, ks, kw))
+            ref = CR.channelizer_ref(x, M, D, w)
+            assert ref.shape == (CR.WEAK_ROWS, M)
+            dist = 20 * np.log10(np.abs(ref[:, ks]) / np.abs(ref[:, kw]))
+            assert np.max(np.abs(dist - 80.0)) <= 0.01, (M, P, D, ks, kw)
+            e = max(e, CR.weak_err(CR.channelizer_model_f32(x, M, D, w), ref, kw))
+        print(f"float32 model, weak channel, M {M} P {P} D {D}: {e:.2e}")
+        worst = max(worst, e)
+    print(f"worst {worst:.3e}, WEAK_MODEL_WORST {CR.WEAK_MODEL_WORST:.1e}, TOL_WEAK_CHAN {CR.TOL_WEAK_CHAN:.2e}")
+    assert worst <= 1e-3                               # beyond that the inputs would be badly chosen
+    assert CR.WEAK_MODEL_WORST / 2 < worst <= CR.WEAK_MODEL_WORST
+    assert CR.TOL_WEAK_CHAN == 7 * CR.WEAK_MODEL_WORST

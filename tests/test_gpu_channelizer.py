@@ -79,6 +79,43 @@ def test_parity(pkg, O, dev, lcg19, nchan, half):
             assert same, (P, name)
 
 
+@pytest.mark.parametrize("combo", CR.combos(), ids=lambda c: "-".join(map(str, c)))
+def test_weak_channel(pkg, O, dev, combo):
+    """A tone of 0.7 on one channel's centre and one 80 dB below it on another's, 24-bit, the Kaiser prototype, 41 rows in
+    one batch, the eight placements of channelizer_ref.weak_channels: in every row the weak channel is within
+    TOL_WEAK_CHAN of its own reference value and the strong one within TOL of its own; the whole matrix is within TOL in
+    test_parity's metric (which bounds the far channels); ragged batches give the bits of the one batch; and the list
+    form over [weak, strong, a far channel] gives the bits of those columns.
+    TOL_WEAK_CHAN = 7 x the independent float32 model's worst on these inputs, 2.67e-4 at M = 4096, P = 1
+    (tests/test_channelizer_cpu.py::test_weak_channel_model re-measures it)."""
+    import torch
+    M, P, D = combo
+    w = CR.kaiser_prototype(M, P)
+    worst = dict(weak=0.0, strong=0.0, matrix=0.0)
+    for r, (ks, kw) in enumerate(CR.weak_channels(M)):
+        packed = CR.weak_packed(O, M, P, D, ks, kw)
+        ref = CR.channelizer_ref(R.to_complex(O, packed), M, D, w)
+        d = torch.from_numpy(packed).to(dev)
+        y1 = run(pkg, d, M, D, w)
+        y = y1.cpu().numpy()
+        assert y.shape == ref.shape == (CR.WEAK_ROWS, M)
+        figs = dict(weak=CR.weak_err(y, ref, kw), strong=CR.weak_err(y, ref, ks), matrix=CR.err(y, ref))
+        worst = {k: max(v, figs[k]) for k, v in worst.items()}
+        assert figs["weak"] <= CR.TOL_WEAK_CHAN, (ks, kw, figs)
+        assert figs["strong"] <= TOL and figs["matrix"] <= TOL, (ks, kw, figs)
+        y2 = run(pkg, d, M, D, w, cuts=R.ragged_cuts(packed.size // 6, M, 7 + M + P + r))
+        assert y1.shape == y2.shape and torch.equal(bits(y1), bits(y2)), (ks, kw)
+        cols = [kw, ks, CR.far_channel(M, ks, kw)]
+        ch = pkg.Channelizer(M, w, D)
+        ch.set_channels(cols)
+        yl = ch.process(d)
+        torch.cuda.synchronize()
+        ch.close()
+        assert yl.shape == (CR.WEAK_ROWS, 3) and torch.equal(bits(yl), bits(y1[:, cols])), (ks, kw)
+    print(f"weak channel, M {M} P {P} D {D}: weak channel off by {worst['weak']:.2e} of itself (TOL_WEAK_CHAN "
+          f"{CR.TOL_WEAK_CHAN:.2e}), strong {worst['strong']:.2e}, matrix {worst['matrix']:.2e} (TOL {TOL:.2e})")
+
+
 def test_batches_shorter_than_the_prototype(pkg, dev, lcg19):
     import torch
     packed, x = lcg19

@@ -66,15 +66,16 @@ def test_against_the_reference(pkg, dev, size):
 @pytest.mark.parametrize("size", SR.CUT_SIZES, ids=lambda s: "-".join(map(str, s)))
 def test_cut_and_company(pkg, dev, size):
     """Bit for bit: one batch against the cut list (0, 1, hop - 1, hop, hop + 1, nfft - 1, nfft, avg hop, ...), the list
-    reversed and a seeded ragged list; 1024 slots against 7, 5 and 1 (counts on either side of the kernel's items per
-    block); the slot order reversed; a slot alone against itself among 1024; two slots on one row."""
+    reversed and a seeded ragged list; 1024 slots (256 at 2048 and 4096, the plans of 2 and 4 waves per transform)
+    against 7, 5 and 1 (counts on either side of the kernel's items per block); the slot order reversed; a slot alone
+    against itself among them all; two slots on one row."""
     nfft, hop, avg = size
     z, zd, w, _ = inputs(size, dev)
     n = z.shape[1]
-    rows = SR.slot_rows(1024)
+    rows = SR.slot_rows(256 if nfft >= 2048 else 1024)
     base = bits(run(pkg, zd, rows, size))
     cuts = SR.gpu_cuts(nfft, hop, avg, n)
-    for name, c in (("cuts", cuts), ("reversed", cuts[::-1]), ("ragged", SR.ragged_cuts(n, nfft, 11))):
+    for name, c in (("cuts", cuts), ("reversed", cuts[::-1]), ("ragged", SR.ragged_cuts(n, nfft, SR.ragged_seed(nfft)))):
         assert np.array_equal(bits(run(pkg, zd, rows, size, c)), base), name
     g = pkg.scope_block_items(nfft)
     assert g == 1 or (7 % g and 5 % g)                 # blocks whose items belong to two line units
@@ -108,6 +109,31 @@ def test_weak_tone(pkg, dev, size):
           f"distance off 80 dB by {worst_db:.4f} dB")
     assert worst <= SR.TOL_WEAK[nfft]
     assert worst_db <= SR.DB_MARGIN
+
+
+def test_repeatability(pkg, dev):
+    """The plans of 2 and 4 waves per transform (2048, 4096) and one of a single wave (1024) as the control, 64 slots, the
+    gpu_series input in gpu_cuts' batches: a fresh object, ten runs after reset() and another fresh object give the same
+    bits in every line."""
+    for size in ((2048, 512, 2), (4096, 1024, 2), (1024, 512, 2)):
+        nfft, hop, avg = size
+        z, zd, w, _ = inputs(size, dev)
+        cuts = SR.gpu_cuts(nfft, hop, avg, z.shape[1])
+        rows = SR.slot_rows(64)
+
+        def once(s):
+            return bits(SR.run_cuts(types.SimpleNamespace(process=lambda b: s.process(b).cpu().numpy()), zd, cuts))
+
+        s = pkg.Scope(SR.NSRC, rows, nfft, hop, avg)
+        first = once(s)
+        assert first.shape == (64, 6, nfft) and first[rows >= 0].any()
+        for i in range(10):
+            s.reset()
+            assert np.array_equal(once(s), first), (size, i)
+        s.close()
+        fresh = pkg.Scope(SR.NSRC, rows, nfft, hop, avg)
+        assert np.array_equal(once(fresh), first), size
+        fresh.close()
 
 
 def test_strides_and_canaries(pkg, dev):
@@ -195,12 +221,11 @@ def test_set_slot_between_batches(pkg, dev, size):
     assert (~want[3].any(axis=-1)).any() and (~want[5].any(axis=-1)).any()
 
 
-def test_a_refused_process_changes_nothing(pkg, dev):
+def refused_calls_change_nothing(pkg, dev, size):
     """Refused calls -- a stride below n, a line stride below the lines due, misaligned z and lines, NULL z, NULL lines
     with lines due, lines overlapping z -- between good batches: the result equals that of an object that never saw them.
     NULL lines when none are due is accepted.  n = 0 and n < nfft on a fresh object work; reset starts the series again."""
     import torch
-    size = SR.CUT_SIZES[0]
     nfft, hop, avg = size
     z, zd, w, _ = inputs(size, dev)
     n, L = z.shape[1], pkg.ddc_lib()
@@ -244,6 +269,18 @@ def test_a_refused_process_changes_nothing(pkg, dev):
     assert again[0].shape == again[1].shape == (16, 0, nfft)
     assert np.array_equal(bits(again[2]), base)
     s.close()
+
+
+def test_a_refused_process_changes_nothing(pkg, dev):
+    """refused_calls_change_nothing at the smallest plan"""
+    refused_calls_change_nothing(pkg, dev, SR.CUT_SIZES[0])
+
+
+def test_a_refused_process_changes_nothing_at_the_largest_plan(pkg, dev):
+    """refused_calls_change_nothing at 4096 / 1024 / 2: the longest carried record and partial line, across refused calls
+    and reset()"""
+    assert (4096, 1024, 2) in SR.CUT_SIZES
+    refused_calls_change_nothing(pkg, dev, (4096, 1024, 2))
 
 
 def test_end_to_end(pkg, dev):

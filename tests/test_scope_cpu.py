@@ -18,7 +18,7 @@ def cut_lists(nfft, hop, avg):
     if (nfft, hop, avg) not in SR.CUT_SIZES:
         return n, [[n]]
     cuts = SR.gpu_cuts(nfft, hop, avg, n)
-    return n, [[n], cuts, cuts[::-1], SR.ragged_cuts(n, nfft, 11)]
+    return n, [[n], cuts, cuts[::-1], SR.ragged_cuts(n, nfft, SR.ragged_seed(nfft))]
 
 
 def test_reference_against_closed_forms():

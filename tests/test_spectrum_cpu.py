@@ -126,6 +126,23 @@ def test_float32_model_against_double(O):
     assert 1e-8 < worst < 1e-5 / 5
 
 
+@pytest.mark.parametrize("nfft", SIZES)
+def test_levels_and_floor_model(O, nfft):
+    """The inputs of tests/test_gpu_spectrum.py::test_levels_and_floor, every placement, through the independent float32
+    model: the three bounds of that test hold -- strong bin within 0.001 dB, weak bin within 0.1 dB, floor below
+    -135 dBFS -- so the inputs alone meet them."""
+    w = R.hann(nfft)
+    pairs = R.level_pairs(nfft)
+    assert len(pairs) == R.LEVEL_CASES and pairs[0] == (int(0.23 * nfft), nfft - int(0.11 * nfft))
+    for k1, k2 in pairs:
+        assert min((k1 - k2) % nfft, (k2 - k1) % nfft) >= 8
+        x = R.to_complex(O, R.tone_packed(O, 64 * nfft, nfft, [(0.9, k1), (0.9 * 1e-5, k2)]))
+        P = R.spectrum_model_f32(x, nfft, nfft, w)
+        strong, weak, floor = R.levels(R.dbfs(P, 64, w), k1, k2)
+        print(f"float32 model N {nfft} bins {k1} / {k2}: strong {strong:+.5f} dB, weak {weak:+.4f} dB, floor {floor:.1f} dBFS")
+        assert abs(strong) <= 0.001 and abs(weak) <= 0.1 and floor <= -135.0, (k1, k2)
+
+
 def test_float32_model_with_the_kernels_partial_sums(O):
     """Full-size structure (tests/test_gpu_spectrum.py::test_full_size): 65 536 segments of 4096 go to 512 float32 partial
     rows of 128 segments each (row = segment mod 512), added in double.  Measured on 2^24 samples of the LCG stream cut
