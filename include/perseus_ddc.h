@@ -1500,6 +1500,115 @@ int pddc_fsk_read(pddc_fsk *f, pddc_fsk_status *host /* [nrx] */, void *stream);
 /* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_fsk_tile_outputs(void);
 
+/* ---- morse: CW (on-off keyed Morse) decoding per receiver -------------------------
+ * Beside the chain, where fsk sits: it reads the rows the tuner, blanker, receiver filter and carrier
+ * write, and gives characters, not samples.  K receivers (1 .. 1024), a window length W (1 .. 256), a
+ * bank of B keyers (1 .. 16), copied at create.  Keyer b: h[W], real float32 taps of the envelope
+ * filter, every value finite; two0, two_min, two_max, uint32: the length of TWO dots in samples times
+ * 256, the start value and the bounds of the speed tracker, 512 <= two_min <= two0 <= two_max <= 2^28;
+ * shift, 0 .. 8, the tracker's time constant.  Common to the object, float32: a_on, a_off
+ * (0 < a_off <= a_on < 1), the thresholds' places between floor and peak; rel, relf in [0, 1], the
+ * release of peak and floor per block; ratio >= 1, the least peak over floor that counts as a signal.
+ * Receiver j: a keyer index and flags PDDC_MORSE_ON, _FIXED (no speed tracking), _RESTART.
+ * Input per batch: z[j z_stride + i], i < n, complex float32, any row stride, n >= 0.  m counts the
+ * object's samples since create / reset (every batch adds n, for every receiver); inputs before a
+ * receiver's first are zero.  Every float operation below is one float32 operation in the stated
+ * order, contraction off; all timing is in integers.
+ * 1. Envelope, for every sample m of an ON receiver: y = sum over t = 0 .. W-1 of h[t] z[m - t], from
+ *    (0, 0) with t ascending, per tap re = fmaf(h, zr, re); im = fmaf(h, zi, im).  p = fmaf(yi, yi, yr yr);
+ *    if !(p <= FLT_MAX) then p = 0: a NaN or an infinity in the window reads as no signal, nothing
+ *    non-finite reaches a tracker, and nothing is left behind once the sample has left the window.
+ * 2. Key: key = p > on ? 1 : (p < off ? 0 : key_prev); on = off = +inf before the first block ends.
+ * 3. Block meter, behind the sample's key and timing.  Blocks are the 64 samples with the same m >> 6,
+ *    absolute in m.  Carried: hi (initially 0), lo (+inf), pk, fl, primed.  Every sample: hi =
+ *    fmaxf(hi, p); lo = fminf(lo, p).  On a block's last sample (m & 63 == 63): if not primed: pk = hi,
+ *    fl = lo, primed; otherwise pk = fmaxf(hi, fmaf(rel, fl - pk, pk)); fl = fminf(lo, fmaf(relf, pk - fl,
+ *    fl)), the new pk in fl.  span = pk - fl.  If pk >= ratio * fl && span > 0: on = fmaf(a_on, span, fl),
+ *    off = fmaf(a_off, span, fl); otherwise on = off = +inf.  Then hi = 0, lo = +inf.  So block k's levels
+ *    govern block k + 1, and the elements in the first block of a transmission are lost.
+ * 4. Element timing, with prev the previous sample's key.  Carried: two, nel, code (initially 1, a
+ *    sentinel), start, word, first (initially 1), t_up, t_down, last (initially 0), the counters.
+ *    In this order:
+ *    a. if !prev && nel > 0 && m - t_up == ((two + 255) >> 8): the character {start, code, nel, flags,
+ *       two} is emitted, flags = (word ? PDDC_MORSE_WORD : 0) | (nel > 15 ? PDDC_MORSE_LONG : 0); chars++;
+ *       nel = 0; code = 1.
+ *    b. rising edge (key && !prev): t_down = m; if nel == 0: start = m and word = first ||
+ *       ((m - t_up) << 9) >= 5 two in uint64 (m - t_up taken as at most 2^40), a gap of at least five dots.
+ *    c. falling edge (!key && prev): dur = min(m - t_down, 2^24); dash = (dur << 8) >= two; if nel < 15:
+ *       code = code << 1 | dash; nel saturates at 255; marks++.  Unless FIXED, and only if last > 0: a =
+ *       min(dur, last), b = max(dur, last); if b >= 2 a && b <= 4 a (a dot beside a dash, whose sum is two
+ *       dots whatever the speed): two += (((a + b) << 7) - two) >> shift in signed 64 bits with an
+ *       arithmetic shift, then clamped to [two_min, two_max].  last = dur; t_up = m; first = 0.
+ *    A dash is a mark of at least two dots, a character gap a space of at least two dots.  code holds
+ *    the first 15 elements, the first highest, dash = 1, under a leading 1 ("A", dot dash: binary 101).
+ * Receiver control.  An OFF receiver is not read and does not advance: its count is 0, its p row, if
+ * one is asked for, is written +0.  set_rx(rx, keyer, flags) takes effect at the next batch's first
+ * sample.  RESTART, or a change from OFF to ON: the carried inputs are zero, the meter is unprimed with
+ * hi, lo and the thresholds as at create, key = 0, the timing is as at create with two = the keyer's
+ * two0; the counters stay.  Another keyer: the same, but the carried inputs stay.  reset() clears
+ * everything and m, and synchronises the device.
+ * Outputs of process(), all device memory, no host synchronisation: chars [nrx][char_stride], the
+ * characters whose emission sample lies in this batch, in order; counts uint32 [nrx]; p float32
+ * [nrx][p_stride] or NULL, the envelope power, one value per input.
+ * Capacity: pddc_morse_max_chars(f, n, &count) is host arithmetic: two emissions lie at least D = 1 +
+ * ((two_min + 255) >> 8) samples apart, D the least over the bank, so n samples end at most
+ * (n - 1) div D + 1 characters (0 for n = 0; DESIGN.md 4, "Morse decoder", derives it).  A char_stride
+ * below it is PDDC_ECAPACITY, and nothing is queued.
+ * process(): every argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned
+ * pointer (z and chars 8 bytes, counts and p 4; p may be NULL; with n = 0 z and chars are not looked at
+ * and counts may be NULL), PDDC_ECAPACITY for a stride below n or below the bound, PDDC_EINVAL when an
+ * output's byte range meets the input's.  n = 0 is valid: counts, if given, is set to 0, nothing
+ * carried moves, marks of set_rx stay for the next batch.  State moves only after the launch was
+ * accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * read(): per receiver chars and marks (since create / reset), two, nel, key, and pk, fl (0 until the
+ * meter is primed) behind the batches submitted so far (it waits for them).
+ * Every bit of chars, counts, p and the status is independent of the cut into batches (n = 0 and n = 1
+ * included), nrx, j's index, the other receivers, strides, grid and tile sizes.
+ * create: argument errors before any device access (non-finite taps, a keyer or a parameter out of
+ * range, a bad keyer index, unknown flag bits); good arguments, no device: PDDC_ENODEV. */
+#define PDDC_MORSE_ON       0x1u
+#define PDDC_MORSE_FIXED    0x2u   /* the keyer's two0 throughout: no speed tracking */
+#define PDDC_MORSE_RESTART  0x4u   /* set_rx: start this receiver afresh          */
+#define PDDC_MORSE_WORD     0x1    /* pddc_morse_char.flags: the first character, or one behind a gap of five dots */
+#define PDDC_MORSE_LONG     0x2    /* more than 15 elements: code holds the first 15 */
+typedef struct pddc_morse_keyer {
+    uint32_t two0, two_min, two_max;   /* two dots in samples, times 256        */
+    uint32_t shift;                    /* 0 .. 8                                */
+} pddc_morse_keyer;
+typedef struct pddc_morse_params {
+    float a_on, a_off, rel, relf, ratio;
+} pddc_morse_params;
+typedef struct pddc_morse_rx {
+    int keyer;            /* 0 .. nkeyers - 1                             */
+    uint32_t flags;       /* PDDC_MORSE_ON | _FIXED | _RESTART            */
+} pddc_morse_rx;
+typedef struct pddc_morse_char {
+    uint64_t start;       /* sample index m of the first element's rising edge */
+    uint16_t code;        /* 1, then an element per bit, dash = 1         */
+    uint8_t nel;          /* elements, saturating at 255                  */
+    uint8_t flags;        /* PDDC_MORSE_WORD | _LONG                      */
+    uint32_t two;         /* the tracker's two dots at the emission       */
+} pddc_morse_char;
+typedef struct pddc_morse_status {
+    uint32_t chars, marks;
+    uint32_t two, nel, key;
+    float pk, fl;
+} pddc_morse_status;
+typedef struct pddc_morse pddc_morse;
+int pddc_morse_create(pddc_morse **out, int device, int nrx, int window, int nkeyers,
+                      const float *taps /* [nkeyers][window]; copied */, const pddc_morse_keyer *keyers /* [nkeyers] */,
+                      const pddc_morse_params *par, const pddc_morse_rx *rx /* [nrx] */);
+int pddc_morse_destroy(pddc_morse *f);
+int pddc_morse_reset(pddc_morse *f);                  /* m and everything carried; synchronises the device */
+int pddc_morse_set_rx(pddc_morse *f, int rx, int keyer, uint32_t flags);
+int pddc_morse_max_chars(const pddc_morse *f, size_t n, size_t *count);
+int pddc_morse_process(pddc_morse *f, const void *d_z, size_t n, size_t z_stride, void *d_chars, size_t char_stride,
+                       void *d_counts, void *d_p, size_t p_stride, void *stream);
+/* status[nrx] after the batches submitted so far (it waits for them) */
+int pddc_morse_read(pddc_morse *f, pddc_morse_status *host /* [nrx] */, void *stream);
+/* samples per tile of the kernel's walk, aligned to m (for tests that place batch cuts on its seams) */
+int pddc_morse_tile_outputs(void);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------- */
 /* Times `iters` back-to-back launches of the pipeline's stage-0 kernel alone
  * with HIP events on `stream`; returns average milliseconds per launch.

@@ -136,6 +136,21 @@ class FskRx(C.Structure):
     _fields_ = [("modem", C.c_int), ("flags", C.c_uint32)]
 
 
+class MorseRx(C.Structure):
+    """pddc_morse_rx"""
+    _fields_ = [("keyer", C.c_int), ("flags", C.c_uint32)]
+
+
+class MorseKeyer(C.Structure):
+    """pddc_morse_keyer"""
+    _fields_ = [("two0", C.c_uint32), ("two_min", C.c_uint32), ("two_max", C.c_uint32), ("shift", C.c_uint32)]
+
+
+class MorseParams(C.Structure):
+    """pddc_morse_params"""
+    _fields_ = [("a_on", C.c_float), ("a_off", C.c_float), ("rel", C.c_float), ("relf", C.c_float), ("ratio", C.c_float)]
+
+
 class BlankerParams(C.Structure):
     """pddc_blanker_params (include/perseus_ddc.h)"""
     _fields_ = [("block", C.c_int), ("guard", C.c_int), ("ramp", C.c_int), ("beta", C.c_float), ("cap", C.c_float)]
@@ -446,6 +461,18 @@ def ddc_lib() -> C.CDLL:
     L.pddc_fsk_tile_outputs.argtypes = []
     for name in ("pddc_fsk_create", "pddc_fsk_destroy", "pddc_fsk_reset", "pddc_fsk_set_rx", "pddc_fsk_max_chars",
                  "pddc_fsk_process", "pddc_fsk_read", "pddc_fsk_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_morse_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(MorseKeyer),
+                                    C.POINTER(MorseParams), C.POINTER(MorseRx)]
+    L.pddc_morse_destroy.argtypes = [vp]
+    L.pddc_morse_reset.argtypes = [vp]
+    L.pddc_morse_set_rx.argtypes = [vp, C.c_int, C.c_int, C.c_uint32]
+    L.pddc_morse_max_chars.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_morse_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]
+    L.pddc_morse_read.argtypes = [vp, vp, vp]
+    L.pddc_morse_tile_outputs.argtypes = []
+    for name in ("pddc_morse_create", "pddc_morse_destroy", "pddc_morse_reset", "pddc_morse_set_rx", "pddc_morse_max_chars",
+                 "pddc_morse_process", "pddc_morse_read", "pddc_morse_tile_outputs"):
         getattr(L, name).restype = C.c_int
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
@@ -961,7 +988,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer and Fsk share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk and Morse share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -2332,6 +2359,151 @@ class Fsk(_StreamObject):
         import numpy as np
         st = np.zeros(self.nrx, dtype=fsk_status_dtype())
         check(ddc_lib().pddc_fsk_read(self._h, st.ctypes.data, self._stream(stream)))
+        return st
+
+
+PDDC_MORSE_ON, PDDC_MORSE_FIXED, PDDC_MORSE_RESTART = 0x1, 0x2, 0x4
+PDDC_MORSE_WORD, PDDC_MORSE_LONG = 0x1, 0x2
+
+
+def morse_tile_outputs() -> int:
+    """pddc_morse_tile_outputs: samples per tile of the kernel's walk (tiles are aligned to the object's sample count);
+    host arithmetic, no device"""
+    return int(ddc_lib().pddc_morse_tile_outputs())
+
+
+def morse_char_dtype():
+    """pddc_morse_char as a numpy structured dtype (16 bytes)"""
+    import numpy as np
+    return np.dtype([("start", np.uint64), ("code", np.uint16), ("nel", np.uint8), ("flags", np.uint8), ("two", np.uint32)])
+
+
+def morse_status_dtype():
+    """pddc_morse_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("chars", np.uint32), ("marks", np.uint32), ("two", np.uint32), ("nel", np.uint32), ("key", np.uint32),
+                     ("pk", np.float32), ("fl", np.float32)])
+
+
+def morse_keyer(rate_hz: float, wpm: float, W: int, wpm_min: float = 5, wpm_max: float = 60, shift: int = 2):
+    """A keyer for Morse's bank.  A dot lasts 1.2 / wpm seconds (PARIS), so two dots are 2.4 rate_hz / wpm samples: two0 at
+    wpm, two_min at wpm_max and two_max at wpm_min, each round(256 x that) and brought into 512 .. 2^28 with two_min <=
+    two0 <= two_max.  The taps are a Hann window over L = min(W, max(1, round(0.6 rate_hz / wpm))) samples, about half
+    a dot at wpm, w[t] = 1 - cos(2 pi (t + 1) / (L + 1)), of unit sum, computed in double and rounded once, zero
+    beyond.  -> (h float32[W], two0, two_min, two_max, shift)"""
+    import numpy as np
+    W, rate, wpm = int(W), float(rate_hz), float(wpm)
+    if W <= 0 or not rate > 0.0 or not wpm > 0.0 or not 0.0 < float(wpm_min) <= float(wpm_max):
+        raise PddcError(-1, "morse_keyer: W, the rate and the speeds must be positive, wpm_min <= wpm_max")
+    L = min(W, max(1, int(round(0.6 * rate / wpm))))
+    t = np.arange(W, dtype=np.float64)
+    w = np.where(t < L, 1.0 - np.cos(2.0 * np.pi * (t + 1.0) / (L + 1.0)), 0.0)
+    two = [min(max(int(round(256.0 * 2.4 * rate / float(v))), 512), 1 << 28) for v in (wpm, wpm_max, wpm_min)]
+    return (w / w.sum()).astype(np.float32), min(max(two[0], two[1]), two[2]), two[1], two[2], int(shift)
+
+
+_MORSE_ITU = {".-": "A", "-...": "B", "-.-.": "C", "-..": "D", ".": "E", "..-.": "F", "--.": "G", "....": "H", "..": "I",
+              ".---": "J", "-.-": "K", ".-..": "L", "--": "M", "-.": "N", "---": "O", ".--.": "P", "--.-": "Q", ".-.": "R",
+              "...": "S", "-": "T", "..-": "U", "...-": "V", ".--": "W", "-..-": "X", "-.--": "Y", "--..": "Z",
+              "-----": "0", ".----": "1", "..---": "2", "...--": "3", "....-": "4", ".....": "5", "-....": "6", "--...": "7",
+              "---..": "8", "----.": "9", ".-.-.-": ".", "--..--": ",", "---...": ":", "..--..": "?", ".----.": "'", "-....-": "-",
+              "-..-.": "/", "-.--.": "(", "-.--.-": ")", ".-..-.": '"', "-...-": "=", ".-.-.": "+", ".--.-.": "@", "..-..": "\u00c9"}
+_MORSE_CODES = {int("1" + k.replace(".", "0").replace("-", "1"), 2): v for k, v in _MORSE_ITU.items()}
+
+
+def morse_text(records) -> str:
+    """The text of pddc_morse_char records (a numpy array of morse_char_dtype, or any sequence of records with code and
+    flags), host only: the ITU table (letters, figures, punctuation, accented E), `?` for a code it does not hold or a
+    character with PDDC_MORSE_LONG, a space in front of every character with PDDC_MORSE_WORD but the first."""
+    out = []
+    for i, c in enumerate(records):
+        flags = int(c["flags"])
+        if flags & PDDC_MORSE_WORD and i:
+            out.append(" ")
+        out.append("?" if flags & PDDC_MORSE_LONG else _MORSE_CODES.get(int(c["code"]), "?"))
+    return "".join(out)
+
+
+class Morse(_StreamObject):
+    """pddc_morse: CW decoding of every receiver's complex series, such as Tuner, Blanker, RxFilter or Carrier write, on the
+    device (include/perseus_ddc.h): a real envelope filter of W taps, a block meter that places two thresholds between
+    floor and peak, and the element timing with a speed tracker per receiver; the output is characters, not samples.
+    bank: up to 16 keyers (h, two0, two_min, two_max, shift), as morse_keyer gives them, every h of W taps; sel: one
+    (keyer, flags) per receiver, flags PDDC_MORSE_ON | PDDC_MORSE_FIXED.  Feed it every batch in order on one stream;
+    every output bit is the same however the series is cut."""
+    _kind = "morse"
+
+    def __init__(self, bank, sel, W: int, a_on: float = 0.5, a_off: float = 0.3, rel: float = 1.0 / 16, relf: float = 1.0 / 64,
+                 ratio: float = 4.0, device: int = 0):
+        import numpy as np
+        bank = [tuple(b) for b in bank]
+        sel = [tuple(r) for r in sel]
+        self.W, self.nrx, self.nkeyers, self.device = int(W), len(sel), len(bank), device
+        taps = np.zeros((max(self.nkeyers, 1), max(self.W, 1)), np.float32)
+        keyers = (MorseKeyer * max(self.nkeyers, 1))()
+        u32 = lambda v: max(0, min(int(v), (1 << 32) - 1))
+        for b, (h, two0, two_min, two_max, shift) in enumerate(bank):
+            h = np.asarray(h, dtype=np.float32).reshape(-1)
+            if h.size != self.W:
+                raise PddcError(-1, f"morse: keyer {b}: {h.size} taps for a window of {self.W}")
+            taps[b] = h
+            keyers[b] = MorseKeyer(u32(two0), u32(two_min), u32(two_max), u32(shift))
+        arr = (MorseRx * max(self.nrx, 1))()
+        for j, (keyer, flags) in enumerate(sel):
+            arr[j] = MorseRx(_clip(keyer), int(flags) & 0xFFFFFFFF)
+        par = MorseParams(a_on, a_off, rel, relf, ratio)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_morse_create(C.byref(h), device, self.nrx, _clip(W), self.nkeyers,
+                                          taps.ctypes.data_as(C.POINTER(C.c_float)), keyers, C.byref(par), arr))
+        self._h = h
+
+    def max_chars(self, n: int) -> int:
+        """pddc_morse_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_morse_max_chars(self._h, int(n), C.byref(c)))
+        return int(c.value)
+
+    def process(self, z, chars=None, counts=None, p=None, want_p: bool = False, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (chars, counts) or,
+        with want_p or p given, (chars, counts, p): chars int32 [nrx, capacity, 4], four words per pddc_morse_char
+        (`.cpu().numpy().view(morse_char_dtype())[..., 0]` gives the records), of which the first counts[j] (int32 [nrx])
+        of row j are written; p float32 [nrx, n], the envelope power.  chars, counts and p, if given, are tensors of
+        these kinds (chars and p with any capacity that suffices); no output may overlap z."""
+        import torch
+        if not self._rows(z, torch.complex64):
+            raise PddcError(-1, "morse: z must be a complex64 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        dev = torch.device("cuda", self.device)
+        if chars is None:
+            chars = torch.empty((self.nrx, max(self.max_chars(n), 1), 4), dtype=torch.int32, device=dev)
+        elif not (chars.dtype == torch.int32 and chars.dim() == 3 and chars.shape[0] == self.nrx and chars.shape[2] == 4
+                  and chars[0].is_contiguous()):
+            raise PddcError(-1, "morse: chars must be an int32 tensor [nrx, capacity, 4] with contiguous rows")
+        if counts is None:
+            counts = torch.empty((self.nrx,), dtype=torch.int32, device=dev)
+        elif not (counts.dtype == torch.int32 and counts.dim() == 1 and counts.shape[0] == self.nrx and counts.is_contiguous()):
+            raise PddcError(-1, "morse: counts must be a contiguous int32 tensor [nrx]")
+        pcap = 0
+        if p is not None or want_p:
+            p, pcap = self._out(p, n, torch.float32, "p must be a float32")
+        # the ABI takes the row stride in characters; a capacity below the bound must reach it as one (PDDC_ECAPACITY)
+        ccap = int(chars.stride(0)) // 4 if chars.shape[1] >= self.max_chars(n) else int(chars.shape[1])
+        check(ddc_lib().pddc_morse_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                           chars.data_ptr() if chars.numel() else None, ccap, counts.data_ptr(),
+                                           p.data_ptr() if p is not None and p.numel() else None, pcap, self._stream(stream)))
+        return (chars, counts) if p is None else (chars, counts, p[:, :n])
+
+    def set_rx(self, rx: int, keyer: int, flags: int):
+        """receiver rx from the next batch's first sample on: PDDC_MORSE_RESTART, or OFF -> ON, starts it afresh (the
+        counters stay); another keyer does the same but keeps the carried inputs"""
+        check(ddc_lib().pddc_morse_set_rx(self._h, int(rx), _clip(keyer), int(flags) & 0xFFFFFFFF))
+
+    def read(self, stream=None):
+        """-> numpy structured array [nrx] (chars, marks, two, nel, key, pk, fl) after the batches submitted so far (it
+        waits for them)"""
+        import numpy as np
+        st = np.zeros(self.nrx, dtype=morse_status_dtype())
+        check(ddc_lib().pddc_morse_read(self._h, st.ctypes.data, self._stream(stream)))
         return st
 
 
