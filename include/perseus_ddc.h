@@ -1609,6 +1609,105 @@ int pddc_morse_read(pddc_morse *f, pddc_morse_status *host /* [nrx] */, void *st
 /* samples per tile of the kernel's walk, aligned to m (for tests that place batch cuts on its seams) */
 int pddc_morse_tile_outputs(void);
 
+/* ---- psk: differential BPSK (PSK31 / 63 / 125) decoding per receiver ---------------
+ * Beside the chain, where fsk and morse sit: it reads the rows the tuner, blanker, receiver filter and
+ * carrier write, and gives Varicode characters.  Where this block is silent, fsk's rules hold.
+ * K receivers (1 .. 1024), a window length W (1 .. 256), a bank of B modems (1 .. 16), copied at
+ * create.  Modem b: h[W], real float32 taps of the matched filter, every value finite; inc, uint32 in
+ * 1 .. 2^29: the symbol phase advanced per sample, 2^32 baud / rate, so a symbol is at least 8 samples;
+ * q in 1 .. 64 with 4 q inc <= 2^32: the early and late offset in samples, about a quarter symbol;
+ * step, uint32 in 0 .. inc: the clock correction per reversal, 0 is a fixed clock.  Receiver j: a modem
+ * index and flags PDDC_PSK_ON, _RESTART.
+ * Input per batch: z[j z_stride + i], i < n, complex float32, any row stride, n >= 0.  m counts the
+ * object's samples since create / reset.  Every float operation below is one float32 operation in the
+ * stated order, contraction off; the clock and the framing are integers.
+ * 1. Filter, for every sample m of an ON receiver: y[m] = sum over t = 0 .. W-1 of h[t] z[m - t], from
+ *    (0, 0) with t ascending, per tap re = fmaf(h, zr, re); im = fmaf(h, zi, im).  p[m] = fmaf(yi, yi,
+ *    yr yr).  z, y and p at samples before the receiver's first are +0.
+ * 2. Clock.  Carried: acc, uint32, 0 at the start.  Each sample: a2 = acc + inc mod 2^32; a strobe iff
+ *    a2 < acc; acc = a2.
+ * 3. On a strobe at sample m, with c = m - q the on-time sample, e = m - 2 q the early one and m the
+ *    late one.  u = y[c], pu = p[c]; carried v, pv: the previous strobe's u and pu, zero at the start.
+ *    dot = fmaf(ui, vi, ur vr); cross = fmaf(ui, vr, -(ur vi)); s = pu + pv; d = s > 0 ? (dot + dot) / s
+ *    : 0; x = s > 0 ? (cross + cross) / s : 0, both divisions correctly rounded.  bit = dot > 0: no
+ *    reversal is 1, and a NaN reads as 0, the idle bit.
+ *    Clock correction, on a reversal (bit == 0) only -- a run of ones has a flat envelope and nothing to
+ *    time: if p[m] > p[e], the peak lies later: acc = acc >= step ? acc - step : 0; otherwise, if
+ *    p[e] > p[m]: acc = acc + step (no overflow: acc < inc behind a strobe).  A NaN moves nothing.
+ *    Framing.  Carried: reg (uint32, 0), nb (saturates at 255), qmin, start.  If reg == 0 and bit == 0:
+ *    nothing.  Otherwise: if reg == 0: start = c, nb = 0, qmin = |d|.  reg = reg << 1 | bit; ++nb; qmin =
+ *    fminf(qmin, |d|).  If (reg & 3) == 0: the character {start, code = (reg >> 2) & 0xFFFF, nbits =
+ *    nb - 2, flags = (nb - 2 > 16 ? PDDC_PSK_LONG : 0), quality = qmin} is emitted; chars++; reg = 0.
+ *    Then v = u, pv = pu, symbols++.
+ *    code is the Varicode character as sent, the first bit highest ("e" is binary 11, space is 1).
+ * Receiver control.  An OFF receiver is not read and does not advance: its count and its nsym are 0.
+ * set_rx(rx, modem, flags) takes effect at the next batch's first sample.  RESTART, a change from OFF
+ * to ON and another modem do the same: the carried inputs and filter outputs are zero, the clock, the
+ * differential pair and the framing are as at create; the counters stay.  reset() clears everything and
+ * m, and synchronises the device.
+ * Outputs of process(), all device memory, no host synchronisation: chars [nrx][char_stride], the
+ * characters whose last strobe lies in this batch, in order; counts uint32 [nrx]; sym float2
+ * [nrx][sym_stride] or NULL, one (d, x) per strobe of the batch, in order, with nsym uint32 [nrx]: the
+ * hook for a phase display, for AFC on the host (the angle of (d + j x)^2 is twice the offset's phase
+ * per symbol) and for host decoders of QPSK and FEC modes.
+ * Capacity, host arithmetic.  Behind a strobe acc <= inc - 1 + step, so two strobes lie at least D_b =
+ * floor((2^32 - step_b) / inc_b) samples apart ("PSK decoder", derives it), D the least
+ * over the bank: pddc_psk_max_syms(f, n, &count) gives (n - 1) div D + 1, 0 for n = 0.  Emissions lie
+ * at least 3 strobes apart: pddc_psk_max_chars gives (max_syms - 1) div 3 + 1, 0 for n = 0.  A
+ * char_stride or, with sym, a sym_stride below its bound is PDDC_ECAPACITY, and nothing is queued.
+ * process(): every argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned
+ * pointer (z, chars and sym 8 bytes, counts and nsym 4; sym may be NULL, and nsym is then not looked at
+ * beyond its alignment; with n = 0 z, chars and sym are not looked at and counts and nsym may be NULL),
+ * PDDC_ECAPACITY for a stride below n or below a bound, PDDC_EINVAL when an output's byte range meets
+ * the input's.  n = 0 is valid: counts and nsym, if given, are set to 0, nothing carried moves, marks
+ * of set_rx stay for the next batch.  State moves only after the launch was accepted.  Stream-ordered;
+ * one stream per object, one thread at a time.
+ * read(): per receiver chars and symbols (since create / reset), acc, reg, and the last strobe's d and
+ * x behind the batches submitted so far (it waits for them).
+ * Every bit of chars, counts, sym, nsym and the status is independent of the cut into batches (n = 0
+ * and n = 1 included), nrx, j's index, the other receivers, strides, grid and tile sizes.
+ * create: argument errors before any device access (non-finite taps, a modem out of range, a bad modem
+ * index, unknown flag bits); good arguments, no device: PDDC_ENODEV. */
+#define PDDC_PSK_ON       0x1u
+#define PDDC_PSK_RESTART  0x4u   /* set_rx: start this receiver afresh          */
+#define PDDC_PSK_LONG     0x1    /* pddc_psk_char.flags: more than 16 bits: code holds the last 16 */
+typedef struct pddc_psk_modem {
+    uint32_t inc;         /* 1 .. 2^29: 2^32 baud / rate                  */
+    uint32_t q;           /* 1 .. 64, 4 q inc <= 2^32                     */
+    uint32_t step;        /* 0 .. inc                                     */
+} pddc_psk_modem;
+typedef struct pddc_psk_rx {
+    int modem;            /* 0 .. nmodems - 1                             */
+    uint32_t flags;       /* PDDC_PSK_ON | _RESTART                       */
+} pddc_psk_rx;
+typedef struct pddc_psk_char {
+    uint64_t start;       /* sample index m of the first bit's on-time sample */
+    uint16_t code;        /* the bits in front of the two zeros, the first highest */
+    uint8_t nbits;        /* their number, saturating at 253              */
+    uint8_t flags;        /* PDDC_PSK_LONG                                */
+    float quality;        /* the least |d| of the character's strobes     */
+} pddc_psk_char;
+typedef struct pddc_psk_status {
+    uint32_t chars, symbols;
+    uint32_t acc, reg;
+    float d_last, x_last;
+} pddc_psk_status;
+typedef struct pddc_psk pddc_psk;
+int pddc_psk_create(pddc_psk **out, int device, int nrx, int window, int nmodems,
+                    const float *taps /* [nmodems][window]; copied */, const pddc_psk_modem *modems /* [nmodems] */,
+                    const pddc_psk_rx *rx /* [nrx] */);
+int pddc_psk_destroy(pddc_psk *f);
+int pddc_psk_reset(pddc_psk *f);                      /* m and everything carried; synchronises the device */
+int pddc_psk_set_rx(pddc_psk *f, int rx, int modem, uint32_t flags);
+int pddc_psk_max_syms(const pddc_psk *f, size_t n, size_t *count);
+int pddc_psk_max_chars(const pddc_psk *f, size_t n, size_t *count);
+int pddc_psk_process(pddc_psk *f, const void *d_z, size_t n, size_t z_stride, void *d_chars, size_t char_stride,
+                     void *d_counts, void *d_sym, size_t sym_stride, void *d_nsym, void *stream);
+/* status[nrx] after the batches submitted so far (it waits for them) */
+int pddc_psk_read(pddc_psk *f, pddc_psk_status *host /* [nrx] */, void *stream);
+/* samples per tile of the kernel's walk, from the batch's first (for tests that place batch cuts on its seams) */
+int pddc_psk_tile_outputs(void);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------- */
 /* Times `iters` back-to-back launches of the pipeline's stage-0 kernel alone
  * with HIP events on `stream`; returns average milliseconds per launch.

@@ -141,6 +141,16 @@ class MorseRx(C.Structure):
     _fields_ = [("keyer", C.c_int), ("flags", C.c_uint32)]
 
 
+class PskRx(C.Structure):
+    """pddc_psk_rx"""
+    _fields_ = [("modem", C.c_int), ("flags", C.c_uint32)]
+
+
+class PskModem(C.Structure):
+    """pddc_psk_modem"""
+    _fields_ = [("inc", C.c_uint32), ("q", C.c_uint32), ("step", C.c_uint32)]
+
+
 class MorseKeyer(C.Structure):
     """pddc_morse_keyer"""
     _fields_ = [("two0", C.c_uint32), ("two_min", C.c_uint32), ("two_max", C.c_uint32), ("shift", C.c_uint32)]
@@ -473,6 +483,19 @@ def ddc_lib() -> C.CDLL:
     L.pddc_morse_tile_outputs.argtypes = []
     for name in ("pddc_morse_create", "pddc_morse_destroy", "pddc_morse_reset", "pddc_morse_set_rx", "pddc_morse_max_chars",
                  "pddc_morse_process", "pddc_morse_read", "pddc_morse_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_psk_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(PskModem),
+                                  C.POINTER(PskRx)]
+    L.pddc_psk_destroy.argtypes = [vp]
+    L.pddc_psk_reset.argtypes = [vp]
+    L.pddc_psk_set_rx.argtypes = [vp, C.c_int, C.c_int, C.c_uint32]
+    L.pddc_psk_max_syms.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_psk_max_chars.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_psk_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]
+    L.pddc_psk_read.argtypes = [vp, vp, vp]
+    L.pddc_psk_tile_outputs.argtypes = []
+    for name in ("pddc_psk_create", "pddc_psk_destroy", "pddc_psk_reset", "pddc_psk_set_rx", "pddc_psk_max_syms", "pddc_psk_max_chars",
+                 "pddc_psk_process", "pddc_psk_read", "pddc_psk_tile_outputs"):
         getattr(L, name).restype = C.c_int
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
@@ -988,7 +1011,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk and Morse share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse and Psk share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -2504,6 +2527,184 @@ class Morse(_StreamObject):
         import numpy as np
         st = np.zeros(self.nrx, dtype=morse_status_dtype())
         check(ddc_lib().pddc_morse_read(self._h, st.ctypes.data, self._stream(stream)))
+        return st
+
+
+PDDC_PSK_ON, PDDC_PSK_RESTART = 0x1, 0x4
+PDDC_PSK_LONG = 0x1
+
+
+def psk_tile_outputs() -> int:
+    """pddc_psk_tile_outputs: samples per tile of the kernel's walk (tiles begin at the batch's first sample); host
+    arithmetic, no device"""
+    return int(ddc_lib().pddc_psk_tile_outputs())
+
+
+def psk_char_dtype():
+    """pddc_psk_char as a numpy structured dtype (16 bytes)"""
+    import numpy as np
+    return np.dtype([("start", np.uint64), ("code", np.uint16), ("nbits", np.uint8), ("flags", np.uint8), ("quality", np.float32)])
+
+
+def psk_status_dtype():
+    """pddc_psk_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("chars", np.uint32), ("symbols", np.uint32), ("acc", np.uint32), ("reg", np.uint32),
+                     ("d_last", np.float32), ("x_last", np.float32)])
+
+
+def psk_modem(W: int, samples_per_symbol: float, step: int = None, q: int = None):
+    """A modem for Psk's bank at samples_per_symbol = rate / baud (8 or more; 31.25 baud is PSK31).  The taps are the
+    raised-cosine pulse a PSK31 sender keys with, over L = min(W, round(2 sps)) samples: w[t] = 1 + cos(pi (t - (L - 1) /
+    2) / sps) inside, zero beyond, of unit sum, computed in double and rounded once: the matched filter, whose output
+    peaks at the symbol's middle (L - 1) / 2 samples later.  inc = round(2^32 / sps), at most 2^29; q = round(sps / 4)
+    in 1 .. 64 with 4 q inc <= 2^32; step defaults to inc / 4, a quarter of a sample per reversal.
+    -> (h float32[W], inc, q, step)"""
+    import numpy as np
+    W, sps = int(W), float(samples_per_symbol)
+    if W <= 0 or not sps >= 8.0 or not sps <= float(1 << 32):
+        raise PddcError(-1, "psk_modem: W must be positive and a symbol 8 .. 2^32 samples")
+    L = min(W, max(1, int(round(2.0 * sps))))
+    t = np.arange(W, dtype=np.float64)
+    w = np.where(t < L, 1.0 + np.cos(np.pi * (t - (L - 1) / 2.0) / sps), 0.0)
+    inc = min(max(int(round(float(1 << 32) / sps)), 1), 1 << 29)
+    if q is None:
+        q = int(round(sps / 4.0))
+    q = min(max(int(q), 1), 64)
+    while q > 1 and 4 * q * inc > (1 << 32):
+        q -= 1
+    step = inc // 4 if step is None else int(step)
+    return (w / w.sum()).astype(np.float32), inc, q, step
+
+
+# G3PLX Varicode, as published with PSK31 (Peter Martinez, RadCom 1998 / ARRL): ASCII 0 .. 127
+_PSK_VARICODE = (
+    "1010101011 1011011011 1011101101 1101110111 1011101011 1101011111 1011101111 1011111101 1011111111 11101111 11101 "
+    "1101101111 1011011101 11111 1101110101 1110101011 1011110111 1011110101 1110101101 1110101111 1101011011 1101101011 "
+    "1101101101 1101010111 1101111011 1101111101 1110110111 1101010101 1101011101 1110111011 1011111011 1101111111 1 "
+    "111111111 101011111 111110101 111011011 1011010101 1010111011 101111111 11111011 11110111 101101111 111011111 1110101 "
+    "110101 1010111 110101111 10110111 10111101 11101101 11111111 101110111 101011011 101101011 110101101 110101011 "
+    "110110111 11110101 110111101 111101101 1010101 111010111 1010101111 1010111101 1111101 11101011 10101101 10110101 "
+    "1110111 11011011 11111101 101010101 1111111 111111101 101111101 11010111 10111011 11011101 10101011 11010101 "
+    "111011101 10101111 1101111 1101101 101010111 110110101 101011101 101110101 101111011 1010101101 111110111 111101111 "
+    "111111011 1010111111 101101101 1011011111 1011 1011111 101111 101101 11 111101 1011011 101011 1101 111101011 10111111 "
+    "11011 111011 1111 111 111111 110111111 10101 10111 101 110111 1111011 1101011 11011111 1011101 111010101 1010110111 "
+    "110111011 1010110101 1011010111 1110110101").split()
+_PSK_CODES = {int(b, 2): chr(i) for i, b in enumerate(_PSK_VARICODE)}
+
+
+def psk_varicode(codes) -> str:
+    """The text of Varicode codes (the `code` field of pddc_psk_char records, or any sequence of integers), host only:
+    the G3PLX table of ASCII 0 .. 127 (space is 1, e is 11, t is 101, o is 111), U+FFFD for a code it does not hold."""
+    return "".join(_PSK_CODES.get(int(c), "\ufffd") for c in codes)
+
+
+def psk_varicode_bits(text: str):
+    """The bits that send `text` (ASCII) in Varicode, each character followed by 00: a list of 0 / 1, a 0 being a
+    phase reversal on the air.  Host only; what tests and tools key their signals with."""
+    out = []
+    for ch in text:
+        out += [int(b) for b in _PSK_VARICODE[ord(ch)]] + [0, 0]
+    return out
+
+
+class Psk(_StreamObject):
+    """pddc_psk: differential BPSK (PSK31 and its faster siblings) decoding of every receiver's complex series, such as
+    Tuner, Blanker, RxFilter or Carrier write, on the device (include/perseus_ddc.h): a real matched filter of W taps, a
+    symbol clock that the envelope corrects at every phase reversal, the differential decision and the Varicode framing
+    per receiver; the output is characters, not samples.
+    bank: up to 16 modems (h, inc, q, step), as psk_modem gives them, every h of W taps; sel: one (modem, flags) per
+    receiver, flags PDDC_PSK_ON.  Feed it every batch in order on one stream; every output bit is the same however the
+    series is cut."""
+    _kind = "psk"
+
+    def __init__(self, bank, sel, W: int, device: int = 0):
+        import numpy as np
+        bank = [tuple(b) for b in bank]
+        sel = [tuple(r) for r in sel]
+        self.W, self.nrx, self.nmodems, self.device = int(W), len(sel), len(bank), device
+        taps = np.zeros((max(self.nmodems, 1), max(self.W, 1)), np.float32)
+        modems = (PskModem * max(self.nmodems, 1))()
+        u32 = lambda v: max(0, min(int(v), (1 << 32) - 1))
+        for b, (h, inc, q, step) in enumerate(bank):
+            h = np.asarray(h, dtype=np.float32).reshape(-1)
+            if h.size != self.W:
+                raise PddcError(-1, f"psk: modem {b}: {h.size} taps for a window of {self.W}")
+            taps[b] = h
+            modems[b] = PskModem(u32(inc), u32(q), u32(step))
+        arr = (PskRx * max(self.nrx, 1))()
+        for j, (modem, flags) in enumerate(sel):
+            arr[j] = PskRx(_clip(modem), int(flags) & 0xFFFFFFFF)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_psk_create(C.byref(h), device, self.nrx, _clip(W), self.nmodems,
+                                        taps.ctypes.data_as(C.POINTER(C.c_float)), modems, arr))
+        self._h = h
+
+    def max_syms(self, n: int) -> int:
+        """pddc_psk_max_syms: the most strobes one receiver can have in a batch of n samples (host arithmetic)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_psk_max_syms(self._h, int(n), C.byref(c)))
+        return int(c.value)
+
+    def max_chars(self, n: int) -> int:
+        """pddc_psk_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_psk_max_chars(self._h, int(n), C.byref(c)))
+        return int(c.value)
+
+    def process(self, z, chars=None, counts=None, sym=None, nsym=None, want_sym: bool = False, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (chars, counts) or,
+        with want_sym or sym given, (chars, counts, sym, nsym): chars int32 [nrx, capacity, 4], four words per
+        pddc_psk_char (`.cpu().numpy().view(psk_char_dtype())[..., 0]` gives the records), of which the first counts[j]
+        (int32 [nrx]) of row j are written; sym float32 [nrx, capacity, 2], (d, x) per strobe, of which the first nsym[j]
+        (int32 [nrx]) are written.  The outputs, if given, are tensors of these kinds (chars and sym with any capacity
+        that suffices); no output may overlap z."""
+        import torch
+        if not self._rows(z, torch.complex64):
+            raise PddcError(-1, "psk: z must be a complex64 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        dev = torch.device("cuda", self.device)
+        if chars is None:
+            chars = torch.empty((self.nrx, max(self.max_chars(n), 1), 4), dtype=torch.int32, device=dev)
+        elif not (chars.dtype == torch.int32 and chars.dim() == 3 and chars.shape[0] == self.nrx and chars.shape[2] == 4
+                  and chars[0].is_contiguous()):
+            raise PddcError(-1, "psk: chars must be an int32 tensor [nrx, capacity, 4] with contiguous rows")
+
+        def vec(t, what):
+            if t is None:
+                return torch.empty((self.nrx,), dtype=torch.int32, device=dev)
+            if not (t.dtype == torch.int32 and t.dim() == 1 and t.shape[0] == self.nrx and t.is_contiguous()):
+                raise PddcError(-1, f"psk: {what} must be a contiguous int32 tensor [nrx]")
+            return t
+        counts = vec(counts, "counts")
+        scap = 0
+        if sym is not None or want_sym:
+            if sym is None:
+                sym = torch.empty((self.nrx, max(self.max_syms(n), 1), 2), dtype=torch.float32, device=dev)
+            elif not (sym.dtype == torch.float32 and sym.dim() == 3 and sym.shape[0] == self.nrx and sym.shape[2] == 2
+                      and sym[0].is_contiguous()):
+                raise PddcError(-1, "psk: sym must be a float32 tensor [nrx, capacity, 2] with contiguous rows")
+            nsym = vec(nsym, "nsym")
+            scap = int(sym.stride(0)) // 2 if sym.shape[1] >= self.max_syms(n) else int(sym.shape[1])
+        # the ABI takes the row strides in records; a capacity below the bound must reach it as one (PDDC_ECAPACITY)
+        ccap = int(chars.stride(0)) // 4 if chars.shape[1] >= self.max_chars(n) else int(chars.shape[1])
+        check(ddc_lib().pddc_psk_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                         chars.data_ptr() if chars.numel() else None, ccap, counts.data_ptr(),
+                                         sym.data_ptr() if sym is not None and sym.numel() else None, scap,
+                                         nsym.data_ptr() if sym is not None else None, self._stream(stream)))
+        return (chars, counts) if sym is None else (chars, counts, sym, nsym)
+
+    def set_rx(self, rx: int, modem: int, flags: int):
+        """receiver rx from the next batch's first sample on: PDDC_PSK_RESTART, OFF -> ON or another modem starts it
+        afresh (the counters stay)"""
+        check(ddc_lib().pddc_psk_set_rx(self._h, int(rx), _clip(modem), int(flags) & 0xFFFFFFFF))
+
+    def read(self, stream=None):
+        """-> numpy structured array [nrx] (chars, symbols, acc, reg, d_last, x_last) after the batches submitted so far
+        (it waits for them)"""
+        import numpy as np
+        st = np.zeros(self.nrx, dtype=psk_status_dtype())
+        check(ddc_lib().pddc_psk_read(self._h, st.ctypes.data, self._stream(stream)))
         return st
 
 
