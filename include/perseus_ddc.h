@@ -1003,7 +1003,9 @@ int pddc_adapt_tile_outputs(void);
  * Under HOLD S and N are not touched and A alone is lost, for one frame.  Recovery: the caller feeds
  * nfft good samples and then calls set_rx with PDDC_DENOISE_RESTART; the next completed frame q holds
  * good samples only and is a first frame, and from out index q hop + nfft on (once the overlap has
- * drained) the row is that of a receiver restarted there on the good series.  Or reset.
+ * drained) the row is that of a receiver restarted there on the good series.  Or reset.  What
+ * counts is that frame alone: a RESTART whose next completed frame still holds the bad sample makes
+ * a first frame of it, S = N = P is NaN, and N is NaN again.
  * process(): x is [nrx][x_stride] and out [nrx][out_stride] float32, n values used per row.  Every
  * argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned (4 bytes)
  * pointer with work to do, PDDC_ECAPACITY when a stride is below n; in place is not offered: any
@@ -1354,6 +1356,8 @@ int pddc_audio_process(pddc_audio *a, const void *d_x, size_t n, size_t x_stride
  * +-Inf in y, in block k: m is Inf for the blocks k - 1 and k, so t = 0 and E = 0 there; the sample
  * itself becomes Inf * 0 = NaN, which fmaxf drops: it leaves as -ceil, as does a NaN in y (which P
  * ignores: it changes no gain).  From block k + 1 on E recovers by rel per block.  Nothing sticks.
+ * In block 0 the ramp comes down from E[-1] = 1, so g > 0 at every sample but the block's last: an
+ * infinity there is Inf * g = Inf and leaves clamped, as +ceil or -ceil by its sign.
  * Outputs, either or both: f32[q * f32_stride + k] planar; i16[k * nbus + q] interleaved frames,
  * p = (int16) clamp(rintf(out scale), -32768, 32767), NaN -> 0, audio's rule.
  * Status per bus (pddc_mixer_read): peak = fmaxf of |y| over the samples processed since create or

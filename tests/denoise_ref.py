@@ -115,6 +115,12 @@ class Stream:
         self.K = K = len(rx)
         self.rx = _Rx(rx, dtype)
         self.fwd, self.inv = _transforms(dtype)
+        self.reset()
+
+    def reset(self):
+        """everything carried, the first-frame mark included; the receivers' settings stay"""
+        K, nfft, hop, dtype = self.K, self.nfft, self.hop, self.dtype
+        self.rx.first[:] = True
         B = nfft // 2 + 1
         self.st = [np.zeros((K, B), dtype) for _ in range(3)]
         self.inputs = np.zeros((K, nfft - hop), dtype)     # since the start of the oldest incomplete frame (x[m] = 0, m < 0)

@@ -19,11 +19,20 @@ POISON = {"nan": QNAN, "+inf": F32(np.inf), "-inf": F32(-np.inf)}
 POISON_EXACT = dict(POISON, huge=F32(1e25), tiny=F32(2.0 ** -80))
 
 
-def words(x):
-    """the uint32 words of a float32 / complex64 array (complex: re, im interleaved along the last axis); integer arrays
-    as they are"""
+FLOATS = {np.dtype(np.float32): (F32, np.uint32), np.dtype(np.complex64): (F32, np.uint32), np.dtype(np.float64): (np.float64, np.uint64)}
+
+
+def parts(x):
+    """a float32 / complex64 / float64 array as its real numbers (complex: re, im interleaved along the last axis)"""
     x = np.ascontiguousarray(x)
-    return x.view(np.uint32) if x.dtype in (np.float32, np.complex64) else x
+    return x.view(FLOATS[x.dtype][0])
+
+
+def words(x):
+    """the uint32 words of a float32 / complex64 array (complex: re, im interleaved along the last axis), the uint64
+    words of a float64 one (the equaliser's states); integer arrays as they are"""
+    x = np.ascontiguousarray(x)
+    return x.view(FLOATS[x.dtype][1]) if x.dtype in FLOATS else x
 
 
 def never_read(shape, dtype):
@@ -89,14 +98,14 @@ def same_or_both_nan(got, want, what=""):
     are no NaN, or the comparison would say nothing."""
     got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
     assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    if got.dtype not in (np.float32, np.complex64):
+    if got.dtype not in FLOATS:
         assert np.array_equal(got, want), (what, np.argwhere(got != want)[:4].tolist())
         return
-    g, w = got.view(F32), want.view(F32)
+    g, w = parts(got), parts(want)
     gn, wn = np.isnan(g), np.isnan(w)
     assert not wn.all(), (what, "nothing but NaN to compare with")
     assert np.array_equal(gn, wn), (what, "NaN positions", np.argwhere(gn != wn)[:4].tolist())
-    gw, ww = g.view(np.uint32), w.view(np.uint32)
+    gw, ww = words(g), words(w)
     bad = (gw != ww) & ~wn
     assert not bad.any(), (what, "bits", np.argwhere(bad)[:4].tolist())
 
@@ -108,7 +117,32 @@ def clean_rows_identical(got, clean, rows, what=""):
     assert got.shape == clean.shape and got.dtype == clean.dtype, (what, got.shape, clean.shape)
     rows = np.asarray(rows)
     c = clean[rows]
-    if c.dtype in (np.float32, np.complex64):
-        assert np.isfinite(c.view(F32)).all(), (what, "the clean run is not finite on these rows")
+    if c.dtype in FLOATS:
+        assert np.isfinite(parts(c)).all(), (what, "the clean run is not finite on these rows")
     gw, cw = words(got[rows]), words(c)
     assert np.array_equal(gw, cw), (what, np.argwhere(gw != cw)[:4].tolist())
+
+
+# ---- ragged outputs: records of which the first counts[j] of row j are written ---------------------------------------
+
+def gather(buf, counts):
+    """a record buffer [K, capacity, ...] and its counts [K] -> one array per row, the records that were written"""
+    counts = np.asarray(counts)
+    assert counts.shape == (buf.shape[0],) and (counts >= 0).all() and (counts <= buf.shape[1]).all(), (counts.tolist(), buf.shape)
+    return [buf[j, :counts[j]].copy() for j in range(buf.shape[0])]
+
+
+def dense(rows, width):
+    """per-row record lists (each [count_j, ...], one dtype and record shape) as one array [K, width, ...], zeros behind
+    a row's records: rows that hold the same records give the same array, so the comparisons above apply.  With the
+    rows' counts beside it nothing is lost: a record of zeros is told from no record"""
+    out = np.zeros((len(rows), width) + tuple(rows[0].shape[1:]), rows[0].dtype)
+    for j, r in enumerate(rows):
+        assert r.shape[0] <= width and r.shape[1:] == out.shape[2:] and r.dtype == out.dtype, (j, r.shape, out.shape)
+        out[j, :r.shape[0]] = r
+    return out
+
+
+def record_words(chars):
+    """per-row arrays of 16-byte records (a reference's CHAR arrays) as int32 [count_j, 4], the device's layout"""
+    return [np.ascontiguousarray(c).view(np.int32).reshape(-1, 4) for c in chars]
