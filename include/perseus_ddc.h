@@ -237,7 +237,8 @@ int pddc_fir_i8x_taps2(const float *taps2, int ntaps2, int mix, uint32_t freg, f
 int pddc_pipeline_set_option(pddc_pipeline *p, const char *name, int value);
 /* Process-wide development knobs of the launchers (tile schedule of k_fir8, block shapes, gang plumbing): "fir8_dyn_pct",
  * "fir8_chunk", "fir8_walk" (1: chunks handed round the blocks, 0: static runs + dynamic tail, -1: the launcher's default), "gen_shape_nt", "gen_shape_p", "no_firp", "firp_packed_p", "unpack_blocks", "debug", "push_three_streams",
- * "gang_copy_out", "gang_gen_inline", "gang_solo".  Their PDDC_<NAME> environment variables are read once, at first use;
+ * "gang_copy_out", "gang_gen_inline", "gang_solo", "chan_run", "wblank_run" (samples one workgroup of the wideband
+ * blanker walks), "wblank_chunk" (samples one round of its launches takes); 0: automatic.  Their PDDC_<NAME> environment variables are read once, at first use;
  * no library call on the data path looks at the environment.                                                         */
 int pddc_set_tunable(const char *name, int value);
 int pddc_get_tunable(const char *name, int *value);
@@ -1218,6 +1219,74 @@ int pddc_blanker_read(pddc_blanker *b, pddc_blanker_status *host /* [nrx] */, vo
 int pddc_blanker_delay(const pddc_blanker *b);
 /* samples per tile of the kernel's walk (for tests that place batch cuts on its seams) */
 int pddc_blanker_tile_outputs(void);
+
+/* ---- wblank: impulse blanking on the packed ADC stream ------------------------
+ * A stage in front of everything that reads the packed 24-bit stream (pipeline, bank, panorama,
+ * channelizer): packed samples in, packed samples out, so none of them changes.  At the full ADC
+ * bandwidth an impulse is 1 - 3 samples long and is cut with a few dozen samples lost; behind the
+ * channelizer and the tuner it has their filters' length and is in every receiver.
+ * Everything is integer arithmetic: every output bit and every counter depends on the stream, the
+ * create parameters and the set() history alone, not on the cut into batches, grid, tile or run.
+ * Samples: I[m], Q[m] are the 24-bit codes in [-2^23, 2^23) (pddc_unpack24_i32 >> 8, arithmetic); m
+ * counts input samples since create / reset (uint64 N is carried).  p[m] = I^2 + Q^2, uint64, at
+ * most 2^47.
+ * Fixed at create: B, samples per metering block, a power of two 64 .. 4096, b = log2 B; H, blocks
+ * of history, 1 .. 16; W, the guard half-width, 0 .. 128; r, the ramp exponent, 0 .. 7, the ramp
+ * length is R = 2^r - 1; D = W + R, at most 255.
+ * Changeable between batches with set(thr16, flags): thr16, the threshold as a power ratio in
+ * sixteenths, 16 .. 65536; flags, a subset of PDDC_WB_ON.  A change applies from the next input
+ * sample on, decisions already taken stay; a bad value is PDDC_EINVAL and changes nothing.
+ * Metering: block k covers samples [k B, (k + 1) B), S_k is the sum of p over it (at most 2^59);
+ * the block grid belongs to the stream.  For k >= 1: mean_k = (the least S_j, j = max(0, k - H) ..
+ * k - 1) >> b; mean_0 = 0.  The minimum keeps the impulses themselves, and a signal keying on, out
+ * of the reference.
+ * Trigger, m in block k: t[m] = ON && mean_k > 0 && p[m] > ((mean_k thr16) >> 4); the product is at
+ * most 2^63.
+ * Gate, as the per-receiver blanker's: dist[m] is the least |m - u| over u with t[u] set and
+ * |m - u| <= D; num = 0 when dist <= W, num = dist - W when W < dist <= D, "open" when no trigger is
+ * that near.
+ * Output n of the stream is made from input c = n - D, one per input, at the same index of the
+ * batch: six zero bytes for c < 0; open: the six input bytes of sample c unchanged; otherwise I and
+ * Q each become sign(v) ((|v| num) >> r), packed again (toward zero, no DC added, |v| num < 2^31).
+ * The last D inputs of a stream come out when D more are fed: there is no flush call.
+ * Carried: N, the open block's partial sum, the last H block sums, the last 2 D inputs (rounded up
+ * to 8) with their trigger bits -- the bits are kept, not taken again, since the threshold may have
+ * changed --, the counters.
+ * read(): after the batches submitted so far (it waits for them): mean, the reference of the block
+ * the next input sample falls into; triggers, the t[m] set; blanked, the outputs made from an input
+ * (c >= 0) whose gate was not open; samples = N.
+ * process(): d_packed holds nsamples packed samples, d_out takes exactly nsamples.  Checked before
+ * anything is queued: nsamples a multiple of 8, both pointers 16-byte aligned and not NULL with
+ * work to do, ANY overlap of out and in is PDDC_EINVAL -- there is no in-place form, a workgroup
+ * reads D samples beyond what it writes.  nsamples = 0 is valid and does nothing; batches shorter
+ * than D or B samples are valid.  The object moves only after the last launch was accepted: a batch
+ * of more than 2^26 samples goes in rounds of 2^26, and no round writes what the object holds.
+ * Stream-ordered, no allocation and no synchronisation; one stream per object, one thread at a time.
+ * create: argument errors before any device access; good arguments, no device: PDDC_ENODEV.
+ * The "wblank_run" knob of pddc_set_tunable sets the samples one workgroup walks (0: automatic). */
+#define PDDC_WB_ON 0x1u
+typedef struct pddc_wblank_params {
+    int block;            /* B: samples per metering block                */
+    int history;          /* H: block sums the reference is the least of  */
+    int guard;            /* W: samples zeroed on either side of a trigger */
+    int ramp_log2;        /* r: the ramp is 2^r - 1 samples on either side */
+} pddc_wblank_params;
+typedef struct pddc_wblank_status {
+    uint64_t mean, triggers, blanked, samples;
+} pddc_wblank_status;
+typedef struct pddc_wblank pddc_wblank;
+int pddc_wblank_create(pddc_wblank **out, int device, const pddc_wblank_params *params, uint32_t thr16, uint32_t flags);
+int pddc_wblank_destroy(pddc_wblank *w);
+int pddc_wblank_reset(pddc_wblank *w);                /* N and everything carried; synchronises the device */
+int pddc_wblank_set(pddc_wblank *w, uint32_t thr16, uint32_t flags);
+int pddc_wblank_process(pddc_wblank *w, const void *d_packed, size_t nsamples, void *d_out, void *stream);
+int pddc_wblank_read(pddc_wblank *w, pddc_wblank_status *host, void *stream);
+/* D = W + 2^r - 1: output n is input n - D */
+int pddc_wblank_delay(const pddc_wblank *w);
+/* samples per tile of the gate kernel's walk, and the samples one workgroup walks under the current "wblank_run" (one
+ * tile when it is automatic): for tests that place batch cuts on the kernel's seams */
+int pddc_wblank_tile_samples(void);
+int pddc_wblank_run_samples(void);
 
 /* ---- scope: each receiver's own spectrum and waterfall lines ------------------
  * Beside the chain, not in it: it reads any of the per-receiver complex float32 series -- the

@@ -171,6 +171,11 @@ class BlankerRx(C.Structure):
     _fields_ = [("thr", C.c_float), ("flags", C.c_uint32)]
 
 
+class WBlankParams(C.Structure):
+    """pddc_wblank_params (include/perseus_ddc.h)"""
+    _fields_ = [("block", C.c_int), ("history", C.c_int), ("guard", C.c_int), ("ramp_log2", C.c_int)]
+
+
 _ddc = None
 
 
@@ -421,6 +426,18 @@ def ddc_lib() -> C.CDLL:
     L.pddc_blanker_tile_outputs.argtypes = []
     for name in ("pddc_blanker_create", "pddc_blanker_destroy", "pddc_blanker_reset", "pddc_blanker_set_rx",
                  "pddc_blanker_process", "pddc_blanker_read", "pddc_blanker_delay", "pddc_blanker_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_wblank_create.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(WBlankParams), C.c_uint32, C.c_uint32]
+    L.pddc_wblank_destroy.argtypes = [vp]
+    L.pddc_wblank_reset.argtypes = [vp]
+    L.pddc_wblank_set.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.pddc_wblank_process.argtypes = [vp, vp, sz, vp, vp]
+    L.pddc_wblank_read.argtypes = [vp, vp, vp]
+    L.pddc_wblank_delay.argtypes = [vp]
+    L.pddc_wblank_tile_samples.argtypes = []
+    L.pddc_wblank_run_samples.argtypes = []
+    for name in ("pddc_wblank_create", "pddc_wblank_destroy", "pddc_wblank_reset", "pddc_wblank_set", "pddc_wblank_process",
+                 "pddc_wblank_read", "pddc_wblank_delay", "pddc_wblank_tile_samples", "pddc_wblank_run_samples"):
         getattr(L, name).restype = C.c_int
     L.pddc_scope_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_float), C.c_uint32]
@@ -1011,7 +1028,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse and Psk share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What WBlank, Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse and Psk share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -1937,6 +1954,83 @@ class Blanker(_StreamObject):
         st = np.zeros(self.nrx, dtype=blanker_status_dtype())
         check(ddc_lib().pddc_blanker_read(self._h, st.ctypes.data, self._stream(stream)))
         return st
+
+
+PDDC_WB_ON = 0x1
+
+
+def wblank_tile_samples() -> int:
+    """pddc_wblank_tile_samples: samples per tile of the gate kernel's walk; host arithmetic, no device"""
+    return int(ddc_lib().pddc_wblank_tile_samples())
+
+
+def wblank_run_samples() -> int:
+    """pddc_wblank_run_samples: samples one workgroup walks under the current "wblank_run" tunable (one tile when it is
+    automatic); host arithmetic, no device"""
+    return int(ddc_lib().pddc_wblank_run_samples())
+
+
+def wblank_status_dtype():
+    """pddc_wblank_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("mean", np.uint64), ("triggers", np.uint64), ("blanked", np.uint64), ("samples", np.uint64)])
+
+
+def _wblank_thr16(thr) -> int:
+    """a power ratio as the C ABI takes it: sixteenths, rounded; out of range stays out of range"""
+    t = float(thr) * 16.0
+    return int(round(t)) if 0.0 <= t < 4.0e9 else 0xFFFFFFFF
+
+
+class WBlank(_StreamObject):
+    """pddc_wblank: the wideband blanker -- impulse blanking on the packed 24-bit ADC stream itself, in front of Pipeline,
+    Bank, Spectrum and Channelizer, which take its output as they take the stream (include/perseus_ddc.h).  Integers
+    only: the power sums of every `block` samples (a power of two 64 .. 4096) are metered, the reference is the least of
+    the last `history` (1 .. 16) block means, a sample whose power exceeds the reference times `thr` (1 .. 4096, in
+    sixteenths) is a trigger; the output is the input delayed by `delay` = guard + 2^ramp_log2 - 1 samples, zero within
+    `guard` samples of a trigger and scaled by 1 / 2^ramp_log2 .. (2^ramp_log2 - 1) / 2^ramp_log2 on the ramps beside it;
+    every other sample keeps its six bytes.  Feed it every batch in order on one stream; all bytes and counters are the
+    same however the stream is cut (on multiples of 8 samples).  The last `delay` inputs come out when `delay` more
+    samples are fed."""
+    _kind = "wblank"
+
+    def __init__(self, block: int, history: int, guard: int, ramp_log2: int, thr: float = 16.0, on: bool = True,
+                 device: int = 0):
+        self.device = device
+        self.block, self.history, self.guard, self.ramp_log2 = int(block), int(history), int(guard), int(ramp_log2)
+        self.params = WBlankParams(_clip(block), _clip(history), _clip(guard), _clip(ramp_log2))
+        h = C.c_void_p()
+        check(ddc_lib().pddc_wblank_create(C.byref(h), device, C.byref(self.params), _wblank_thr16(thr),
+                                           PDDC_WB_ON if on else 0))
+        self._h = h
+        self.delay = int(ddc_lib().pddc_wblank_delay(h))
+
+    def process(self, packed, nsamples=None, out=None, stream=None):
+        """One batch: a torch uint8 CUDA tensor of packed samples (or a device address with nsamples).  -> uint8 tensor
+        of 6 nsamples bytes (the front of `out`, a contiguous uint8 CUDA tensor that does not overlap the input, if
+        given): sample i of it is input i - delay of the stream."""
+        import torch
+        ptr, nsamples = _packed_arg(self._kind, packed, nsamples)
+        nsamples = int(nsamples)
+        if out is None:
+            out = torch.empty(6 * max(nsamples, 0), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < 6 * nsamples:
+            raise PddcError(-1, "wblank: out must be a contiguous uint8 tensor of at least 6 nsamples bytes")
+        check(ddc_lib().pddc_wblank_process(self._h, ptr if nsamples else None, nsamples,
+                                            out.data_ptr() if nsamples else None, self._stream(stream)))
+        return out.view(-1)[:6 * nsamples]
+
+    def set(self, thr: float, on: bool = True):
+        """threshold and ON / OFF from the next input sample on; nothing carried is reset"""
+        check(ddc_lib().pddc_wblank_set(self._h, _wblank_thr16(thr), PDDC_WB_ON if on else 0))
+
+    def read(self, stream=None):
+        """-> numpy structured scalar (mean, triggers, blanked, samples) after the batches submitted so far (it waits for
+        them)"""
+        import numpy as np
+        st = np.zeros(1, dtype=wblank_status_dtype())
+        check(ddc_lib().pddc_wblank_read(self._h, st.ctypes.data, self._stream(stream)))
+        return st[0]
 
 
 PDDC_SCOPE_CENTERED = 0x1

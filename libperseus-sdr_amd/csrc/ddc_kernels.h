@@ -30,6 +30,8 @@ struct Tunables {
     std::atomic<int> debug{ 0 };              /* allocation / placement messages on stderr                             */
     std::atomic<int> push_three_streams{ 0 }, gang_copy_out{ 0 }, gang_gen_inline{ 0 }, gang_solo{ 0 };
     std::atomic<int> chan_run{ 0 };           /* rows per block of a k_channelize launch (0: the launcher's choice)    */
+    std::atomic<int> wblank_run{ 0 };         /* samples one workgroup of k_wblank_gate walks (0: the launcher's choice) */
+    std::atomic<int> wblank_chunk{ 0 };       /* samples one round of the wideband blanker's launches takes (0: 2^26)  */
 };
 Tunables &tunables();
 bool set_tunable(const char *name, int value);       /* false: no such knob */

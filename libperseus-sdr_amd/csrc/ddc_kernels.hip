@@ -103,6 +103,8 @@ Tunables &tunables()
         flag("PDDC_GANG_GEN_INLINE", t.gang_gen_inline);
         flag("PDDC_GANG_SOLO", t.gang_solo);
         env("PDDC_CHAN_RUN", t.chan_run);
+        env("PDDC_WBLANK_RUN", t.wblank_run);
+        env("PDDC_WBLANK_CHUNK", t.wblank_chunk);
     });
     return t;
 }
@@ -118,7 +120,7 @@ static std::atomic<int> *tunable_by_name(const char *name)
                 { "gen_shape_p", &t.gen_shape_p },     { "no_firp", &t.no_firp },             { "firp_packed_p", &t.firp_packed_p },
                 { "unpack_blocks", &t.unpack_blocks }, { "debug", &t.debug },                 { "push_three_streams", &t.push_three_streams },
                 { "gang_copy_out", &t.gang_copy_out }, { "gang_gen_inline", &t.gang_gen_inline }, { "gang_solo", &t.gang_solo },
-                { "chan_run", &t.chan_run } };
+                { "chan_run", &t.chan_run },           { "wblank_run", &t.wblank_run },       { "wblank_chunk", &t.wblank_chunk } };
     if (name)
         for (const auto &e : tab)
             if (!strcmp(e.n, name))
