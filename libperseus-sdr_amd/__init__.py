@@ -2336,6 +2336,43 @@ class Mixer(_StreamObject):
         return st
 
 
+class _Decoder(_StreamObject):
+    """What Fsk, Morse and Psk share: the capacity bound, the chars and counts outputs of process() and the status read."""
+
+    def max_chars(self, n: int) -> int:
+        """pddc_<kind>_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
+        c = C.c_size_t()
+        check(getattr(ddc_lib(), f"pddc_{self._kind}_max_chars")(self._h, int(n), C.byref(c)))
+        return int(c.value)
+
+    def _batch(self, z, chars, counts):
+        """What process() begins with: z tested, chars and counts tested or made.  -> (n, chars, counts, the capacity of
+        chars for the C ABI).  The ABI takes the row stride in characters; a capacity below the bound must reach it as
+        one (PDDC_ECAPACITY)."""
+        import torch
+        if not self._rows(z, torch.complex64):
+            raise PddcError(-1, f"{self._kind}: z must be a complex64 tensor [nrx, n] with contiguous rows")
+        n = int(z.shape[1])
+        bound = self.max_chars(n)
+        if chars is None:
+            chars = torch.empty((self.nrx, max(bound, 1), 4), dtype=torch.int32, device=torch.device("cuda", self.device))
+        elif not (chars.dtype == torch.int32 and chars.dim() == 3 and chars.shape[0] == self.nrx and chars.shape[2] == 4
+                  and chars[0].is_contiguous()):
+            raise PddcError(-1, f"{self._kind}: chars must be an int32 tensor [nrx, capacity, 4] with contiguous rows")
+        if counts is None:
+            counts = torch.empty((self.nrx,), dtype=torch.int32, device=torch.device("cuda", self.device))
+        elif not (counts.dtype == torch.int32 and counts.dim() == 1 and counts.shape[0] == self.nrx and counts.is_contiguous()):
+            raise PddcError(-1, f"{self._kind}: counts must be a contiguous int32 tensor [nrx]")
+        return n, chars, counts, int(chars.stride(0)) // 4 if chars.shape[1] >= bound else int(chars.shape[1])
+
+    def _read(self, dtype, stream):
+        """read(): -> numpy structured array [nrx] of `dtype`, the pddc_<kind>_status records"""
+        import numpy as np
+        st = np.zeros(self.nrx, dtype=dtype)
+        check(getattr(ddc_lib(), f"pddc_{self._kind}_read")(self._h, st.ctypes.data, self._stream(stream)))
+        return st
+
+
 PDDC_FSK_ON, PDDC_FSK_REVERSE, PDDC_FSK_RESTART = 0x1, 0x2, 0x4
 PDDC_FSK_FRAMING = 0x1
 PDDC_FSK_IDLE, PDDC_FSK_START, PDDC_FSK_DATA, PDDC_FSK_STOP = 0, 1, 2, 3
@@ -2397,7 +2434,7 @@ def fsk_ita2(codes, flags=None) -> str:
     return "".join(out)
 
 
-class Fsk(_StreamObject):
+class Fsk(_Decoder):
     """pddc_fsk: start-stop FSK (RTTY) decoding of every receiver's complex series, such as Tuner, Blanker, RxFilter or
     Carrier write, on the device (include/perseus_ddc.h): two matched filters of W complex taps and a start-stop
     receiver per receiver; the output is characters, not samples.  bank: up to 16 modems (hm, hs, inc, nbits), as
@@ -2429,37 +2466,17 @@ class Fsk(_StreamObject):
                                         nbits.ctypes.data_as(C.POINTER(C.c_int)), arr))
         self._h = h
 
-    def max_chars(self, n: int) -> int:
-        """pddc_fsk_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
-        c = C.c_size_t()
-        check(ddc_lib().pddc_fsk_max_chars(self._h, int(n), C.byref(c)))
-        return int(c.value)
-
     def process(self, z, chars=None, counts=None, d=None, want_d: bool = False, stream=None):
         """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (chars, counts) or,
         with want_d or d given, (chars, counts, d): chars int32 [nrx, capacity, 4], four words per pddc_fsk_char
         (`.cpu().numpy().view(fsk_char_dtype())[..., 0]` gives the records), of which the first counts[j] (int32 [nrx])
         of row j are written; d float32 [nrx, n], the soft discriminator.  chars, counts and d, if given, are
         tensors of these kinds (chars and d with any capacity that suffices); no output may overlap z."""
-        import torch
-        if not self._rows(z, torch.complex64):
-            raise PddcError(-1, "fsk: z must be a complex64 tensor [nrx, n] with contiguous rows")
-        n = int(z.shape[1])
-        dev = torch.device("cuda", self.device)
-        if chars is None:
-            chars = torch.empty((self.nrx, self.max_chars(n), 4), dtype=torch.int32, device=dev)
-        elif not (chars.dtype == torch.int32 and chars.dim() == 3 and chars.shape[0] == self.nrx and chars.shape[2] == 4
-                  and chars[0].is_contiguous()):
-            raise PddcError(-1, "fsk: chars must be an int32 tensor [nrx, capacity, 4] with contiguous rows")
-        if counts is None:
-            counts = torch.empty((self.nrx,), dtype=torch.int32, device=dev)
-        elif not (counts.dtype == torch.int32 and counts.dim() == 1 and counts.shape[0] == self.nrx and counts.is_contiguous()):
-            raise PddcError(-1, "fsk: counts must be a contiguous int32 tensor [nrx]")
+        n, chars, counts, ccap = self._batch(z, chars, counts)
         dcap = 0
         if d is not None or want_d:
+            import torch
             d, dcap = self._out(d, n, torch.float32, "d must be a float32")
-        # the ABI takes the row stride in characters; a capacity below the bound must reach it as one (PDDC_ECAPACITY)
-        ccap = int(chars.stride(0)) // 4 if chars.shape[1] >= self.max_chars(n) else int(chars.shape[1])
         check(ddc_lib().pddc_fsk_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
                                          chars.data_ptr() if chars.numel() else None, ccap, counts.data_ptr(),
                                          d.data_ptr() if d is not None and d.numel() else None, dcap, self._stream(stream)))
@@ -2473,10 +2490,7 @@ class Fsk(_StreamObject):
     def read(self, stream=None):
         """-> numpy structured array [nrx] (chars, framing, false_starts, state, d_last) after the batches submitted so
         far (it waits for them)"""
-        import numpy as np
-        st = np.zeros(self.nrx, dtype=fsk_status_dtype())
-        check(ddc_lib().pddc_fsk_read(self._h, st.ctypes.data, self._stream(stream)))
-        return st
+        return self._read(fsk_status_dtype(), stream)
 
 
 PDDC_MORSE_ON, PDDC_MORSE_FIXED, PDDC_MORSE_RESTART = 0x1, 0x2, 0x4
@@ -2541,7 +2555,7 @@ def morse_text(records) -> str:
     return "".join(out)
 
 
-class Morse(_StreamObject):
+class Morse(_Decoder):
     """pddc_morse: CW decoding of every receiver's complex series, such as Tuner, Blanker, RxFilter or Carrier write, on the
     device (include/perseus_ddc.h): a real envelope filter of W taps, a block meter that places two thresholds between
     floor and peak, and the element timing with a speed tracker per receiver; the output is characters, not samples.
@@ -2574,37 +2588,17 @@ class Morse(_StreamObject):
                                           taps.ctypes.data_as(C.POINTER(C.c_float)), keyers, C.byref(par), arr))
         self._h = h
 
-    def max_chars(self, n: int) -> int:
-        """pddc_morse_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
-        c = C.c_size_t()
-        check(ddc_lib().pddc_morse_max_chars(self._h, int(n), C.byref(c)))
-        return int(c.value)
-
     def process(self, z, chars=None, counts=None, p=None, want_p: bool = False, stream=None):
         """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (chars, counts) or,
         with want_p or p given, (chars, counts, p): chars int32 [nrx, capacity, 4], four words per pddc_morse_char
         (`.cpu().numpy().view(morse_char_dtype())[..., 0]` gives the records), of which the first counts[j] (int32 [nrx])
         of row j are written; p float32 [nrx, n], the envelope power.  chars, counts and p, if given, are tensors of
         these kinds (chars and p with any capacity that suffices); no output may overlap z."""
-        import torch
-        if not self._rows(z, torch.complex64):
-            raise PddcError(-1, "morse: z must be a complex64 tensor [nrx, n] with contiguous rows")
-        n = int(z.shape[1])
-        dev = torch.device("cuda", self.device)
-        if chars is None:
-            chars = torch.empty((self.nrx, max(self.max_chars(n), 1), 4), dtype=torch.int32, device=dev)
-        elif not (chars.dtype == torch.int32 and chars.dim() == 3 and chars.shape[0] == self.nrx and chars.shape[2] == 4
-                  and chars[0].is_contiguous()):
-            raise PddcError(-1, "morse: chars must be an int32 tensor [nrx, capacity, 4] with contiguous rows")
-        if counts is None:
-            counts = torch.empty((self.nrx,), dtype=torch.int32, device=dev)
-        elif not (counts.dtype == torch.int32 and counts.dim() == 1 and counts.shape[0] == self.nrx and counts.is_contiguous()):
-            raise PddcError(-1, "morse: counts must be a contiguous int32 tensor [nrx]")
+        n, chars, counts, ccap = self._batch(z, chars, counts)
         pcap = 0
         if p is not None or want_p:
+            import torch
             p, pcap = self._out(p, n, torch.float32, "p must be a float32")
-        # the ABI takes the row stride in characters; a capacity below the bound must reach it as one (PDDC_ECAPACITY)
-        ccap = int(chars.stride(0)) // 4 if chars.shape[1] >= self.max_chars(n) else int(chars.shape[1])
         check(ddc_lib().pddc_morse_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
                                            chars.data_ptr() if chars.numel() else None, ccap, counts.data_ptr(),
                                            p.data_ptr() if p is not None and p.numel() else None, pcap, self._stream(stream)))
@@ -2618,10 +2612,7 @@ class Morse(_StreamObject):
     def read(self, stream=None):
         """-> numpy structured array [nrx] (chars, marks, two, nel, key, pk, fl) after the batches submitted so far (it
         waits for them)"""
-        import numpy as np
-        st = np.zeros(self.nrx, dtype=morse_status_dtype())
-        check(ddc_lib().pddc_morse_read(self._h, st.ctypes.data, self._stream(stream)))
-        return st
+        return self._read(morse_status_dtype(), stream)
 
 
 PDDC_PSK_ON, PDDC_PSK_RESTART = 0x1, 0x4
@@ -2702,7 +2693,7 @@ def psk_varicode_bits(text: str):
     return out
 
 
-class Psk(_StreamObject):
+class Psk(_Decoder):
     """pddc_psk: differential BPSK (PSK31 and its faster siblings) decoding of every receiver's complex series, such as
     Tuner, Blanker, RxFilter or Carrier write, on the device (include/perseus_ddc.h): a real matched filter of W taps, a
     symbol clock that the envelope corrects at every phase reversal, the differential decision and the Varicode framing
@@ -2740,12 +2731,6 @@ class Psk(_StreamObject):
         check(ddc_lib().pddc_psk_max_syms(self._h, int(n), C.byref(c)))
         return int(c.value)
 
-    def max_chars(self, n: int) -> int:
-        """pddc_psk_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
-        c = C.c_size_t()
-        check(ddc_lib().pddc_psk_max_chars(self._h, int(n), C.byref(c)))
-        return int(c.value)
-
     def process(self, z, chars=None, counts=None, sym=None, nsym=None, want_sym: bool = False, stream=None):
         """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (chars, counts) or,
         with want_sym or sym given, (chars, counts, sym, nsym): chars int32 [nrx, capacity, 4], four words per
@@ -2753,35 +2738,22 @@ class Psk(_StreamObject):
         (int32 [nrx]) of row j are written; sym float32 [nrx, capacity, 2], (d, x) per strobe, of which the first nsym[j]
         (int32 [nrx]) are written.  The outputs, if given, are tensors of these kinds (chars and sym with any capacity
         that suffices); no output may overlap z."""
-        import torch
-        if not self._rows(z, torch.complex64):
-            raise PddcError(-1, "psk: z must be a complex64 tensor [nrx, n] with contiguous rows")
-        n = int(z.shape[1])
-        dev = torch.device("cuda", self.device)
-        if chars is None:
-            chars = torch.empty((self.nrx, max(self.max_chars(n), 1), 4), dtype=torch.int32, device=dev)
-        elif not (chars.dtype == torch.int32 and chars.dim() == 3 and chars.shape[0] == self.nrx and chars.shape[2] == 4
-                  and chars[0].is_contiguous()):
-            raise PddcError(-1, "psk: chars must be an int32 tensor [nrx, capacity, 4] with contiguous rows")
-
-        def vec(t, what):
-            if t is None:
-                return torch.empty((self.nrx,), dtype=torch.int32, device=dev)
-            if not (t.dtype == torch.int32 and t.dim() == 1 and t.shape[0] == self.nrx and t.is_contiguous()):
-                raise PddcError(-1, f"psk: {what} must be a contiguous int32 tensor [nrx]")
-            return t
-        counts = vec(counts, "counts")
+        n, chars, counts, ccap = self._batch(z, chars, counts)
         scap = 0
         if sym is not None or want_sym:
+            import torch
+            dev = torch.device("cuda", self.device)
             if sym is None:
                 sym = torch.empty((self.nrx, max(self.max_syms(n), 1), 2), dtype=torch.float32, device=dev)
             elif not (sym.dtype == torch.float32 and sym.dim() == 3 and sym.shape[0] == self.nrx and sym.shape[2] == 2
                       and sym[0].is_contiguous()):
                 raise PddcError(-1, "psk: sym must be a float32 tensor [nrx, capacity, 2] with contiguous rows")
-            nsym = vec(nsym, "nsym")
+            if nsym is None:
+                nsym = torch.empty((self.nrx,), dtype=torch.int32, device=dev)
+            elif not (nsym.dtype == torch.int32 and nsym.dim() == 1 and nsym.shape[0] == self.nrx and nsym.is_contiguous()):
+                raise PddcError(-1, "psk: nsym must be a contiguous int32 tensor [nrx]")
+            # as for chars: a capacity below the bound must reach the ABI as one (PDDC_ECAPACITY)
             scap = int(sym.stride(0)) // 2 if sym.shape[1] >= self.max_syms(n) else int(sym.shape[1])
-        # the ABI takes the row strides in records; a capacity below the bound must reach it as one (PDDC_ECAPACITY)
-        ccap = int(chars.stride(0)) // 4 if chars.shape[1] >= self.max_chars(n) else int(chars.shape[1])
         check(ddc_lib().pddc_psk_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
                                          chars.data_ptr() if chars.numel() else None, ccap, counts.data_ptr(),
                                          sym.data_ptr() if sym is not None and sym.numel() else None, scap,
@@ -2796,10 +2768,7 @@ class Psk(_StreamObject):
     def read(self, stream=None):
         """-> numpy structured array [nrx] (chars, symbols, acc, reg, d_last, x_last) after the batches submitted so far
         (it waits for them)"""
-        import numpy as np
-        st = np.zeros(self.nrx, dtype=psk_status_dtype())
-        check(ddc_lib().pddc_psk_read(self._h, st.ctypes.data, self._stream(stream)))
-        return st
+        return self._read(psk_status_dtype(), stream)
 
 
 class PinnedBuffer:

@@ -5,46 +5,25 @@
 #ifndef PDDC_DDC_FSK_H
 #define PDDC_DDC_FSK_H
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "ddc_decoder_rx.h"
 
 namespace pddc {
 
-static constexpr int kFskMaxRx = 1024;
-static constexpr int kFskMaxModems = 16;
-static constexpr int kFskMaxWindow = 256;
-static constexpr int kFskGroup = 4;                     /* G: receivers per block, one wave each                   */
-static constexpr int kFskThreads = 64 * kFskGroup;
-static constexpr int kFskOut = 4;                       /* O: outputs per lane and tile, 64 apart                  */
-static constexpr int kFskTile = 64 * kFskOut;           /* TT: outputs per receiver and tile                       */
-static constexpr int kFskStep = 8;                      /* taps per pass of the tap loop                           */
-/* a modem's taps on the device: per tap (hm.re, hm.im, hs.re, hs.im), W taps rounded up to a whole number of passes
- * (zeros behind the W-th: the tap loop loads whole passes and runs the first W taps only) */
-inline __host__ __device__ int fsk_row(int window) { return (window + kFskStep - 1) / kFskStep * kFskStep; }
-
-/* LDS per receiver of the group: W - 1 carried inputs and a tile of them (float2), the tile's d (float), and 2 O
- * 64-bit masks, the tile's decisions and rising edges */
-inline __host__ __device__ int fsk_row_slots(int window) { return window - 1 + kFskTile; }
+/* LDS per receiver of the group: the input row (float2), the tile's d (float), and 2 O 64-bit masks, the tile's
+ * decisions and rising edges */
 inline size_t fsk_lds_bytes(int window)
 {
-    return (size_t)kFskGroup * ((size_t)fsk_row_slots(window) * sizeof(float2) + (size_t)kFskTile * sizeof(float) + 2 * kFskOut * 8);
+    return (size_t)kDecGroup * ((size_t)dec_in_slots(window) * sizeof(float2) + (size_t)kDecTile * sizeof(float) + 2 * kDecOut * 8);
 }
 static constexpr size_t kFskLdsCap =
-    (size_t)kFskGroup * ((size_t)(kFskMaxWindow - 1 + kFskTile) * 8 + (size_t)kFskTile * 4 + 2 * kFskOut * 8);
+    (size_t)kDecGroup * ((size_t)(kDecMaxWindow - 1 + kDecTile) * 8 + (size_t)kDecTile * 4 + 2 * kDecOut * 8);
 
-/* receiver flags on the device: the header's two and the marks of the host */
-static constexpr uint32_t kFskOn = 0x1, kFskReverse = 0x2;
-static constexpr uint32_t kFskFresh = 0x100;            /* create / reset: nothing carried is read, all of it is zero */
-static constexpr uint32_t kFskClear = 0x200;            /* RESTART, OFF -> ON: carried inputs zero, IDLE, prev = mark */
-static constexpr uint32_t kFskIdle = 0x400;             /* another modem: IDLE, a character in progress is dropped  */
-static constexpr uint32_t kFskMarks = kFskFresh | kFskClear | kFskIdle;
+/* receiver flags beside kDecOn and the marks: kDecClear also means IDLE and prev = mark */
+static constexpr uint32_t kFskReverse = 0x2;
+static constexpr uint32_t kFskIdle = kDecThird;         /* another modem: IDLE, a character in progress is dropped  */
+static constexpr uint32_t kFskMarks = kDecFresh | kDecClear | kFskIdle;
 
 static constexpr uint32_t kFskStIdle = 0, kFskStStart = 1, kFskStData = 2, kFskStStop = 3;
-
-struct FskRx {
-    int32_t modem;
-    uint32_t flags;
-};
 
 struct FskModem {
     uint32_t inc;             /* bit phase per sample, 1 .. 2^30                                                 */
@@ -82,19 +61,19 @@ struct FskArgs {
     uint32_t *counts;         /* [nrx]                                                                           */
     float *d;                 /* [nrx][d_stride] or NULL                                                         */
     long long d_stride;
-    const float *taps;        /* [nmodems][fsk_row(W)][4]                                                        */
-    const FskModem *modems;   /* [nmodems]                                                                       */
-    const FskRx *rx;          /* [nrx]                                                                           */
+    const float *taps;        /* [nbank][dec_row(W)][4]                                                          */
+    const FskModem *bank;     /* [nbank]                                                                         */
+    const DecRx *rx;          /* [nrx]                                                                           */
     const FskState *state;    /* [nrx] (not read where fresh)                                                    */
     FskState *new_state;
     const float2 *hist;       /* [nrx][W - 1]: the inputs before the batch's first (not read where fresh or cleared) */
     float2 *new_hist;
     int nrx;
-    int nmodems;
+    int nbank;
     int window;               /* W                                                                               */
 };
 
-/* k_fsk: grid ceil(nrx / kFskGroup) */
+/* k_fsk: grid ceil(nrx / kDecGroup) */
 hipError_t launch_fsk(const FskArgs &a, hipStream_t s);
 
 } // namespace pddc

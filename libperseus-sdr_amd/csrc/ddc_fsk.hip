@@ -10,7 +10,12 @@
  *           s = pm + ps; d = s > 0 ? (pm - ps) / s : 0; q = |d|; then one step of the start-stop receiver.
  *           DESIGN.md 8 and include/perseus_ddc.h have the definition.
  *
- * Walk: a block owns G = 4 consecutive receivers, one wave each, and goes through the batch in tiles of TT = 256
+ * Walk: ddc_decoder_dev.h's, tiles from the batch's first sample, but spelled out here and not made of that header's
+ * functions: with the 32 scalar coefficients of a pass live this kernel sits at the edge of its registers (80 VGPRs, 106
+ * SGPRs, 8 of them spilled to VGPR lanes), and each of those functions that was put in place of the text below -- the
+ * prologue, the accessor with staging and carry, the tap loop -- moved the spills (5 .. 17), the VGPRs (79 .. 81) or
+ * the time at W = 256 (up to 1 %; profiles/r28/decoder_refactor.txt).  A change to the walk is made there and here.
+ * A block owns G = 4 consecutive receivers, one wave each, and goes through the batch in tiles of TT = 256
  * samples; the waves share nothing (each has its own rows in LDS), the two barriers per tile are there for the reader.
  *   1. the wave stages its receiver's inputs from W - 1 before the tile's first sample to its last one: consecutive
  *      lanes, consecutive inputs, 8-byte loads; an input before the batch's first comes from the carried record (zero
@@ -36,30 +41,29 @@
  *   the strides or the tile and lane a sample falls into.  No atomics, no scratch.
  * Bounds: z and d are indexed by receivers < nrx and 0 <= i < n only; the records by receivers < nrx and 0 <= e < W - 1;
  *   a staged slot is < W - 1 + TT, a read one lies in 0 .. W - 2 + TT - 1; the taps are read inside the modem's
- *   fsk_row(W) entries; the modem index is checked by the host; chars[j][c] has c below char_stride, which the host has
+ *   4 dec_row(W) floats; the modem index is checked by the host; chars[j][c] has c below char_stride, which the host has
  *   tested against the bound of pddc_fsk_max_chars (DESIGN.md derives it: the kernel's own test is never taken).
  */
 #include "ddc_fsk.h"
-#include "ddc_dev.h"
-#include "ddc_host.h"
+#include "ddc_decoder_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace pddc {
 
-/* one pass of kFskStep taps from tap t0: hw[4 s ..] = (hm.re, hm.im, hs.re, hs.im) of tap t0 + s; p points at the
+/* one pass of kDecStep taps from tap t0: hw[4 s ..] = (hm.re, hm.im, hs.re, hs.im) of tap t0 + s; p points at the
  * lane's slot of output 0, tap 0 */
 template <bool Guard>
-__device__ __forceinline__ void fsk_pass(const float2 *p, int t0, int W, const float (&hw)[4 * kFskStep], float2 (&M)[kFskOut],
-                                         float2 (&S)[kFskOut])
+__device__ __forceinline__ void fsk_pass(const float2 *p, int t0, int W, const float (&hw)[4 * kDecStep], float2 (&M)[kDecOut],
+                                         float2 (&S)[kDecOut])
 {
 #pragma unroll
-    for (int s = 0; s < kFskStep; ++s) {
+    for (int s = 0; s < kDecStep; ++s) {
         if (Guard && t0 + s >= W)
             break;
         const float mr = hw[4 * s], mi = hw[4 * s + 1], sr = hw[4 * s + 2], si = hw[4 * s + 3];
 #pragma unroll
-        for (int o = 0; o < kFskOut; ++o) {
+        for (int o = 0; o < kDecOut; ++o) {
             const float2 z = p[64 * o - (t0 + s)];
             M[o].x = fmaf(mr, z.x, M[o].x);
             M[o].x = fmaf(-mi, z.y, M[o].x);
@@ -83,23 +87,23 @@ __device__ __forceinline__ uint32_t fsk_bit(const unsigned long long *w, int i)
 __device__ __forceinline__ int fsk_next(const unsigned long long *w, int pos)
 {
     unsigned long long keep = ~0ull << (pos & 63);
-    for (int o = pos >> 6; o < kFskOut; ++o) {
+    for (int o = pos >> 6; o < kDecOut; ++o) {
         const unsigned long long v = w[o] & keep;
         if (v)
             return 64 * o + __ffsll(v) - 1;
         keep = ~0ull;
     }
-    return kFskTile;
+    return kDecTile;
 }
 
-__global__ __launch_bounds__(kFskThreads) void k_fsk(FskArgs a)
+__global__ __launch_bounds__(kDecThreads) void k_fsk(FskArgs a)
 {
-    constexpr int G = kFskGroup, O = kFskOut, TT = kFskTile, U = kFskStep;
+    constexpr int G = kDecGroup, O = kDecOut, TT = kDecTile, U = kDecStep;
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
     const int lane = (int)threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int W = a.window, H = W - 1;
-    const int RS = fsk_row_slots(W);
+    const int RS = dec_in_slots(W);
     const int j = (int)blockIdx.x * G + wave;
     const bool have = j < a.nrx;
     float2 *row = lds2 + wave * RS;
@@ -108,14 +112,14 @@ __global__ __launch_bounds__(kFskThreads) void k_fsk(FskArgs a)
     unsigned long long *sp = reinterpret_cast<unsigned long long *>(lds2 + G * RS + G * TT / 2) + wave * 2 * O;
     unsigned long long *edge = sp + O;
 
-    FskRx r{ 0, 0u };
+    DecRx r{ 0, 0u };
     if (have)
         r = a.rx[j];
     const uint32_t flags = __builtin_amdgcn_readfirstlane(r.flags);
-    const int modem = __builtin_amdgcn_readfirstlane(r.modem);
-    const bool on = have && (flags & kFskOn);
+    const int modem = __builtin_amdgcn_readfirstlane(r.bank);
+    const bool on = have && (flags & kDecOn);
     const bool reverse = (flags & kFskReverse) != 0u;
-    const bool keep = !(flags & (kFskFresh | kFskClear));            /* the carried inputs are read */
+    const bool keep = !(flags & (kDecFresh | kDecClear));            /* the carried inputs are read */
     const float2 *zr = a.z + (long long)(have ? j : 0) * a.z_stride;
     const float2 *old = a.hist + (long long)(have ? j : 0) * H;
 
@@ -131,14 +135,14 @@ __global__ __launch_bounds__(kFskThreads) void k_fsk(FskArgs a)
     uint32_t st_state = kFskStIdle, st_acc = 0u, st_k = 0u, st_shift = 0u, st_prev = 0u;
     uint32_t st_chars = 0u, st_framing = 0u, st_false = 0u;
     float st_qmin = 0.0f, st_dlast = 0.0f;
-    if (have && !(flags & kFskFresh)) {
+    if (have && !(flags & kDecFresh)) {
         const FskState *o = a.state + j;
         st_chars = o->chars;
         st_framing = o->framing;
         st_false = o->false_starts;
         st_dlast = o->d_last;
         st_prev = o->prev;
-        if (!(flags & (kFskClear | kFskIdle))) {
+        if (!(flags & (kDecClear | kFskIdle))) {
             st_start = o->start;
             st_state = o->state;
             st_acc = o->acc;
@@ -146,16 +150,16 @@ __global__ __launch_bounds__(kFskThreads) void k_fsk(FskArgs a)
             st_shift = o->shift;
             st_qmin = o->qmin;
         }
-        if (flags & kFskClear)
+        if (flags & kDecClear)
             st_prev = 0u;
     }
     uint32_t inc = 1u, nbits = 5u;
     if (on) {
-        const FskModem mo = a.modems[modem];
+        const FskModem mo = a.bank[modem];
         inc = mo.inc;
         nbits = mo.nbits;
     }
-    const float PDDC_CONSTANT *h = (const float PDDC_CONSTANT *)a.taps + (long long)modem * (fsk_row(W) * 4);
+    const float PDDC_CONSTANT *h = (const float PDDC_CONSTANT *)a.taps + (long long)modem * (dec_row(W) * 4);
     FskChar *chars = a.chars + (long long)(have ? j : 0) * a.char_stride;
     uint32_t nch = 0u;
 
@@ -303,12 +307,7 @@ __global__ __launch_bounds__(kFskThreads) void k_fsk(FskArgs a)
 
 hipError_t launch_fsk(const FskArgs &a, hipStream_t s)
 {
-    if (a.n <= 0 || a.nrx <= 0 || a.nrx > kFskMaxRx || a.nmodems < 1 || a.nmodems > kFskMaxModems || a.window < 1 ||
-        a.window > kFskMaxWindow || !a.z || a.z_stride < a.n || !a.chars || a.char_stride < 1 || !a.counts ||
-        (a.d && a.d_stride < a.n) || !a.taps || !a.modems || !a.rx || !a.state || !a.new_state || !a.hist || !a.new_hist)
-        return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.nrx + kFskGroup - 1) / kFskGroup));
-    return launch_dynamic_lds<&k_fsk>(kFskLdsCap, grid, dim3(kFskThreads), fsk_lds_bytes(a.window), s, a);
+    return dec_launch<&k_fsk>(a, !a.d || a.d_stride >= a.n, kFskLdsCap, fsk_lds_bytes(a.window), s);
 }
 
 } // namespace pddc

@@ -6,41 +6,21 @@
 #ifndef PDDC_DDC_MORSE_H
 #define PDDC_DDC_MORSE_H
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "ddc_morse_timing.h"
+#include "ddc_decoder_rx.h"
 
 namespace pddc {
 
-static constexpr int kMorseMaxRx = 1024;
-static constexpr int kMorseMaxKeyers = 16;
-static constexpr int kMorseMaxWindow = 256;
-static constexpr int kMorseGroup = 4;                   /* G: receivers per block, one wave each                   */
-static constexpr int kMorseThreads = 64 * kMorseGroup;
-static constexpr int kMorseOut = 4;                     /* O: outputs per lane and tile, 64 apart: a meter block each */
-static constexpr int kMorseBlockLog2 = 6;               /* the meter's blocks: the samples with the same m >> 6    */
-static constexpr int kMorseTile = 64 * kMorseOut;       /* TT: samples per tile, tiles aligned to m                */
-static constexpr int kMorseStep = 8;                    /* taps per pass of the tap loop                           */
-/* a keyer's taps on the device: W real taps rounded up to a whole number of passes, zeros behind the W-th */
-inline __host__ __device__ int morse_row(int window) { return (window + kMorseStep - 1) / kMorseStep * kMorseStep; }
+static constexpr int kMorseBlockLog2 = 6;               /* the meter's blocks: the samples with the same m >> 6: an output group */
 
-/* LDS per receiver of the group: W - 1 carried inputs and a tile of them (float2) */
-inline __host__ __device__ int morse_row_slots(int window) { return window - 1 + kMorseTile; }
-inline size_t morse_lds_bytes(int window) { return (size_t)kMorseGroup * (size_t)morse_row_slots(window) * sizeof(float2); }
-static constexpr size_t kMorseLdsCap = (size_t)kMorseGroup * (size_t)(kMorseMaxWindow - 1 + kMorseTile) * 8;
+/* LDS per receiver of the group: the input row */
+inline size_t morse_lds_bytes(int window) { return (size_t)kDecGroup * (size_t)dec_in_slots(window) * sizeof(float2); }
+static constexpr size_t kMorseLdsCap = (size_t)kDecGroup * (size_t)(kDecMaxWindow - 1 + kDecTile) * 8;
 
-/* receiver flags on the device: the header's two and the marks of the host */
-static constexpr uint32_t kMorseOn = 0x1, kMorseFixed = 0x2;
-static constexpr uint32_t kMorseFresh = 0x100;          /* create / reset: nothing carried is read, all of it is zero */
-static constexpr uint32_t kMorseClear = 0x200;          /* RESTART, OFF -> ON: carried inputs zero, meter and timing afresh */
-static constexpr uint32_t kMorseRekey = 0x400;          /* another keyer: meter and timing afresh, the inputs stay   */
-static constexpr uint32_t kMorseMarks = kMorseFresh | kMorseClear | kMorseRekey;
-
-struct MorseRx {
-    int32_t keyer;
-    uint32_t flags;
-};
+/* receiver flags beside kDecOn and the marks: kDecClear also means meter and timing afresh */
+static constexpr uint32_t kMorseFixed = 0x2;
+static constexpr uint32_t kMorseRekey = kDecThird;      /* another keyer: meter and timing afresh, the inputs stay   */
+static constexpr uint32_t kMorseMarks = kDecFresh | kDecClear | kMorseRekey;
 
 /* the object's float parameters */
 struct MorseParams {
@@ -67,20 +47,20 @@ struct MorseArgs {
     uint32_t *counts;         /* [nrx]                                                                           */
     float *p;                 /* [nrx][p_stride] or NULL                                                         */
     long long p_stride;
-    const float *taps;        /* [nkeyers][morse_row(W)]                                                         */
-    const MorseKeyer *keyers; /* [nkeyers]                                                                       */
-    const MorseRx *rx;        /* [nrx]                                                                           */
+    const float *taps;        /* [nbank][dec_row(W)]                                                             */
+    const MorseKeyer *bank;   /* [nbank]                                                                         */
+    const DecRx *rx;          /* [nrx]                                                                           */
     const MorseState *state;  /* [nrx] (not read where fresh)                                                    */
     MorseState *new_state;
     const float2 *hist;       /* [nrx][W - 1]: the inputs before the batch's first (not read where fresh or cleared) */
     float2 *new_hist;
     MorseParams par;
     int nrx;
-    int nkeyers;
+    int nbank;
     int window;               /* W                                                                               */
 };
 
-/* k_morse: grid ceil(nrx / kMorseGroup) */
+/* k_morse: grid ceil(nrx / kDecGroup) */
 hipError_t launch_morse(const MorseArgs &a, hipStream_t s);
 
 } // namespace pddc

@@ -8,18 +8,11 @@
  *             one step of the element timing (ddc_morse_timing.h); the block meter, whose levels govern the next block.
  *             DESIGN.md 8 and include/perseus_ddc.h have the definition.
  *
- * Walk: a block owns G = 4 consecutive receivers, one wave each, and goes through the batch in tiles of TT = 256
- * samples that are aligned to m, the object's sample count, not to the batch: tile k holds the samples with m >> 8 = k,
- * so the first and the last tile of a batch may be partial, and the lanes outside the batch are masked.  The waves share
- * nothing (each has its own row in LDS), the two barriers per tile are there for the reader.
- *   1. the wave stages its receiver's inputs from W - 1 before the tile's first sample of the batch to its last one:
- *      consecutive lanes, consecutive inputs, 8-byte loads; an input before the batch's first comes from the carried
- *      record (zero where the receiver is fresh or cleared).
- *   2. lane l makes the O = 4 outputs l, l + 64, l + 128, l + 192 of the tile, each with accumulators of its own that
- *      meet the taps in ascending t: the bits are the definition's whatever O is.  Per tap and output 8 bytes of LDS
- *      feed 2 fmaf (the compiler reads two outputs, 512 bytes apart, with one ds_read2_b64).  The taps are
- *      wave-uniform: the keyer index goes through readfirstlane and a pass of 8 real taps comes through the scalar
- *      cache into SGPRs; the last pass of a window that is no multiple of 8 tests every tap.
+ * Walk: ddc_decoder_dev.h's (steps 1 and 2: stage, filter; the compiler reads two outputs, 512 bytes apart, with one
+ * ds_read2_b64), with tiles that are aligned to m, the object's sample count, not
+ * to the batch: tile k holds the samples with m >> 8 = k, so the first and the last tile of a batch may be partial;
+ * staging begins at the tile's first sample of the batch, and the lanes outside the batch are masked.  The waves share
+ * nothing (each has its own row in LDS), the two barriers per tile are there for the reader.  Behind the filter, per tile:
  *   3. output group o of a tile is exactly one meter block (the samples with the same m >> 6), so per group, in order:
  *      the masks p > on and p < off of its 64 samples (__ballot; the thresholds are the same in every lane); lane 0
  *      advances hysteresis and timing from event to event -- with the key up the next event is the lowest set bit of
@@ -27,47 +20,28 @@
  *      where they meet), with the key down the lowest set bit of the off-mask; the wave reduces the block's hi and lo
  *      (fmaxf / fminf of values that are never NaN: any order gives the same bits); where the block's last sample is
  *      in the batch every lane makes the new pk, fl, on and off for the next group.
- *   After the last tile lane 0 writes the receiver's record and the count, and the wave the new carried inputs, the last
- *   W - 1 of [old record | batch], from global memory into the other buffer.
+ *   After the last tile lane 0 writes the receiver's record and the count.
  * OFF receivers: nothing of z is read; the record goes to the other buffer as it is (or as the host's marks say), the
  *   count is 0, the p row +0.
  * Bits: one lane makes each value with one operation sequence (contraction is off in this file, every fmaf is spelled);
  *   nothing depends on the batch cut, nrx, j's index, the other receivers, the strides or the lane a sample falls into.
  *   No atomics, no scratch.
- * Bounds: z and p are indexed by receivers < nrx and 0 <= i < n only (a tile's samples lo .. hi - 1 with 0 <= o0 + lo and
- *   o0 + hi <= n); the records by receivers < nrx and 0 <= e < W - 1; a staged slot is < W - 1 + TT, a read one lies in
- *   0 .. W - 2 + TT (a masked lane may read a slot nobody staged: inside the wave's own row, and its value is dropped);
- *   the taps are read inside the keyer's morse_row(W) entries; the keyer index is checked by the host; chars[j][c] has
- *   c below char_stride, which the host has tested against the bound of pddc_morse_max_chars (DESIGN.md derives it: the
- *   kernel's own test is never taken).
+ * Bounds: the walk's are in ddc_decoder_dev.h; a tile's samples of the batch are lo_i .. hi_i - 1 with 0 <= o0 + lo_i and
+ *   o0 + hi_i <= n, hi_i <= TT, so staging (first = lo_i, end = hi_i) reads z at 0 <= idx < n only and a masked lane's
+ *   read of a slot nobody staged stays inside the wave's own row, its value dropped (`valid`); the taps are read inside
+ *   the keyer's dec_row(W) floats; the keyer index is checked by the host (receiver 0's entry, index 0, where the wave has
+ *   none).  Here: p is indexed by receivers < nrx and o0 + 64 o + lane of valid lanes, 0 <= . < n; the state records by
+ *   receivers < nrx; chars[j][c] has c below char_stride, which the host has tested against the bound of
+ *   pddc_morse_max_chars (DESIGN.md derives it: the kernel's own test is never taken).
  */
 #include "ddc_morse.h"
-#include "ddc_dev.h"
-#include "ddc_host.h"
+#include "ddc_decoder_dev.h"
 
 #include <cfloat>
 
 #pragma clang fp contract(off)
 
 namespace pddc {
-
-/* one pass of kMorseStep taps from tap t0; p points at the lane's slot of output 0, tap 0 */
-template <bool Guard>
-__device__ __forceinline__ void morse_pass(const float2 *p, int t0, int W, const float (&hw)[kMorseStep], float2 (&y)[kMorseOut])
-{
-#pragma unroll
-    for (int s = 0; s < kMorseStep; ++s) {
-        if (Guard && t0 + s >= W)
-            break;
-        const float h = hw[s];
-#pragma unroll
-        for (int o = 0; o < kMorseOut; ++o) {
-            const float2 z = p[64 * o - (t0 + s)];
-            y[o].x = fmaf(h, z.x, y[o].x);
-            y[o].y = fmaf(h, z.y, y[o].y);
-        }
-    }
-}
 
 /* the meter, the key and the timing as a restart leaves them; the counters stay */
 __device__ __forceinline__ void morse_state_restart(MorseState &s, uint32_t two0)
@@ -81,48 +55,31 @@ __device__ __forceinline__ void morse_state_restart(MorseState &s, uint32_t two0
     s.on = s.off = INFINITY;
 }
 
-__global__ __launch_bounds__(kMorseThreads) void k_morse(MorseArgs a)
+__global__ __launch_bounds__(kDecThreads) void k_morse(MorseArgs a)
 {
-    constexpr int G = kMorseGroup, O = kMorseOut, TT = kMorseTile, U = kMorseStep;
+    constexpr int O = kDecOut, TT = kDecTile;
     static_assert(64 == 1 << kMorseBlockLog2, "an output group is a meter block");
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
-    const int lane = (int)threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int W = a.window, H = W - 1;
-    const int RS = morse_row_slots(W);
-    const int j = (int)blockIdx.x * G + wave;
-    const bool have = j < a.nrx;
-    float2 *row = lds2 + wave * RS;
+    const DecWave w = dec_wave(a.rx, a.nrx);
+    const int lane = w.lane, j = w.j;
+    float2 *row = lds2 + w.wave * dec_in_slots(W);
 
-    MorseRx r{ 0, 0u };
-    if (have)
-        r = a.rx[j];
-    const uint32_t flags = __builtin_amdgcn_readfirstlane(r.flags);
-    const int keyer = __builtin_amdgcn_readfirstlane(r.keyer);
-    const bool on = have && (flags & kMorseOn);
-    const bool fixed = (flags & kMorseFixed) != 0u;
-    const bool keep = !(flags & (kMorseFresh | kMorseClear));         /* the carried inputs are read */
-    const float2 *zr = a.z + (long long)(have ? j : 0) * a.z_stride;
-    const float2 *old = a.hist + (long long)(have ? j : 0) * H;
+    const bool on = w.have && (w.flags & kDecOn);
+    const bool fixed = (w.flags & kMorseFixed) != 0u;
+    const DecInput input = dec_input(w, a.z, a.z_stride, a.hist, H, H);
 
-    /* input idx of the receiver: before the batch's first from the carried record (H values, the newest last) */
-    auto input = [&](long long idx) -> float2 {
-        if (idx < 0)
-            return (keep && idx >= -(long long)H) ? old[H + idx] : make_float2(0.0f, 0.0f);
-        return zr[idx];
-    };
-
-    const MorseKeyer kp = a.keyers[keyer];
+    const MorseKeyer kp = a.bank[w.bank];
     const MorseParams par = a.par;
     /* the receiver's record, as the host's marks leave it */
     MorseState s{};
-    if (have && !(flags & kMorseFresh))
+    if (w.have && !(w.flags & kDecFresh))
         s = a.state[j];
-    if (flags & kMorseMarks)
+    if (w.flags & kMorseMarks)
         morse_state_restart(s, kp.two0);
 
-    const float PDDC_CONSTANT *h = (const float PDDC_CONSTANT *)a.taps + (long long)keyer * morse_row(W);
-    MorseChar *chars = a.chars + (long long)(have ? j : 0) * a.char_stride;
+    const float PDDC_CONSTANT *h = (const float PDDC_CONSTANT *)a.taps + (long long)w.bank * dec_row(W);
+    MorseChar *chars = a.chars + (long long)w.jr * a.char_stride;
     uint32_t nch = 0u;
 
     /* tiles are aligned to m: the first begins at or before the batch's first sample */
@@ -132,26 +89,12 @@ __global__ __launch_bounds__(kMorseThreads) void k_morse(MorseArgs a)
         const int lo_i = o0 < 0 ? (int)-o0 : 0;                       /* the tile's samples lo_i .. hi_i - 1 are the batch's */
         const int hi_i = (int)(a.n - o0 < TT ? a.n - o0 : TT);
         if (on)
-            for (int e = lo_i + lane; e < H + hi_i; e += 64)
-                row[e] = input(o0 - H + e);
+            dec_stage(row, input, lane, o0, lo_i, hi_i);
         __syncthreads();
 
         if (on) {
             float2 y[O];
-#pragma unroll
-            for (int o = 0; o < O; ++o)
-                y[o] = make_float2(0.0f, 0.0f);
-            const float2 *p = row + H + lane;
-            for (int t0 = 0; t0 < W; t0 += U) {
-                float hw[U];
-#pragma unroll
-                for (int i = 0; i < U; ++i)
-                    hw[i] = h[t0 + i];
-                if (t0 + U <= W)
-                    morse_pass<false>(p, t0, W, hw, y);
-                else
-                    morse_pass<true>(p, t0, W, hw, y);
-            }
+            dec_filter(row, lane, H, W, h, y);
             const unsigned long long mtile = mtile0 + (unsigned long long)(o0 - base);
 #pragma unroll
             for (int o = 0; o < O; ++o) {
@@ -235,33 +178,25 @@ __global__ __launch_bounds__(kMorseThreads) void k_morse(MorseArgs a)
                     s.lo = INFINITY;
                 }
             }
-        } else if (have && a.p) {
+        } else if (w.have && a.p) {
             for (int i = lo_i + lane; i < hi_i; i += 64)
                 a.p[(long long)j * a.p_stride + o0 + i] = 0.0f;
         }
         __syncthreads();
     }
 
-    if (!have)
+    if (!w.have)
         return;
     if (lane == 0) {
         a.new_state[j] = s;
         a.counts[j] = nch;
     }
-    /* the new carried record: the last W - 1 of [old record | batch]; an OFF receiver's batch is empty */
-    const long long used = on ? a.n : 0;
-    for (int e = lane; e < H; e += 64)
-        a.new_hist[(long long)j * H + e] = input(used - H + e);
+    dec_carry(a.new_hist, H, w, input, on ? a.n : 0);
 }
 
 hipError_t launch_morse(const MorseArgs &a, hipStream_t s)
 {
-    if (a.n <= 0 || a.nrx <= 0 || a.nrx > kMorseMaxRx || a.nkeyers < 1 || a.nkeyers > kMorseMaxKeyers || a.window < 1 ||
-        a.window > kMorseMaxWindow || !a.z || a.z_stride < a.n || !a.chars || a.char_stride < 1 || !a.counts ||
-        (a.p && a.p_stride < a.n) || !a.taps || !a.keyers || !a.rx || !a.state || !a.new_state || !a.hist || !a.new_hist)
-        return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.nrx + kMorseGroup - 1) / kMorseGroup));
-    return launch_dynamic_lds<&k_morse>(kMorseLdsCap, grid, dim3(kMorseThreads), morse_lds_bytes(a.window), s, a);
+    return dec_launch<&k_morse>(a, !a.p || a.p_stride >= a.n, kMorseLdsCap, morse_lds_bytes(a.window), s);
 }
 
 } // namespace pddc

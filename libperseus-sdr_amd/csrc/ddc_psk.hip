@@ -9,62 +9,37 @@
  *             strobe's), d, x, the bit, on a reversal the early / late correction from p[m] and p[m - 2 q], and the
  *             framing (ddc_psk_bits.h).  DESIGN.md 8 and include/perseus_ddc.h have the definition.
  *
- * Walk: a block owns G = 4 consecutive receivers, one wave each, and goes through the batch in tiles of TT = 256
- * samples from the batch's first.  The waves share nothing (each has its own row in LDS), the barriers are there for the
- * reader and for the order of a wave's own LDS traffic.
- *   1. the wave stages its receiver's inputs from W - 1 before the tile's first sample to its last one: consecutive
- *      lanes, consecutive inputs, 8-byte loads; an input before the batch's first comes from the carried record (zero
- *      where the receiver is fresh or cleared).
- *   2. lane l makes the O = 4 outputs l, l + 64, l + 128, l + 192 of the tile, each with accumulators of its own that
- *      meet the taps in ascending t: the bits are the definition's whatever O is.  Per tap and output 8 bytes of LDS
- *      feed 2 fmaf.  The taps are wave-uniform: the modem index goes through readfirstlane and a pass of 8 real taps
- *      comes through the scalar cache into SGPRs; the last pass of a window that is no multiple of 8 tests every tap.
- *      The outputs go to the row's second part, behind the B = 128 outputs before the tile (2 q <= B of them are looked
+ * Walk: ddc_decoder_dev.h's (steps 1 and 2: stage, filter), tiles from the batch's
+ * first sample.  The waves share nothing (each has its own row in LDS: the input row, then B = 128 filter outputs before
+ * the tile and the tile's), the barriers are there for the reader and for the order of a wave's own LDS traffic.
+ * Behind the filter, per tile:
+ *   3. the outputs go to the row's second part, behind the B outputs before the tile (2 q <= B of them are looked
  *      at); p is made from y where it is wanted, with the definition's one operation sequence.
- *   3. lane 0 walks the tile's strobes from one to the next: the clock jumps (~acc) / inc + 1 samples at once; a
+ *   4. lane 0 walks the tile's strobes from one to the next: the clock jumps (~acc) / inc + 1 samples at once; a
  *      strobe reads y at m - q, m and m - 2 q from LDS.  Characters and (d, x) pairs go to global memory as they come.
- *   4. the wave moves the last B outputs of [the B before | the tile] to the front for the next tile.
- *   After the last tile lane 0 writes the receiver's record and the counts, and the wave the new carried record: the last
- *   W - 1 of [old inputs | batch] from global memory, and the B outputs in front of the row, into the other buffer.
+ *   5. the wave moves the last B outputs of [the B before | the tile] to the front for the next tile.
+ *   After the last tile lane 0 writes the receiver's record and the counts, and the wave, behind the walk's carried
+ *   inputs, the B outputs in front of the row into the other buffer.
  *   y[m] is a function of the inputs alone, so a carried output has the bits a longer batch would have made.
  * OFF receivers: nothing of z is read; the record goes to the other buffer as it is (or as the host's marks say), the
  *   counts are 0.
  * Bits: one lane makes each value with one operation sequence (contraction is off in this file, every fmaf is spelled);
  *   nothing depends on the batch cut, nrx, j's index, the other receivers, the strides or the lane a sample falls into.
  *   No atomics, no scratch.
- * Bounds: z is indexed by receivers < nrx and 0 <= i < n only; the records by receivers < nrx and 0 <= e < W - 1 + B; a
- *   staged slot is < W - 1 + TT, a read one lies in 0 .. W - 2 + TT (a masked lane may read a slot nobody staged: inside
- *   the wave's own row, and its value is dropped); an output slot is B + i with 0 <= i < hi <= TT, a strobe reads B + i,
- *   B + i - q and B + i - 2 q >= 0 since 2 q <= B (the host tests q); the move reads hi + e < TT + B; the taps are read
- *   inside the modem's psk_row(W) entries; the modem index is checked by the host; chars[j][c] and sym[j][c] have c below
- *   their strides, which the host has tested against the bounds of pddc_psk_max_chars and pddc_psk_max_syms (DESIGN.md
- *   derives them: the kernel's own test is never taken).
+ * Bounds: the walk's are in ddc_decoder_dev.h (staging ends at the tile's last sample, hi <= TT; a receiver's carried
+ *   record has psk_hist_slots(W) = W - 1 + B float2, the inputs first; the taps are read inside the modem's dec_row(W)
+ *   floats; the modem index is checked by the host).  Here: the records' outputs are read and written at W - 1 + e with
+ *   0 <= e < B, of receivers < nrx; an output slot is B + i with 0 <= i < hi <= TT, a strobe reads B + i, B + i - q and
+ *   B + i - 2 q >= 0 since 2 q <= B (the host tests q); the move reads hi + e < TT + B; chars[j][c] and sym[j][c] have c
+ *   below their strides, which the host has tested against the bounds of pddc_psk_max_chars and pddc_psk_max_syms
+ *   (DESIGN.md derives them: the kernel's own test is never taken).
  */
 #include "ddc_psk.h"
-#include "ddc_dev.h"
-#include "ddc_host.h"
+#include "ddc_decoder_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace pddc {
-
-/* one pass of kPskStep taps from tap t0; p points at the lane's slot of output 0, tap 0 */
-template <bool Guard>
-__device__ __forceinline__ void psk_pass(const float2 *p, int t0, int W, const float (&hw)[kPskStep], float2 (&y)[kPskOut])
-{
-#pragma unroll
-    for (int s = 0; s < kPskStep; ++s) {
-        if (Guard && t0 + s >= W)
-            break;
-        const float h = hw[s];
-#pragma unroll
-        for (int o = 0; o < kPskOut; ++o) {
-            const float2 z = p[64 * o - (t0 + s)];
-            y[o].x = fmaf(h, z.x, y[o].x);
-            y[o].y = fmaf(h, z.y, y[o].y);
-        }
-    }
-}
 
 __device__ __forceinline__ float psk_power(float2 y) { return fmaf(y.y, y.y, y.x * y.x); }
 
@@ -77,78 +52,49 @@ __device__ __forceinline__ void psk_state_restart(PskState &s)
     s.d_last = s.x_last = 0.0f;
 }
 
-__global__ __launch_bounds__(kPskThreads) void k_psk(PskArgs a)
+__global__ __launch_bounds__(kDecThreads) void k_psk(PskArgs a)
 {
-    constexpr int G = kPskGroup, O = kPskOut, TT = kPskTile, U = kPskStep, B = kPskBack;
+    constexpr int O = kDecOut, TT = kDecTile, B = kPskBack;
     extern __shared__ __attribute__((aligned(16))) float2 lds2[];
-    const int lane = (int)threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int W = a.window, H = W - 1;
+    const DecWave w = dec_wave(a.rx, a.nrx);
+    const int lane = w.lane, j = w.j;
     const int HS = psk_hist_slots(W);
-    const int j = (int)blockIdx.x * G + wave;
-    const bool have = j < a.nrx;
-    float2 *row = lds2 + wave * psk_row_slots(W);
-    float2 *yb = row + psk_in_slots(W);                                /* B outputs before the tile, then the tile's */
+    float2 *row = lds2 + w.wave * psk_row_slots(W);
+    float2 *yb = row + dec_in_slots(W);                                /* B outputs before the tile, then the tile's */
 
-    PskRx r{ 0, 0u };
-    if (have)
-        r = a.rx[j];
-    const uint32_t flags = __builtin_amdgcn_readfirstlane(r.flags);
-    const int modem = __builtin_amdgcn_readfirstlane(r.modem);
-    const bool on = have && (flags & kPskOn);
-    const bool keep = !(flags & kPskMarks);                           /* the carried record is read */
-    const float2 *zr = a.z + (long long)(have ? j : 0) * a.z_stride;
-    const float2 *old = a.hist + (long long)(have ? j : 0) * HS;
+    const bool on = w.have && (w.flags & kDecOn);
+    const DecInput input = dec_input(w, a.z, a.z_stride, a.hist, HS, H);
+    const bool keep = input.keep;
 
-    /* input idx of the receiver: before the batch's first from the carried record (H values, the newest last) */
-    auto input = [&](long long idx) -> float2 {
-        if (idx < 0)
-            return (keep && idx >= -(long long)H) ? old[H + idx] : make_float2(0.0f, 0.0f);
-        return zr[idx];
-    };
-
-    const PskModem mp = a.modems[modem];
+    const PskModem mp = a.bank[w.bank];
     const uint32_t inc = mp.inc, step = mp.step;
     const int q = (int)mp.q;
     /* the receiver's record, as the host's marks leave it */
     PskState s{};
-    if (have && !(flags & kPskFresh))
+    if (w.have && !(w.flags & kDecFresh))
         s = a.state[j];
-    if (flags & kPskMarks)
+    if (w.flags & kPskMarks)
         psk_state_restart(s);
 
-    const float PDDC_CONSTANT *h = (const float PDDC_CONSTANT *)a.taps + (long long)modem * psk_row(W);
-    PskChar *chars = a.chars + (long long)(have ? j : 0) * a.char_stride;
-    float2 *sym = a.sym ? a.sym + (long long)(have ? j : 0) * a.sym_stride : nullptr;
+    const float PDDC_CONSTANT *h = (const float PDDC_CONSTANT *)a.taps + (long long)w.bank * dec_row(W);
+    PskChar *chars = a.chars + (long long)w.jr * a.char_stride;
+    float2 *sym = a.sym ? a.sym + (long long)w.jr * a.sym_stride : nullptr;
     uint32_t nch = 0u, nsy = 0u;
 
     /* the B outputs before the batch's first */
     for (int e = lane; e < B; e += 64)
-        yb[e] = (have && keep) ? old[H + e] : make_float2(0.0f, 0.0f);
+        yb[e] = (w.have && keep) ? input.old[H + e] : make_float2(0.0f, 0.0f);
 
     for (long long o0 = 0; o0 < a.n; o0 += TT) {
         const int hi = (int)(a.n - o0 < TT ? a.n - o0 : TT);          /* the tile's samples 0 .. hi - 1 */
         if (on)
-            for (int e = lane; e < H + hi; e += 64)
-                row[e] = input(o0 - H + e);
+            dec_stage(row, input, lane, o0, 0, hi);
         __syncthreads();
 
         if (on) {
             float2 y[O];
-#pragma unroll
-            for (int o = 0; o < O; ++o)
-                y[o] = make_float2(0.0f, 0.0f);
-            const float2 *p = row + H + lane;
-            for (int t0 = 0; t0 < W; t0 += U) {
-                float hw[U];
-#pragma unroll
-                for (int i = 0; i < U; ++i)
-                    hw[i] = h[t0 + i];
-                if (t0 + U <= W)
-                    psk_pass<false>(p, t0, W, hw, y);
-                else
-                    psk_pass<true>(p, t0, W, hw, y);
-            }
+            dec_filter(row, lane, H, W, h, y);
 #pragma unroll
             for (int o = 0; o < O; ++o)
                 if (64 * o + lane < hi)
@@ -217,7 +163,7 @@ __global__ __launch_bounds__(kPskThreads) void k_psk(PskArgs a)
         __syncthreads();
     }
 
-    if (!have)
+    if (!w.have)
         return;
     if (lane == 0) {
         a.new_state[j] = s;
@@ -225,23 +171,15 @@ __global__ __launch_bounds__(kPskThreads) void k_psk(PskArgs a)
         if (a.nsym)
             a.nsym[j] = nsy;
     }
-    /* the new carried record: the last W - 1 of [old inputs | batch], an OFF receiver's batch being empty, and the B
-     * outputs in front of the row (an OFF receiver's are the old ones) */
-    const long long used = on ? a.n : 0;
-    for (int e = lane; e < H; e += 64)
-        a.new_hist[(long long)j * HS + e] = input(used - H + e);
+    /* the new carried record: the inputs, and the B outputs in front of the row (an OFF receiver's are the old ones) */
+    dec_carry(a.new_hist, HS, w, input, on ? a.n : 0);
     for (int e = lane; e < B; e += 64)
         a.new_hist[(long long)j * HS + H + e] = yb[e];
 }
 
 hipError_t launch_psk(const PskArgs &a, hipStream_t s)
 {
-    if (a.n <= 0 || a.nrx <= 0 || a.nrx > kPskMaxRx || a.nmodems < 1 || a.nmodems > kPskMaxModems || a.window < 1 ||
-        a.window > kPskMaxWindow || !a.z || a.z_stride < a.n || !a.chars || a.char_stride < 1 || !a.counts ||
-        (a.sym && (a.sym_stride < 1 || !a.nsym)) || !a.taps || !a.modems || !a.rx || !a.state || !a.new_state || !a.hist || !a.new_hist)
-        return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((a.nrx + kPskGroup - 1) / kPskGroup));
-    return launch_dynamic_lds<&k_psk>(kPskLdsCap, grid, dim3(kPskThreads), psk_lds_bytes(a.window), s, a);
+    return dec_launch<&k_psk>(a, !a.sym || (a.sym_stride >= 1 && a.nsym), kPskLdsCap, psk_lds_bytes(a.window), s);
 }
 
 static_assert(kPskBack == 128, "the move to the front takes two slots per lane");
