@@ -1781,6 +1781,121 @@ int pddc_psk_read(pddc_psk *f, pddc_psk_status *host /* [nrx] */, void *stream);
 /* samples per tile of the kernel's walk, from the batch's first (for tests that place batch cuts on its seams) */
 int pddc_psk_tile_outputs(void);
 
+/* ---- sitor: synchronous FSK (SITOR-B / NAVTEX / AMTOR FEC) decoding per receiver ----
+ * Beside the chain, where fsk, morse and psk sit: it reads the rows the tuner, blanker, receiver filter
+ * and carrier write, and gives the 7-bit characters of the constant-ratio code of ITU-R M.476 (100
+ * baud, 170 Hz shift, no start or stop elements).  Where this block is silent, fsk's rules hold.
+ * K receivers (1 .. 1024), a window length W (1 .. 256), a bank of B modems (1 .. 16), copied at
+ * create.  Modem b: hm[W] and hs[W], complex float32 taps of the mark and the space filter as for fsk,
+ * every value finite; inc, uint32 in 1 .. 2^29: the bit phase advanced per sample, 2^32 baud / rate, so
+ * a bit is at least 8 samples; step, uint32 in 0 .. inc: the clock correction per transition, 0 is a
+ * fixed clock; lock, 0, 2, 3 or 4: the valid characters in a row that lock the framing without a
+ * phasing word (0: only a phasing word locks); unlock, 1 .. 15: the invalid characters in a row that
+ * unlock it.  Receiver j: a modem index and flags PDDC_SITOR_ON, _REVERSE, _RESTART.
+ * Input per batch: z[j z_stride + i], i < n, complex float32, any row stride, n >= 0.  m counts the
+ * object's samples since create / reset (every batch adds n, for every receiver); inputs before a
+ * receiver's first are zero.
+ * Discriminator, for every sample m of an ON receiver: exactly fsk's operation sequence.  M and S by
+ * four spelled fmaf per tap, t ascending; pm = fmaf(M.im, M.im, M.re M.re), ps likewise (REVERSE: pm
+ * and ps exchanged); space = ps > pm; s = pm + ps; d = s > 0 ? (pm - ps) / s : 0, correctly rounded;
+ * q = |d|.  Non-finite samples are data: fsk's "Non-finite samples" paragraph holds word for word, in
+ * the receiver's own row alone (while a NaN is in the window s is NaN, d = +0 and the sample reads
+ * mark; fminf drops a NaN q; nothing is left behind once the sample has left the window -- but for the
+ * bits it put into reg and the corrections it gave the clock, which the framing's own rules undo).
+ * Clock and framing, per sample, behind the discriminator, all integer.  Carried per receiver: acc
+ * (uint32), prev (initially mark), reg (uint32, 28 bits used), seen, nb, bad, locked, start (uint64),
+ * qmin, the counters chars, symbols, errors, reframes, and d_last.
+ * 1. a2 = acc + inc mod 2^32; a strobe iff a2 < acc; acc = a2.
+ * 2. On a strobe, in order: symbols++; bit = space ? 0 : 1; reg = (reg >> 1) | (bit << 27); seen =
+ *    min(seen + 1, 28); with soft, d is appended to the receiver's soft row.  The newest character is
+ *    reg >> 21, its first-received bit lowest.
+ *    a. If locked: if nb == 0: start = m, qmin = q; otherwise qmin = fminf(qmin, q).  ++nb.  When nb ==
+ *       7: the record {start, code = reg >> 21, flags = (popcount(code) == 4 ? PDDC_SITOR_VALID : 0),
+ *       quality = qmin} is emitted; chars++; nb = 0.  If the code was valid: bad = 0; otherwise
+ *       errors++ and ++bad.  If bad >= unlock: locked = 0, seen = 0.
+ *    b. Then, if reg is one of the two 28-bit phasing words -- alpha beta alpha beta and beta alpha beta
+ *       alpha with alpha = 0x0F (phasing signal 1) and beta = 0x33 (phasing signal 2), 7 bits each, the
+ *       newest character highest: 0x1ECC7B3 and 0x663D98F -- : unless locked and nb == 0: reframes++.
+ *       Then locked = 1, nb = 0, bad = 0: a character in progress is dropped.  This rule acts in every
+ *       state: four of the seven bit phases of the phasing sequence are all-valid, and rule c alone
+ *       locks on one of them (DESIGN.md 8 has what that costs).
+ *    c. Otherwise, if not locked, lock > 0, seen >= 7 lock and each of the newest `lock` 7-bit groups of
+ *       reg has four ones: locked = 1, nb = 0, bad = 0.
+ * 3. If space != prev: acc += step where acc < 2^31, else acc -= step (neither can wrap, since step <=
+ *    inc <= 2^29); then prev = space.  A transition in a bit's first half brings the strobe nearer, one
+ *    in its second half moves it away: the strobe settles half a bit behind the transitions.
+ * Receiver control.  An OFF receiver is not read and does not advance: its count and its nsoft are 0.
+ * set_rx(rx, modem, flags) takes effect at the next batch's first sample.  RESTART, or a change from
+ * OFF to ON: the carried inputs are zero, acc = 0, prev = mark, reg = seen = nb = bad = locked = 0; the
+ * counters stay.  Another modem: the carried inputs, acc and prev stay, reg = seen = nb = bad = locked
+ * = 0.  reset() clears everything and m, and synchronises the device.
+ * Outputs of process(), all device memory, no host synchronisation: chars [nrx][char_stride], the
+ * characters whose seventh strobe lies in this batch, in order; counts uint32 [nrx]; soft float32
+ * [nrx][soft_stride] or NULL, d at every strobe of the batch, in order, with nsoft uint32 [nrx]: the
+ * hook for soft-decision combining of the two copies of a mode-B character on the host.
+ * Capacity, host arithmetic.  The clock is advanced below 2^31 only, and acc enters [2^31, 2^32) below
+ * 2^31 + inc, so two strobes lie at least D_b = 2^31 div inc_b samples apart ("SITOR
+ * decoder", derives it), D the least over the bank: pddc_sitor_max_syms(f, n, &count) gives (n - 1)
+ * div D + 1, 0 for n = 0.  Emissions lie at least 7 strobes apart: pddc_sitor_max_chars gives
+ * (max_syms - 1) div 7 + 1, 0 for n = 0.  A char_stride or, with soft, a soft_stride below its bound is
+ * PDDC_ECAPACITY, and nothing is queued.  The kernel never drops.
+ * process(): every argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned
+ * pointer (z and chars 8 bytes, counts, soft and nsoft 4; soft may be NULL, and nsoft is then not
+ * looked at beyond its alignment; with n = 0 z, chars and soft are not looked at and counts and nsoft
+ * may be NULL), PDDC_ECAPACITY for a stride below n or below a bound, PDDC_EINVAL when an output's byte
+ * range meets the input's.  n = 0 is valid: counts and nsoft, if given, are set to 0, nothing carried
+ * moves, marks of set_rx stay for the next batch.  State moves only after the launch was accepted.
+ * Stream-ordered; one stream per object, one thread at a time.
+ * read(): per receiver chars, symbols, errors and reframes (since create / reset), locked, acc, reg,
+ * and d_last (the last d computed, 0 before the first) behind the batches submitted so far (it waits
+ * for them), as the next batch will find them.
+ * Every bit of chars, counts, soft, nsoft and the status is independent of the cut into batches (n = 0
+ * and n = 1 included), nrx, j's index, the other receivers, strides, grid and tile sizes.
+ * create: argument errors before any device access (non-finite taps, a modem out of range, a bad modem
+ * index, unknown flag bits); good arguments, no device: PDDC_ENODEV.
+ * The text (the M.476 table, the letters and figures shifts, the pairing of a mode-B character's two
+ * copies) is host work: Python's sitor_text has it. */
+#define PDDC_SITOR_ON       0x1u
+#define PDDC_SITOR_REVERSE  0x2u   /* mark and space exchanged                    */
+#define PDDC_SITOR_RESTART  0x4u   /* set_rx: start this receiver afresh          */
+#define PDDC_SITOR_VALID    0x1    /* pddc_sitor_char.flags: four of the seven bits are mark */
+typedef struct pddc_sitor_modem {
+    uint32_t inc;         /* 1 .. 2^29: 2^32 baud / rate                  */
+    uint32_t step;        /* 0 .. inc                                     */
+    uint32_t lock;        /* 0, 2, 3 or 4                                 */
+    uint32_t unlock;      /* 1 .. 15                                      */
+} pddc_sitor_modem;
+typedef struct pddc_sitor_rx {
+    int modem;            /* 0 .. nmodems - 1                             */
+    uint32_t flags;       /* PDDC_SITOR_ON | _REVERSE | _RESTART          */
+} pddc_sitor_rx;
+typedef struct pddc_sitor_char {
+    uint64_t start;       /* sample index m of the character's first strobe */
+    uint16_t code;        /* the first-received bit in bit 0, mark = 1    */
+    uint16_t flags;       /* PDDC_SITOR_VALID                             */
+    float quality;        /* the least |d| of the character's strobes     */
+} pddc_sitor_char;
+typedef struct pddc_sitor_status {
+    uint32_t chars, symbols, errors, reframes;
+    uint32_t locked, acc, reg;
+    float d_last;
+} pddc_sitor_status;
+typedef struct pddc_sitor pddc_sitor;
+int pddc_sitor_create(pddc_sitor **out, int device, int nrx, int window, int nmodems,
+                      const float *taps /* [nmodems][2][window] complex: hm, then hs; copied */,
+                      const pddc_sitor_modem *modems /* [nmodems] */, const pddc_sitor_rx *rx /* [nrx] */);
+int pddc_sitor_destroy(pddc_sitor *f);
+int pddc_sitor_reset(pddc_sitor *f);                  /* m and everything carried; synchronises the device */
+int pddc_sitor_set_rx(pddc_sitor *f, int rx, int modem, uint32_t flags);
+int pddc_sitor_max_syms(const pddc_sitor *f, size_t n, size_t *count);
+int pddc_sitor_max_chars(const pddc_sitor *f, size_t n, size_t *count);
+int pddc_sitor_process(pddc_sitor *f, const void *d_z, size_t n, size_t z_stride, void *d_chars, size_t char_stride,
+                       void *d_counts, void *d_soft, size_t soft_stride, void *d_nsoft, void *stream);
+/* status[nrx] after the batches submitted so far (it waits for them) */
+int pddc_sitor_read(pddc_sitor *f, pddc_sitor_status *host /* [nrx] */, void *stream);
+/* samples per tile of the kernel's walk, from the batch's first (for tests that place batch cuts on its seams) */
+int pddc_sitor_tile_outputs(void);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------- */
 /* Times `iters` back-to-back launches of the pipeline's stage-0 kernel alone
  * with HIP events on `stream`; returns average milliseconds per launch.

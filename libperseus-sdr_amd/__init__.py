@@ -151,6 +151,16 @@ class PskModem(C.Structure):
     _fields_ = [("inc", C.c_uint32), ("q", C.c_uint32), ("step", C.c_uint32)]
 
 
+class SitorRx(C.Structure):
+    """pddc_sitor_rx"""
+    _fields_ = [("modem", C.c_int), ("flags", C.c_uint32)]
+
+
+class SitorModem(C.Structure):
+    """pddc_sitor_modem"""
+    _fields_ = [("inc", C.c_uint32), ("step", C.c_uint32), ("lock", C.c_uint32), ("unlock", C.c_uint32)]
+
+
 class MorseKeyer(C.Structure):
     """pddc_morse_keyer"""
     _fields_ = [("two0", C.c_uint32), ("two_min", C.c_uint32), ("two_max", C.c_uint32), ("shift", C.c_uint32)]
@@ -513,6 +523,19 @@ def ddc_lib() -> C.CDLL:
     L.pddc_psk_tile_outputs.argtypes = []
     for name in ("pddc_psk_create", "pddc_psk_destroy", "pddc_psk_reset", "pddc_psk_set_rx", "pddc_psk_max_syms", "pddc_psk_max_chars",
                  "pddc_psk_process", "pddc_psk_read", "pddc_psk_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_sitor_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(SitorModem),
+                                    C.POINTER(SitorRx)]
+    L.pddc_sitor_destroy.argtypes = [vp]
+    L.pddc_sitor_reset.argtypes = [vp]
+    L.pddc_sitor_set_rx.argtypes = [vp, C.c_int, C.c_int, C.c_uint32]
+    L.pddc_sitor_max_syms.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_sitor_max_chars.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_sitor_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp]
+    L.pddc_sitor_read.argtypes = [vp, vp, vp]
+    L.pddc_sitor_tile_outputs.argtypes = []
+    for name in ("pddc_sitor_create", "pddc_sitor_destroy", "pddc_sitor_reset", "pddc_sitor_set_rx", "pddc_sitor_max_syms",
+                 "pddc_sitor_max_chars", "pddc_sitor_process", "pddc_sitor_read", "pddc_sitor_tile_outputs"):
         getattr(L, name).restype = C.c_int
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
@@ -1028,7 +1051,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What WBlank, Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse and Psk share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What WBlank, Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse, Psk and Sitor share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -2337,7 +2360,7 @@ class Mixer(_StreamObject):
 
 
 class _Decoder(_StreamObject):
-    """What Fsk, Morse and Psk share: the capacity bound, the chars and counts outputs of process() and the status read."""
+    """What Fsk, Morse, Psk and Sitor share: the capacity bound, the chars and counts outputs of process() and the status read."""
 
     def max_chars(self, n: int) -> int:
         """pddc_<kind>_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
@@ -2769,6 +2792,230 @@ class Psk(_Decoder):
         """-> numpy structured array [nrx] (chars, symbols, acc, reg, d_last, x_last) after the batches submitted so far
         (it waits for them)"""
         return self._read(psk_status_dtype(), stream)
+
+
+PDDC_SITOR_ON, PDDC_SITOR_REVERSE, PDDC_SITOR_RESTART = 0x1, 0x2, 0x4
+PDDC_SITOR_VALID = 0x1
+SITOR_ALPHA, SITOR_BETA, SITOR_REPEAT = 0x0F, 0x33, 0x66
+
+
+def sitor_tile_outputs() -> int:
+    """pddc_sitor_tile_outputs: samples per tile of the kernel's walk (tiles begin at the batch's first sample); host
+    arithmetic, no device"""
+    return int(ddc_lib().pddc_sitor_tile_outputs())
+
+
+def sitor_char_dtype():
+    """pddc_sitor_char as a numpy structured dtype (16 bytes)"""
+    import numpy as np
+    return np.dtype([("start", np.uint64), ("code", np.uint16), ("flags", np.uint16), ("quality", np.float32)])
+
+
+def sitor_status_dtype():
+    """pddc_sitor_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("chars", np.uint32), ("symbols", np.uint32), ("errors", np.uint32), ("reframes", np.uint32),
+                     ("locked", np.uint32), ("acc", np.uint32), ("reg", np.uint32), ("d_last", np.float32)])
+
+
+def sitor_modem(W: int, samples_per_bit: float, shift: float = 1.7, step: int = None, lock: int = 3, unlock: int = 4):
+    """A modem for Sitor's bank at samples_per_bit = rate / baud (8 or more; 100 baud for SITOR-B and NAVTEX).  `shift` is
+    the distance of the two tones in units of the baud rate (170 Hz at 100 baud: 1.7); mark lies shift / 2 above the
+    receiver's tuned frequency and space as far below it (PDDC_SITOR_REVERSE exchanges them).  The matched filters are
+    fsk_modem's: h[t] = w[t] exp(+2 pi i f t), f = +-shift / (2 samples_per_bit) cycles per sample, w a boxcar over
+    min(W, round(samples_per_bit)) samples with sum 1 and zero beyond, computed in double and rounded once.  inc =
+    round(2^32 / samples_per_bit), at most 2^29; step defaults to inc / 8, an eighth of a sample per transition.
+    -> (hm complex64[W], hs complex64[W], inc, step, lock, unlock)"""
+    import numpy as np
+    W, sps = int(W), float(samples_per_bit)
+    if W <= 0 or not sps >= 8.0 or not sps <= float(1 << 32):
+        raise PddcError(-1, "sitor_modem: W must be positive and a bit 8 .. 2^32 samples")
+    L = min(W, max(1, int(round(sps))))
+    t = np.arange(W, dtype=np.float64)
+    w = np.where(t < L, 1.0 / L, 0.0)
+    f = float(shift) / (2.0 * sps)
+    hm, hs = ((w * np.exp(2j * np.pi * g * t)).astype(np.complex64) for g in (f, -f))
+    inc = min(max(int(round(float(1 << 32) / sps)), 1), 1 << 29)
+    return hm, hs, inc, inc // 8 if step is None else int(step), int(lock), int(unlock)
+
+
+# The 7-bit constant-ratio code of ITU-R M.476 as this project holds it, the first-received bit lowest, mark (B) = 1;
+# unverified against the Recommendation's own text, which was not at hand when this was written.  35 codes, every one of
+# weight four: all there are.
+_SITOR_LETTERS = {"J": 0x17, "F": 0x1B, "C": 0x1D, "K": 0x1E, "W": 0x27, "Y": 0x2B, "P": 0x2D, "Q": 0x2E, "G": 0x35, "M": 0x39,
+                  "X": 0x3A, "V": 0x3C, "A": 0x47, "S": 0x4B, "I": 0x4D, "U": 0x4E, "D": 0x53, "R": 0x55, "E": 0x56, "N": 0x59,
+                  " ": 0x5C, "Z": 0x63, "L": 0x65, "H": 0x69, "\n": 0x6C, "O": 0x71, "B": 0x72, "T": 0x74, "\r": 0x78}
+_SITOR_LTRS, _SITOR_FIGS, _SITOR_BLANK = 0x5A, 0x36, 0x6A
+# code -> the 5-bit ITA2 code of the same character: the text goes through fsk_ita2's tables
+_SITOR_ITA2 = {code: _ITA2_LTRS.index(ch) for ch, code in _SITOR_LETTERS.items()}
+_SITOR_ITA2.update({_SITOR_LTRS: 31, _SITOR_FIGS: 27, _SITOR_BLANK: 0})
+_SITOR_FROM_ITA2 = {v: k for k, v in _SITOR_ITA2.items()}
+
+
+def sitor_encode(text: str, phasing: int = 16):
+    """The mode-B (collective FEC) slot sequence that sends `text`: slots alternate between the DX and the RX position;
+    every character goes out in a DX slot and again five slots later in an RX slot, and a slot with nothing to send
+    holds phasing signal 2 (beta, DX) or 1 (alpha, RX).  `phasing` pairs of phasing signals come first; three more DX
+    slots behind the text carry the last RX copies.  Letters and figures go through the ITA2 tables (the text starts in
+    letters; a shift code wherever the table changes).  -> (codes uint8 [slots], bits uint8 [7 slots]: each code's
+    first-received bit first, mark = 1).  Host only; what tests and tools key their signals with."""
+    import numpy as np
+    codes, figs = [], False
+    for ch in text.upper():
+        here, there = (_ITA2_FIGS, _ITA2_LTRS) if figs else (_ITA2_LTRS, _ITA2_FIGS)
+        i = here.find(ch)
+        if i <= 0 or i in (27, 31):
+            i = there.find(ch)
+            if i <= 0 or i in (27, 31):
+                raise PddcError(-1, f"sitor_encode: no code for {ch!r}")
+            figs = not figs
+            codes.append(_SITOR_FIGS if figs else _SITOR_LTRS)
+        codes.append(_SITOR_FROM_ITA2[i])
+    P, N = max(int(phasing), 0), len(codes)
+    slots = np.empty(2 * (P + N) + 6, np.uint8)
+    slots[0::2], slots[1::2] = SITOR_BETA, SITOR_ALPHA
+    for i, c in enumerate(codes):
+        slots[2 * (P + i)] = slots[2 * (P + i) + 5] = c
+    bits = ((slots[:, None] >> np.arange(7, dtype=np.uint8)[None, :]) & 1).astype(np.uint8).reshape(-1)
+    return slots, bits
+
+
+def sitor_text(records) -> str:
+    """The text of pddc_sitor_char records of one receiver (a numpy array of sitor_char_dtype, or any sequence of records
+    with start, code and flags), host only: the receiving side of mode B's time diversity.  The records are put on a
+    grid of slots by their start samples (the slot's length is the median distance of two records), so that dropped
+    characters do not shift what follows; records off the grid of the last one by more than half a bit -- what a lock
+    at a wrong bit phase gave before a phasing word put it right -- are left out; the slot parity that holds beta and, five slots on, what it held before is
+    DX; every DX character is paired with the RX one five slots on and whichever of the two is PDDC_SITOR_VALID is
+    taken, U+FFFD where neither is; the code is read through the M.476 table and the letters and figures shifts of
+    fsk_ita2's tables.  Phasing, repeat and blank signals give no character."""
+    import numpy as np
+    starts = np.array([int(r["start"]) for r in records], np.int64)
+    if starts.size == 0:
+        return ""
+    codes = [int(r["code"]) for r in records]
+    valid = [bool(int(r["flags"]) & PDDC_SITOR_VALID) for r in records]
+    gaps = np.diff(starts)
+    T = float(np.median(gaps[gaps > 0])) if (gaps > 0).any() else 1.0
+    # from the last record back: a record is on the grid if it lies a whole number of slots, to half a bit, in front of
+    # the nearest one that is
+    at, slot, ahead = {0: starts.size - 1}, 0, int(starts[-1])
+    for i in range(starts.size - 2, -1, -1):
+        gap = ahead - int(starts[i])
+        k = int(round(gap / T))
+        if k >= 1 and abs(gap - k * T) <= T / 14.0:
+            slot, ahead = slot - k, int(starts[i])
+            at[slot] = i
+    votes = [0, 0]                                                     # for DX on the even / the odd slots
+    for k, i in at.items():
+        if not valid[i]:
+            continue
+        if codes[i] == SITOR_BETA:
+            votes[k & 1] += 4
+        elif codes[i] == SITOR_ALPHA:
+            votes[~k & 1] += 4
+        else:
+            j = at.get(k + 5)
+            if j is not None and valid[j] and codes[j] == codes[i]:
+                votes[k & 1] += 1
+    dx = 0 if votes[0] >= votes[1] else 1
+    out, table = [], _ITA2_LTRS
+    first = min(at) - 5
+    first += (first ^ dx) & 1
+    for k in range(first, max(at) + 1, 2):
+        a, b = at.get(k), at.get(k + 5)
+        if a is None and b is None:
+            continue
+        if a is not None and valid[a]:
+            c = codes[a]
+        elif b is not None and valid[b]:
+            c = codes[b]
+        else:
+            out.append("�")
+            continue
+        c = _SITOR_ITA2.get(c)
+        if c is None or c == 0:                                        # alpha, beta, repeat; blank
+            continue
+        if c == 27:
+            table = _ITA2_FIGS
+        elif c == 31:
+            table = _ITA2_LTRS
+        else:
+            out.append(table[c])
+    return "".join(out)
+
+
+class Sitor(_Decoder):
+    """pddc_sitor: synchronous FSK (SITOR-B, NAVTEX, AMTOR FEC) decoding of every receiver's complex series, such as Tuner,
+    Blanker, RxFilter or Carrier write, on the device (include/perseus_ddc.h): fsk's two matched filters of W complex
+    taps, a bit clock that every transition corrects, and the framing of the 7-bit constant-ratio code by the phasing
+    signals per receiver; the output is 7-bit characters, which sitor_text turns into text on the host.
+    bank: up to 16 modems (hm, hs, inc, step, lock, unlock), as sitor_modem gives them, every hm and hs of W taps; sel:
+    one (modem, flags) per receiver, flags PDDC_SITOR_ON | PDDC_SITOR_REVERSE.  Feed it every batch in order on one
+    stream; every output bit is the same however the series is cut."""
+    _kind = "sitor"
+
+    def __init__(self, bank, sel, W: int, device: int = 0):
+        import numpy as np
+        bank = [tuple(b) for b in bank]
+        sel = [tuple(r) for r in sel]
+        self.W, self.nrx, self.nmodems, self.device = int(W), len(sel), len(bank), device
+        taps = np.zeros((max(self.nmodems, 1), 2, max(self.W, 1)), np.complex64)
+        modems = (SitorModem * max(self.nmodems, 1))()
+        u32 = lambda v: max(0, min(int(v), (1 << 32) - 1))
+        for b, (hm, hs, inc, step, lock, unlock) in enumerate(bank):
+            for i, h in enumerate((hm, hs)):
+                h = np.asarray(h, dtype=np.complex64).reshape(-1)
+                if h.size != self.W:
+                    raise PddcError(-1, f"sitor: modem {b}: {h.size} taps for a window of {self.W}")
+                taps[b, i] = h
+            modems[b] = SitorModem(u32(inc), u32(step), u32(lock), u32(unlock))
+        arr = (SitorRx * max(self.nrx, 1))()
+        for j, (modem, flags) in enumerate(sel):
+            arr[j] = SitorRx(_clip(modem), int(flags) & 0xFFFFFFFF)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_sitor_create(C.byref(h), device, self.nrx, _clip(W), self.nmodems,
+                                          taps.ctypes.data_as(C.POINTER(C.c_float)), modems, arr))
+        self._h = h
+
+    def max_syms(self, n: int) -> int:
+        """pddc_sitor_max_syms: the most strobes one receiver can have in a batch of n samples (host arithmetic)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_sitor_max_syms(self._h, int(n), C.byref(c)))
+        return int(c.value)
+
+    def process(self, z, chars=None, counts=None, soft=None, nsoft=None, want_soft: bool = False, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (chars, counts) or,
+        with want_soft or soft given, (chars, counts, soft, nsoft): chars int32 [nrx, capacity, 4], four words per
+        pddc_sitor_char (`.cpu().numpy().view(sitor_char_dtype())[..., 0]` gives the records), of which the first
+        counts[j] (int32 [nrx]) of row j are written; soft float32 [nrx, capacity], d at every strobe, of which the first
+        nsoft[j] (int32 [nrx]) are written.  The outputs, if given, are tensors of these kinds (chars and soft with any
+        capacity that suffices); no output may overlap z."""
+        n, chars, counts, ccap = self._batch(z, chars, counts)
+        scap = 0
+        if soft is not None or want_soft:
+            import torch
+            soft, scap = self._out(soft, max(self.max_syms(n), 1) if soft is None else self.max_syms(n), torch.float32,
+                                   "soft must be a float32")
+            if nsoft is None:
+                nsoft = torch.empty((self.nrx,), dtype=torch.int32, device=torch.device("cuda", self.device))
+            elif not (nsoft.dtype == torch.int32 and nsoft.dim() == 1 and nsoft.shape[0] == self.nrx and nsoft.is_contiguous()):
+                raise PddcError(-1, "sitor: nsoft must be a contiguous int32 tensor [nrx]")
+        check(ddc_lib().pddc_sitor_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                           chars.data_ptr() if chars.numel() else None, ccap, counts.data_ptr(),
+                                           soft.data_ptr() if soft is not None and soft.numel() else None, scap,
+                                           nsoft.data_ptr() if soft is not None else None, self._stream(stream)))
+        return (chars, counts) if soft is None else (chars, counts, soft, nsoft)
+
+    def set_rx(self, rx: int, modem: int, flags: int):
+        """receiver rx from the next batch's first sample on: PDDC_SITOR_RESTART, or OFF -> ON, starts it afresh (the
+        counters stay); another modem keeps the carried inputs and the clock and starts the framing afresh"""
+        check(ddc_lib().pddc_sitor_set_rx(self._h, int(rx), _clip(modem), int(flags) & 0xFFFFFFFF))
+
+    def read(self, stream=None):
+        """-> numpy structured array [nrx] (chars, symbols, errors, reframes, locked, acc, reg, d_last) after the batches
+        submitted so far (it waits for them)"""
+        return self._read(sitor_status_dtype(), stream)
 
 
 class PinnedBuffer:
