@@ -1896,6 +1896,129 @@ int pddc_sitor_read(pddc_sitor *f, pddc_sitor_status *host /* [nrx] */, void *st
 /* samples per tile of the kernel's walk, from the batch's first (for tests that place batch cuts on its seams) */
 int pddc_sitor_tile_outputs(void);
 
+/* ---- fax: radiofax (WEFAX) image decoding per receiver ----
+ * Beside the chain, where fsk, morse, psk and sitor sit: it reads the rows the tuner, blanker, receiver
+ * filter and carrier write, and gives the pixels and the line structure of a frequency-modulated
+ * facsimile (120 lines a minute, black 1500 Hz, white 2300 Hz of the audio).  The receiver is tuned to
+ * the subcarrier's centre, 1900 Hz of the audio, so black lies 400 Hz below the tuned frequency and
+ * white 400 Hz above it.  Where this block is silent, sitor's rules hold.
+ * K receivers (1 .. 1024), a window length W (1 .. 256), a bank of B modems (1 .. 16), copied at
+ * create.  Modem b: h[W], real float32 taps of the pre-detection low-pass, every value finite; inc,
+ * uint32 in 1 .. 2^31: the pixel phase advanced per sample, 2^32 width lpm / 60 / rate, so a pixel is
+ * at least 2 samples; width, 16 .. 8192 pixels per line (round(pi IOC): 1810 for IOC 576, 905 for IOC
+ * 288); box, 1 .. 16: the length of the post-detection boxcar; scale and bias, finite float32: grey
+ * level = scale v + bias; start_lo <= start_hi and stop_lo <= stop_hi, uint16, two ranges that share
+ * no value (the start tone lies below the stop tone for IOC 576 and above it for IOC 288): the
+ * crossings per line that make a line a start-tone or a stop-tone line; need, 1 .. 255: such lines in
+ * a row that start or stop an image.  Receiver j: a modem index and flags PDDC_FAX_ON, _REVERSE, _RESTART.
+ * Input per batch: z[j z_stride + i], i < n, complex float32, any row stride, n >= 0.  m counts the
+ * object's samples since create / reset; inputs, y and f before a receiver's first sample are zero.
+ * Per sample m of an ON receiver, every step with one operation sequence:
+ * 1. y = sum h[t] z[m - t]: y.re = fmaf(h[t], z.re, y.re), y.im likewise, t ascending from (0, 0).
+ * 2. w = y[m] conj(y[m - 1]): w.re = y.re p.re + y.im p.im, w.im = y.im p.re - y.re p.im (products
+ *    rounded, then the sum; p = y[m - 1]).  q = (w.re - w.re) + (w.im - w.im): 0, or NaN where w is
+ *    not finite.  d = 0 where w.re and w.im are both zero, else atan2f(w.im, w.re) (1 / pi) + q with
+ *    1 / pi = 0.318309886183790672f; f = d, under REVERSE -d.  (atan2f is the platform's: f is defined
+ *    to its accuracy, a few units in the last place; everything behind it is exact in f.)
+ * 3. a2 = acc + inc mod 2^32; a strobe iff a2 < acc; acc = a2.
+ * 4. On a strobe: v = (f[m - box + 1] + ... + f[m]), added in that order, times 1.0f / box (correctly
+ *    rounded); g = fmaf(scale, v, bias); pixel = g > 0 ? (uint8) rintf(fminf(g, 255)) : 0, so a NaN
+ *    reads 0; the pixel is appended to the receiver's pixel row; pixels++.
+ * 5. Line structure, behind the strobe, all integer.  Carried: col, start, crossings, white, level
+ *    (initially low), run, class, active.  If col == 0: start = m.  If pixel >= 192 and level is low:
+ *    level = high, crossings++.  If pixel < 64: level = low.  If pixel >= 128: white++.  ++col.  When
+ *    col == width the line ends: class = PDDC_FAX_START if start_lo <= crossings <= start_hi,
+ *    PDDC_FAX_STOP if stop_lo <= crossings <= stop_hi, else 0; run = 0 for class 0, 1 for a class
+ *    other than the previous line's, min(run + 1, 65535) for the same; if class is START and run ==
+ *    need: active = 1, images++; if class is STOP and run == need: active = 0; the record {start,
+ *    crossings, white, flags = class | (active ? PDDC_FAX_ACTIVE : 0), run} is emitted; lines++; col,
+ *    crossings and white go to 0, the level stays.
+ * Non-finite samples are data, in the receiver's own row alone.  A NaN or an infinity at sample p makes
+ * y non-finite for p .. p + W - 1 wherever its tap is not zero (0 times infinity is NaN), w for one
+ * sample more, and q turns every such f into NaN (without q two infinities would give a finite angle);
+ * v is NaN while such an f is under the boxcar and the pixels read 0: W + box samples after p nothing
+ * of it is left in f, the pixels or disc.  What the zero pixels did to crossings, white and the run of
+ * the lines they fell into stays in those lines' records, as a fade would; acc and col never depend on
+ * the data.  fminf never sees a NaN (g > 0 is false for one).
+ * Receiver control.  An OFF receiver is not read and does not advance: its counts and npix are 0.
+ * set_rx(rx, modem, flags) takes effect at the next batch's first sample.  RESTART, or a change from
+ * OFF to ON: the carried inputs, y and f are zero, acc = 0, the level is low, col, the line in
+ * progress, run, class and active are 0; the counters stay.  Another modem: the carried inputs, y, f,
+ * acc and the level stay; col, the line in progress, run, class and active are 0.  reset() clears
+ * everything and m, and synchronises the device.
+ * Outputs of process(), all device memory, no host synchronisation: pix uint8 [nrx][pix_stride], the
+ * pixels whose strobe lies in this batch, in order, with npix uint32 [nrx]; lines [nrx][line_stride],
+ * the lines whose last pixel lies in this batch, with counts uint32 [nrx]; disc float32
+ * [nrx][disc_stride] or NULL, f of every sample of the batch (an OFF receiver's row is not written):
+ * a tuning display, and what a host AFC reads.
+ * Capacity, host arithmetic.  n samples behind any acc hold at most ((n inc - 1) >> 32) + 1 strobes:
+ * pddc_fax_max_pixels(f, n, &count) gives that for the bank's greatest inc, 0 for n = 0;
+ * pddc_fax_max_lines gives (max_pixels - 1) div (the bank's least width) + 1, 0 for n = 0.  A
+ * pix_stride or a line_stride below its bound is PDDC_ECAPACITY, and nothing is queued.  The kernel
+ * never drops.
+ * process(): every argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned
+ * pointer (z and lines 8 bytes, npix, counts and disc 4, pix 1; disc may be NULL; with n = 0 z, pix,
+ * lines and disc are not looked at and npix and counts may be NULL), PDDC_ECAPACITY for a z_stride
+ * or, with disc, a disc_stride below n or a stride below its bound, PDDC_EINVAL when an output's byte
+ * range meets the input's.  n = 0 is valid: npix and counts, if given, are set to 0, nothing carried
+ * moves, marks of set_rx stay for the next batch.  State moves only after the launch was accepted.
+ * Stream-ordered; one stream per object, one thread at a time.
+ * read(): per receiver lines, pixels and images (since create / reset), active, acc, col and f_last
+ * (the last f computed, 0 before the first) behind the batches submitted so far (it waits for them),
+ * as the next batch will find them.
+ * Every bit of pix, npix, lines, counts, disc and the status is independent of the cut into batches
+ * (n = 0 and n = 1 included), nrx, j's index, the other receivers, strides, grid and tile sizes.
+ * create: argument errors before any device access (non-finite taps, a modem out of range,
+ * overlapping tone ranges, a bad modem index, unknown flag bits); good arguments, no device:
+ * PDDC_ENODEV.
+ * The image (cutting the pixel row into lines by the records, finding the phasing pulse, rotating the
+ * lines) is host work: Python's fax_image has it. */
+#define PDDC_FAX_ON       0x1u
+#define PDDC_FAX_REVERSE  0x2u   /* f negated: the receiver is tuned from the other side */
+#define PDDC_FAX_RESTART  0x4u   /* set_rx: start this receiver afresh          */
+#define PDDC_FAX_START    0x1    /* pddc_fax_line.flags: a start-tone line      */
+#define PDDC_FAX_STOP     0x2    /* a stop-tone line                            */
+#define PDDC_FAX_ACTIVE   0x4    /* an image is in progress behind this line    */
+typedef struct pddc_fax_modem {
+    uint32_t inc;         /* 1 .. 2^31: 2^32 width lpm / 60 / rate        */
+    uint32_t width;       /* 16 .. 8192 pixels per line                   */
+    uint32_t box;         /* 1 .. 16                                      */
+    float scale, bias;    /* finite                                       */
+    uint16_t start_lo, start_hi, stop_lo, stop_hi;   /* two ranges apart   */
+    uint32_t need;        /* 1 .. 255                                     */
+} pddc_fax_modem;
+typedef struct pddc_fax_rx {
+    int modem;            /* 0 .. nmodems - 1                             */
+    uint32_t flags;       /* PDDC_FAX_ON | _REVERSE | _RESTART            */
+} pddc_fax_rx;
+typedef struct pddc_fax_line {
+    uint64_t start;       /* sample index m of the strobe of the line's first pixel */
+    uint16_t crossings;   /* low -> high crossings of the hysteresis      */
+    uint16_t white;       /* pixels >= 128                                */
+    uint16_t flags;       /* PDDC_FAX_START or _STOP, | _ACTIVE           */
+    uint16_t run;         /* lines of this class in a row, this one counted */
+} pddc_fax_line;
+typedef struct pddc_fax_status {
+    uint32_t lines, pixels, images;
+    uint32_t active, acc, col;
+    float f_last;
+} pddc_fax_status;
+typedef struct pddc_fax pddc_fax;
+int pddc_fax_create(pddc_fax **out, int device, int nrx, int window, int nmodems,
+                    const float *taps /* [nmodems][window] real; copied */,
+                    const pddc_fax_modem *modems /* [nmodems] */, const pddc_fax_rx *rx /* [nrx] */);
+int pddc_fax_destroy(pddc_fax *f);
+int pddc_fax_reset(pddc_fax *f);                      /* m and everything carried; synchronises the device */
+int pddc_fax_set_rx(pddc_fax *f, int rx, int modem, uint32_t flags);
+int pddc_fax_max_pixels(const pddc_fax *f, size_t n, size_t *count);
+int pddc_fax_max_lines(const pddc_fax *f, size_t n, size_t *count);
+int pddc_fax_process(pddc_fax *f, const void *d_z, size_t n, size_t z_stride, void *d_pix, size_t pix_stride, void *d_npix,
+                     void *d_lines, size_t line_stride, void *d_counts, void *d_disc, size_t disc_stride, void *stream);
+/* status[nrx] after the batches submitted so far (it waits for them) */
+int pddc_fax_read(pddc_fax *f, pddc_fax_status *host /* [nrx] */, void *stream);
+/* samples per tile of the kernel's walk, from the batch's first (for tests that place batch cuts on its seams) */
+int pddc_fax_tile_outputs(void);
+
 /* ---- measurement hooks (bench.py) ----------------------------------------- */
 /* Times `iters` back-to-back launches of the pipeline's stage-0 kernel alone
  * with HIP events on `stream`; returns average milliseconds per launch.

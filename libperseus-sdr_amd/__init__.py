@@ -161,6 +161,18 @@ class SitorModem(C.Structure):
     _fields_ = [("inc", C.c_uint32), ("step", C.c_uint32), ("lock", C.c_uint32), ("unlock", C.c_uint32)]
 
 
+class FaxRx(C.Structure):
+    """pddc_fax_rx"""
+    _fields_ = [("modem", C.c_int), ("flags", C.c_uint32)]
+
+
+class FaxModem(C.Structure):
+    """pddc_fax_modem"""
+    _fields_ = [("inc", C.c_uint32), ("width", C.c_uint32), ("box", C.c_uint32), ("scale", C.c_float), ("bias", C.c_float),
+                ("start_lo", C.c_uint16), ("start_hi", C.c_uint16), ("stop_lo", C.c_uint16), ("stop_hi", C.c_uint16),
+                ("need", C.c_uint32)]
+
+
 class MorseKeyer(C.Structure):
     """pddc_morse_keyer"""
     _fields_ = [("two0", C.c_uint32), ("two_min", C.c_uint32), ("two_max", C.c_uint32), ("shift", C.c_uint32)]
@@ -536,6 +548,19 @@ def ddc_lib() -> C.CDLL:
     L.pddc_sitor_tile_outputs.argtypes = []
     for name in ("pddc_sitor_create", "pddc_sitor_destroy", "pddc_sitor_reset", "pddc_sitor_set_rx", "pddc_sitor_max_syms",
                  "pddc_sitor_max_chars", "pddc_sitor_process", "pddc_sitor_read", "pddc_sitor_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_fax_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(FaxModem),
+                                  C.POINTER(FaxRx)]
+    L.pddc_fax_destroy.argtypes = [vp]
+    L.pddc_fax_reset.argtypes = [vp]
+    L.pddc_fax_set_rx.argtypes = [vp, C.c_int, C.c_int, C.c_uint32]
+    L.pddc_fax_max_pixels.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_fax_max_lines.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_fax_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp, vp, sz, vp]
+    L.pddc_fax_read.argtypes = [vp, vp, vp]
+    L.pddc_fax_tile_outputs.argtypes = []
+    for name in ("pddc_fax_create", "pddc_fax_destroy", "pddc_fax_reset", "pddc_fax_set_rx", "pddc_fax_max_pixels", "pddc_fax_max_lines",
+                 "pddc_fax_process", "pddc_fax_read", "pddc_fax_tile_outputs"):
         getattr(L, name).restype = C.c_int
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
@@ -1051,7 +1076,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What WBlank, Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse, Psk and Sitor share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What WBlank, Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse, Psk, Sitor and Fax share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -2360,12 +2385,14 @@ class Mixer(_StreamObject):
 
 
 class _Decoder(_StreamObject):
-    """What Fsk, Morse, Psk and Sitor share: the capacity bound, the chars and counts outputs of process() and the status read."""
+    """What Fsk, Morse, Psk, Sitor and Fax share: the capacity bound, the chars and counts outputs of process() and the status read
+    (Fax's records are its lines: `_bound` names the bound's function)."""
+    _bound = "max_chars"
 
     def max_chars(self, n: int) -> int:
         """pddc_<kind>_max_chars: the most characters one receiver can end in a batch of n samples (host arithmetic)"""
         c = C.c_size_t()
-        check(getattr(ddc_lib(), f"pddc_{self._kind}_max_chars")(self._h, int(n), C.byref(c)))
+        check(getattr(ddc_lib(), f"pddc_{self._kind}_{self._bound}")(self._h, int(n), C.byref(c)))
         return int(c.value)
 
     def _batch(self, z, chars, counts):
@@ -3016,6 +3043,234 @@ class Sitor(_Decoder):
         """-> numpy structured array [nrx] (chars, symbols, errors, reframes, locked, acc, reg, d_last) after the batches
         submitted so far (it waits for them)"""
         return self._read(sitor_status_dtype(), stream)
+
+
+PDDC_FAX_ON, PDDC_FAX_REVERSE, PDDC_FAX_RESTART = 0x1, 0x2, 0x4
+PDDC_FAX_START, PDDC_FAX_STOP, PDDC_FAX_ACTIVE = 0x1, 0x2, 0x4
+
+
+def fax_tile_outputs() -> int:
+    """pddc_fax_tile_outputs: samples per tile of the kernel's walk (tiles begin at the batch's first sample); host
+    arithmetic, no device"""
+    return int(ddc_lib().pddc_fax_tile_outputs())
+
+
+def fax_line_dtype():
+    """pddc_fax_line as a numpy structured dtype (16 bytes)"""
+    import numpy as np
+    return np.dtype([("start", np.uint64), ("crossings", np.uint16), ("white", np.uint16), ("flags", np.uint16), ("run", np.uint16)])
+
+
+def fax_status_dtype():
+    """pddc_fax_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("lines", np.uint32), ("pixels", np.uint32), ("images", np.uint32), ("active", np.uint32), ("acc", np.uint32),
+                     ("col", np.uint32), ("f_last", np.float32)])
+
+
+def _fax_tone_range(hz: float, lpm: float, tol: float):
+    """the crossings a line of a tone of `hz` has, `tol` either way, as whole numbers that contain them"""
+    import math
+    c = float(hz) * 60.0 / float(lpm)
+    return max(int(math.floor(c * (1.0 - tol))), 0), min(int(math.ceil(c * (1.0 + tol))), 65535)
+
+
+def fax_modem(rate_hz: float, W: int, lpm: float = 120.0, ioc: int = 576, deviation_hz: float = 400.0, width: int = None,
+              start_hz: float = None, stop_hz: float = 450.0, need: int = 4, tone_tol: float = 0.1, box: int = None, beta: float = 5.0,
+              cutoff_hz: float = None):
+    """A modem for Fax's bank at a receiver rate of rate_hz, the receiver tuned to the subcarrier's centre (1900 Hz of the
+    audio): black lies deviation_hz below it and white as far above.  width = round(pi ioc) pixels per line unless given;
+    inc = round(2^32 width lpm / 60 / rate_hz), at most 2^31; box = the samples per pixel, rounded, 1 .. 16.  The taps are
+    a Kaiser-windowed (beta) low-pass of W taps whose -6 dB edge lies at cutoff_hz (at most 0.45 rate_hz), sum 1, computed
+    in double and rounded once.  cutoff_hz defaults to deviation_hz plus an eighth of the pixel rate: the deviation plus
+    half the pixel rate, which passes detail down to single pixels, leaves so much of the discriminator's noise (it grows
+    with the square of the frequency) that at a carrier 20 dB above the noise a flat grey is off by 55 levels; at an
+    eighth it is off by less than 32 (tests/test_fax_cpu.py) and detail of 8 pixels and more keeps its contrast.  scale and bias put f = -+2 deviation_hz / rate_hz on 0 and
+    255.  The start tone is 300 Hz for IOC 576 and 675 Hz for IOC 288 unless given, the stop tone 450 Hz: a line of a
+    tone has tone 60 / lpm crossings, and the ranges take tone_tol either way; `need` such lines in a row start or stop
+    an image.  -> (h float32[W], inc, width, box, scale, bias, start_lo, start_hi, stop_lo, stop_hi, need)"""
+    import numpy as np
+    W, rate, lpm = int(W), float(rate_hz), float(lpm)
+    if W <= 0 or not rate > 0.0 or not lpm > 0.0 or not float(deviation_hz) > 0.0:
+        raise PddcError(-1, "fax_modem: W, the rate, the lines per minute and the deviation must be positive")
+    width = int(round(np.pi * int(ioc))) if width is None else int(width)
+    pixel_rate = width * lpm / 60.0
+    spp = rate / pixel_rate
+    if not spp >= 2.0:
+        raise PddcError(-1, f"fax_modem: {spp:.3f} samples per pixel, a pixel needs 2")
+    inc = min(max(int(round(4294967296.0 / spp)), 1), 1 << 31)
+    box = min(max(int(round(spp)), 1), 16) if box is None else int(box)
+    cutoff_hz = float(deviation_hz) + 0.125 * pixel_rate if cutoff_hz is None else float(cutoff_hz)
+    fc = min(cutoff_hz, 0.45 * rate) / rate                                       # cycles per sample
+    t = np.arange(W, dtype=np.float64) - 0.5 * (W - 1)
+    h = 2.0 * fc * np.sinc(2.0 * fc * t) * np.kaiser(W, float(beta))
+    h = (h / h.sum()).astype(np.float32)
+    fd = 2.0 * float(deviation_hz) / rate
+    if start_hz is None:
+        start_hz = 675.0 if int(ioc) == 288 else 300.0
+    s_lo, s_hi = _fax_tone_range(start_hz, lpm, tone_tol)
+    p_lo, p_hi = _fax_tone_range(stop_hz, lpm, tone_tol)
+    return h, inc, width, box, float(np.float32(127.5 / fd)), 127.5, s_lo, s_hi, p_lo, p_hi, int(need)
+
+
+def fax_encode(image, modem, rate_hz: float, start_lines: int = 10, phasing_lines: int = 20, stop_lines: int = 10, lead: int = 0,
+               deviation_hz: float = 400.0, trail_lines: int = 1):
+    """The complex series of a whole transmission of `image` (uint8 [rows, width], 0 black, 255 white) as a receiver tuned
+    to the subcarrier's centre sees it: `lead` black pixels (the receiver's line grid is not the sender's), start_lines of
+    the start tone, phasing_lines (white for the first twentieth of the line, black behind it), the image, stop_lines of
+    the stop tone and trail_lines of black.  The tones are square waves of black and white with as many periods per line
+    as lie in the middle of the modem's ranges.  A sample's pixel is the one the modem's own clock is in, floor(m inc /
+    2^32); its frequency lies (pixel / 255 - 1 / 2) 2 deviation_hz from the centre, and the phase is continuous.  Host
+    only; what tests and tools make their signals with.  -> complex64 [samples]"""
+    import numpy as np
+    h, inc, width, box, scale, bias, s_lo, s_hi, p_lo, p_hi, need = modem
+    img = np.asarray(image, dtype=np.uint8)
+    if img.ndim != 2 or img.shape[1] != int(width):
+        raise PddcError(-1, f"fax_encode: the image must be [rows, {int(width)}]")
+    col = np.arange(int(width), dtype=np.float64)
+
+    def tone(lo, hi):
+        cycles = 0.5 * (int(lo) + int(hi))
+        return np.where((col * cycles / int(width)) % 1.0 < 0.5, 255, 0).astype(np.uint8)
+    phasing = np.where(col < max(int(width) // 20, 1), 255, 0).astype(np.uint8)
+    rows = ([tone(s_lo, s_hi)] * int(start_lines) + [phasing] * int(phasing_lines) + list(img) + [tone(p_lo, p_hi)] * int(stop_lines)
+            + [np.zeros(int(width), np.uint8)] * int(trail_lines))
+    pixels = np.concatenate([np.zeros(int(lead), np.uint8)] + rows)
+    n = int((pixels.size << 32) // int(inc))                           # the samples whose pixel exists
+    at = (np.arange(n, dtype=np.uint64) * np.uint64(int(inc))) >> np.uint64(32)
+    freq = (pixels[at].astype(np.float64) / 255.0 - 0.5) * 2.0 * float(deviation_hz) / float(rate_hz)
+    phase = 2.0 * np.pi * np.cumsum(freq)
+    return np.exp(1j * phase).astype(np.complex64)
+
+
+def fax_image(records, pixels, width: int):
+    """The pictures in one receiver's output, host only: `records` its pddc_fax_line records of all batches (a numpy
+    array of fax_line_dtype) and `pixels` its pixels of all batches, from a point where the receiver was fresh or
+    restarted, so that record k closes pixels k width .. (k + 1) width - 1.  A picture begins behind the line where a
+    START run reached `need` (run == need; the start-tone lines that follow are skipped) and ends in front of the STOP
+    run whose run reached `need`.  The lines in front that hold a short white pulse (white in at most an eighth of the
+    line, at most two crossings; up to two lines that the start tone ends in are passed over) are the phasing lines: the column where their pulse begins, the median over them, is
+    where the sender's lines begin, and every line of the picture is rotated by it; a line then runs over two of the
+    receiver's lines, and the picture has one line less than the records between.  -> a list of (picture uint8 [rows,
+    width], column, phasing lines found), one per image; a transmission without its stop tone gives none."""
+    import numpy as np
+    width = int(width)
+    rec = np.asarray(records)
+    px = np.asarray(pixels, dtype=np.uint8).reshape(-1)
+    nl = min(int(rec.shape[0]), px.size // width)
+    flags, run = rec["flags"][:nl].astype(np.int64), rec["run"][:nl].astype(np.int64)
+    out, k = [], 0
+
+    def pulse(i):
+        line = px[i * width:(i + 1) * width] >= 128
+        return line if 0 < int(line.sum()) <= width // 8 and int(rec["crossings"][i]) <= 2 else None
+    while k < nl:
+        # the line where a START run begins to count as one: ACTIVE rises there
+        if not (flags[k] & PDDC_FAX_START and flags[k] & PDDC_FAX_ACTIVE and (k == 0 or not flags[k - 1] & PDDC_FAX_ACTIVE)):
+            k += 1
+            continue
+        first = k + 1
+        while first < nl and flags[first] & PDDC_FAX_START:
+            first += 1
+        end = first
+        while end < nl and flags[end] & PDDC_FAX_ACTIVE:
+            end += 1
+        if end >= nl:
+            break
+        last = end - int(run[end]) + 1                                  # the first line of the STOP run that ended it
+        ph = first
+        while ph < min(first + 2, last) and pulse(ph) is None:         # the line the start tone ends in
+            ph += 1
+        cols = []
+        while ph < last and pulse(ph) is not None:
+            line = pulse(ph)
+            cols.append(int(np.flatnonzero(line & ~np.roll(line, 1))[0]))
+            ph += 1
+        if not cols:
+            ph = first
+        col = int(np.median(cols)) if cols else 0
+        body = px[ph * width + col:(last - 1) * width + col] if col else px[ph * width:last * width]
+        out.append((body.reshape(-1, width).copy(), col, len(cols)))
+        k = end
+    return out
+
+
+class Fax(_Decoder):
+    """pddc_fax: radiofax (WEFAX) decoding of every receiver's complex series, such as Tuner, Blanker, RxFilter or Carrier
+    write, on the device (include/perseus_ddc.h): a real low-pass of W taps, an FM discriminator, a free-running pixel
+    clock, a boxcar and a grey map per receiver; the output is pixels and one record per line (its start sample, its
+    crossings and white count, start / stop tone and whether an image is in progress), which fax_image turns into
+    pictures on the host.  bank: up to 16 modems as fax_modem gives them, every h of W taps; sel: one (modem, flags) per
+    receiver, flags PDDC_FAX_ON | PDDC_FAX_REVERSE.  Feed it every batch in order on one stream; every output bit is
+    the same however the series is cut."""
+    _kind = "fax"
+    _bound = "max_lines"
+
+    def __init__(self, bank, sel, W: int, device: int = 0):
+        import numpy as np
+        bank = [tuple(b) for b in bank]
+        sel = [tuple(r) for r in sel]
+        self.W, self.nrx, self.nmodems, self.device = int(W), len(sel), len(bank), device
+        taps = np.zeros((max(self.nmodems, 1), max(self.W, 1)), np.float32)
+        modems = (FaxModem * max(self.nmodems, 1))()
+        u32 = lambda v: max(0, min(int(v), (1 << 32) - 1))
+        u16 = lambda v: max(0, min(int(v), 65535))
+        for b, (h, inc, width, box, scale, bias, s_lo, s_hi, p_lo, p_hi, need) in enumerate(bank):
+            h = np.asarray(h, dtype=np.float32).reshape(-1)
+            if h.size != self.W:
+                raise PddcError(-1, f"fax: modem {b}: {h.size} taps for a window of {self.W}")
+            taps[b] = h
+            modems[b] = FaxModem(u32(inc), u32(width), u32(box), float(scale), float(bias), u16(s_lo), u16(s_hi), u16(p_lo), u16(p_hi),
+                                 u32(need))
+        arr = (FaxRx * max(self.nrx, 1))()
+        for j, (modem, flags) in enumerate(sel):
+            arr[j] = FaxRx(_clip(modem), int(flags) & 0xFFFFFFFF)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_fax_create(C.byref(h), device, self.nrx, _clip(W), self.nmodems,
+                                        taps.ctypes.data_as(C.POINTER(C.c_float)), modems, arr))
+        self._h = h
+
+    max_lines = _Decoder.max_chars
+
+    def max_pixels(self, n: int) -> int:
+        """pddc_fax_max_pixels: the most strobes one receiver can have in a batch of n samples (host arithmetic)"""
+        c = C.c_size_t()
+        check(ddc_lib().pddc_fax_max_pixels(self._h, int(n), C.byref(c)))
+        return int(c.value)
+
+    def process(self, z, pix=None, npix=None, lines=None, counts=None, disc=None, want_disc: bool = False, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (pix, npix, lines,
+        counts) or, with want_disc or disc given, (pix, npix, lines, counts, disc): pix uint8 [nrx, capacity] of which the
+        first npix[j] (int32 [nrx]) of row j are written; lines int32 [nrx, capacity, 4], four words per pddc_fax_line
+        (`.cpu().numpy().view(fax_line_dtype())[..., 0]` gives the records), of which the first counts[j] (int32 [nrx])
+        are written; disc float32 [nrx, n or more], f of every sample.  The outputs, if given, are tensors of these kinds
+        (pix and lines with any capacity that suffices); no output may overlap z."""
+        import torch
+        n, lines, counts, lcap = self._batch(z, lines, counts)
+        bound = self.max_pixels(n)
+        pix, pcap = self._out(pix, max(bound, 1) if pix is None else bound, torch.uint8, "pix must be a uint8")
+        if npix is None:
+            npix = torch.empty((self.nrx,), dtype=torch.int32, device=torch.device("cuda", self.device))
+        elif not (npix.dtype == torch.int32 and npix.dim() == 1 and npix.shape[0] == self.nrx and npix.is_contiguous()):
+            raise PddcError(-1, "fax: npix must be a contiguous int32 tensor [nrx]")
+        dcap = 0
+        if disc is not None or want_disc:
+            disc, dcap = self._out(disc, max(n, 1) if disc is None else n, torch.float32, "disc must be a float32")
+        check(ddc_lib().pddc_fax_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                         pix.data_ptr() if pix.numel() else None, pcap, npix.data_ptr(),
+                                         lines.data_ptr() if lines.numel() else None, lcap, counts.data_ptr(),
+                                         disc.data_ptr() if disc is not None and disc.numel() else None, dcap, self._stream(stream)))
+        return (pix, npix, lines, counts) if disc is None else (pix, npix, lines, counts, disc)
+
+    def set_rx(self, rx: int, modem: int, flags: int):
+        """receiver rx from the next batch's first sample on: PDDC_FAX_RESTART, or OFF -> ON, starts it afresh (the
+        counters stay); another modem keeps the carried inputs, the discriminator and the clock and starts the line afresh"""
+        check(ddc_lib().pddc_fax_set_rx(self._h, int(rx), _clip(modem), int(flags) & 0xFFFFFFFF))
+
+    def read(self, stream=None):
+        """-> numpy structured array [nrx] (lines, pixels, images, active, acc, col, f_last) after the batches submitted so
+        far (it waits for them)"""
+        return self._read(fax_status_dtype(), stream)
 
 
 class PinnedBuffer:

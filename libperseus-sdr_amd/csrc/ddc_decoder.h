@@ -1,5 +1,5 @@
 /*
- * ddc_decoder.h -- what the host files of the character decoders (fsk, morse, psk, sitor) share on top of ddc_stage.h: the
+ * ddc_decoder.h -- what the host files of the decoders (fsk, morse, psk, sitor; fax, whose records are lines) share on top of ddc_stage.h: the
  * handle's common members and the common ends of create / reset / set_rx / process / read.  A decoder's own file keeps
  * its bank entries with their validation and `distance`, its extra outputs, its kernel arguments and its status record.
  * What is carried per receiver lives on the device in two pairs of records, read and written in turn; nothing on the

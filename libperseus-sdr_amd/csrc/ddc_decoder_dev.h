@@ -1,7 +1,8 @@
 /*
  * ddc_decoder_dev.h -- the walk of the character decoders' kernels (gfx950 only): the filter in front of each decoder's
  * own part.  k_morse and k_psk are made of these functions, k_sitor of all but the filter (its complex pass is a copy of
- * k_fsk's); k_fsk walks the same way but spells it out (ddc_fsk.hip says why) and takes the launch from here.  The four
+ * k_fsk's); k_fsk walks the same way but spells it out (ddc_fsk.hip says why) and takes the launch from here; k_fax,
+ * whose records are lines and not characters, is made of all of them.  The five
  * .hip files include it, behind their ddc_<decoder>.h, and nothing else
  * does; its constants and the receiver record are in ddc_decoder_rx.h, which the host files see too.
  *

@@ -1,5 +1,5 @@
 /*
- * ddc_decoder_rx.h -- what both sides of a character decoder (fsk, morse, psk, sitor) name: the constants of the kernels' walk
+ * ddc_decoder_rx.h -- what both sides of a decoder (fsk, morse, psk, sitor; fax, whose records are lines) name: the constants of the kernels' walk
  * (ddc_decoder_dev.h), the receiver record of the table and its flag bits.  No function of the device and no pragma:
  * ddc_<decoder>.h includes it for the host files (ddc_decoder.h) and the kernels alike.  Internal.
  */
