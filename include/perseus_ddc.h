@@ -1723,7 +1723,8 @@ int pddc_morse_tile_outputs(void);
  * [nrx][sym_stride] or NULL, one (d, x) per strobe of the batch, in order, with nsym uint32 [nrx]: the
  * hook for a phase display, for AFC on the host (the angle of (d + j x)^2 is twice the offset's phase
  * per symbol) and for host decoders of QPSK and FEC modes.
- * Capacity, host arithmetic.  Behind a strobe acc <= inc - 1 + step, so two strobes lie at least D_b =
+ * Capacity, host arithmetic.  Behind a strobe acc <= inc - 1 + step (a late correction only puts the next
+ * strobe off), so two strobes lie at least D_b =
  * floor((2^32 - step_b) / inc_b) samples apart ("PSK decoder", derives it), D the least
  * over the bank: pddc_psk_max_syms(f, n, &count) gives (n - 1) div D + 1, 0 for n = 0.  Emissions lie
  * at least 3 strobes apart: pddc_psk_max_chars gives (max_syms - 1) div 3 + 1, 0 for n = 0.  A
@@ -2018,6 +2019,124 @@ int pddc_fax_process(pddc_fax *f, const void *d_z, size_t n, size_t z_stride, vo
 int pddc_fax_read(pddc_fax *f, pddc_fax_status *host /* [nrx] */, void *stream);
 /* samples per tile of the kernel's walk, from the batch's first (for tests that place batch cuts on its seams) */
 int pddc_fax_tile_outputs(void);
+
+/* ---- mfsk: M-tone FSK (2G ALE, MFSK16 / 8, the tone layer of Olivia and Contestia) symbols per receiver ----
+ * Beside the chain, where fsk, morse, psk, sitor and fax sit: it reads the rows the tuner, blanker,
+ * receiver filter and carrier write, and gives one record per symbol: the strongest tone, the second
+ * strongest and how far apart they were.  What the symbols mean (2G ALE's words, an interleaver, a
+ * Viterbi decoder) is host work.  Where this block is silent, psk's rules hold.
+ * K receivers (1 .. 1024), a window length W (1 .. 256), a bank of B modems (1 .. 16), copied at
+ * create.  Modem b: ntones, M in 2 .. 32; the matched filters h_k[W], k < M, complex float32 taps, in
+ * taps[b][k][t] with PDDC_MFSK_MAX_TONES = 32 tone rows per modem whatever M is: every value of all 32
+ * rows finite, the rows from M on not used; inc, uint32 in 1 .. 2^29: the symbol phase advanced per
+ * sample, 2^32 baud / rate; q in 1 .. 64 with 4 q inc <= 2^32: the early and late offset in samples,
+ * about a quarter symbol; step, uint32 in 0 .. inc: the clock correction per strobe, 0 is a fixed
+ * clock.  Receiver j: a modem index and flags PDDC_MFSK_ON, _REVERSE, _RESTART.
+ * Input per batch: z[j z_stride + i], i < n, complex float32, any row stride, n >= 0.  m counts the
+ * object's samples since create / reset.  Every float operation below is one float32 operation in the
+ * stated order, contraction off; the clock and the counter are integers.
+ * 1. Tone powers, for every sample m of an ON receiver and k = 0 .. M-1: Y_k[m] = sum over t = 0 .. W-1
+ *    of h_k[t] z[m - t], from (0, 0) with t ascending, per tap, with h = h_k[t] and z = z[m - t], fsk's
+ *    four operations: re = fmaf(h.re, z.re, re); re = fmaf(-h.im, z.im, re); im = fmaf(h.re, z.im, im);
+ *    im = fmaf(h.im, z.re, im).  p_k = fmaf(Y.im, Y.im, Y.re Y.re).
+ * 2. Best and runner-up of the sample: from a = 0, b = +0, s = 0, r = +0, with k ascending: if p_k > b:
+ *    r = b, s = a, b = p_k, a = k; otherwise, if p_k > r: r = p_k, s = k.  Ties keep the lower tone; a NaN
+ *    power is never greater and is passed over.  a[m], b[m], s[m], r[m] at samples before the receiver's
+ *    first are 0, +0, 0, +0.
+ * 3. Clock.  Carried: acc, uint32, and skip, 0 or 1, both 0 at the start.  Each sample: a2 = acc + inc
+ *    mod 2^32; a wrap iff a2 < acc; acc = a2.  A wrap with skip = 0 is a strobe; a wrap with skip = 1
+ *    is none and clears skip.
+ * 4. On a strobe at sample m, with c = m - q the on-time sample, e = m - 2 q the early one and m the
+ *    late one: tone = a[c], second = s[c] (REVERSE: M - 1 - a[c] and M - 1 - s[c], the tones counted from
+ *    the other end, for a receiver tuned from the other side); sum = b[c] + r[c]; quality = sum > 0 ?
+ *    (b[c] - r[c]) / sum : 0, the division correctly rounded: 1 is one tone alone, 0 two tones alike.
+ *    Clock correction, at every strobe: if b[m] > b[e], the peak lies later: if acc < step, skip = 1;
+ *    acc = acc - step mod 2^32.  Otherwise, if b[e] > b[m]: acc = acc + step (no overflow: acc < inc
+ *    behind a strobe).  A NaN moves nothing.  The late correction differs from psk's, which stops at
+ *    acc = 0: behind a strobe acc < inc is the fraction of a sample the wrap overshot by, and a clock
+ *    whose inc divides 2^32 (8 or 16 samples a symbol) has acc = 0 there for good -- it could be
+ *    advanced and never delayed, and a sender 200 ppm slow walked out of its symbols.  Here a late
+ *    correction larger than acc borrows from the next sample: acc goes below zero, that sample wraps
+ *    it back to acc - step + inc >= 0, and skip keeps that wrap from being a strobe.  The correction is not gated on a tone change: where the tone stays, b is flat
+ *    and the two sides differ by noise alone, which moves the clock either way; a transition on one side
+ *    pushes away from it and the one on the other side pushes back, so on data that changes tone the
+ *    strobe settles where both are as far as they can be, the symbol's middle plus q.
+ *    The record {start = c, tone, second, flags = 0, quality} is emitted; symbols++.
+ * Receiver control.  An OFF receiver is not read and does not advance: its count is 0 and its row of
+ * best is +0.  set_rx(rx, modem, flags) takes effect at the next batch's first sample.  RESTART, a
+ * change from OFF to ON and another modem do the same: the carried inputs and per-sample results are
+ * zero and the clock (acc, skip) is as at create; the counter stays.  reset() clears everything and m, and
+ * synchronises the device.
+ * Outputs of process(), all device memory, no host synchronisation: syms [nrx][sym_stride], the records
+ * of the strobes of this batch, in order (a record's start may lie up to q samples before the batch);
+ * counts uint32 [nrx]; best float32 [nrx][best_stride] or NULL, b[m] of every sample of the batch, for
+ * a tuning display.
+ * Capacity, host arithmetic.  Behind a strobe acc <= inc - 1 + step (a late correction only puts the next
+ * strobe off), so two strobes lie at least D_b =
+ * floor((2^32 - step_b) / inc_b) samples apart ("MFSK decoder", derives it), D the least
+ * over the bank: pddc_mfsk_max_syms(f, n, &count) gives (n - 1) div D + 1, 0 for n = 0.  A sym_stride
+ * below it is PDDC_ECAPACITY, and nothing is queued.
+ * process(): every argument is checked before anything is queued: PDDC_EINVAL for a NULL or misaligned
+ * pointer (z and syms 8 bytes, counts and best 4; best may be NULL; with n = 0 z, syms and best are not
+ * looked at beyond best's alignment and counts may be NULL), PDDC_ECAPACITY for a stride below n or
+ * below the bound, PDDC_EINVAL when an output's byte range meets the input's.  n = 0 is valid: counts,
+ * if given, is set to 0, nothing carried moves, marks of set_rx stay for the next batch.  State moves
+ * only after the launch was accepted.  Stream-ordered; one stream per object, one thread at a time.
+ * read(): per receiver symbols (since create / reset), acc and skip, and the last strobe's tone and quality
+ * behind the batches submitted so far (it waits for them).
+ * Every bit of syms, counts, best and the status is independent of the cut into batches (n = 0 and
+ * n = 1 included), nrx, j's index, the other receivers, strides, grid and tile sizes.
+ * Non-finite samples.  A NaN or an infinity in z[m0] stays in its receiver's row.  It is in the window
+ * of the samples m0 .. m0 + W - 1: a tone whose taps meet it has a NaN or infinite power there (a NaN
+ * is passed over by the maximum, +inf wins it), and b, r or both may be +inf or, where every tone is
+ * NaN, +0 with tone 0.  Strobes at m <= m0 + W - 1 + 2 q read such samples: their quality may be NaN
+ * (inf - inf, inf / inf) or 0 and their tone arbitrary; a comparison with a NaN moves nothing, one with
+ * +inf moves the clock by step like any other.  From sample m0 + W + 2 q on, every value a strobe reads
+ * is the one the clean series gives; what remains is the clock: acc differs by the corrections the
+ * poisoned strobes made or missed, at most step each, and the loop pulls it back like any other timing
+ * error.  The counter, the records' starts and the capacity bound hold whatever the samples are.
+ * create: argument errors before any device access (non-finite taps, a modem out of range, a bad modem
+ * index, unknown flag bits); good arguments, no device: PDDC_ENODEV. */
+#define PDDC_MFSK_ON        0x1u
+#define PDDC_MFSK_REVERSE   0x2u   /* tones counted from the other end              */
+#define PDDC_MFSK_RESTART   0x4u   /* set_rx: start this receiver afresh            */
+#define PDDC_MFSK_MAX_TONES 32     /* tone rows per modem in create's taps          */
+typedef struct pddc_mfsk_modem {
+    uint32_t ntones;      /* 2 .. 32                                      */
+    uint32_t inc;         /* 1 .. 2^29: 2^32 baud / rate                  */
+    uint32_t q;           /* 1 .. 64, 4 q inc <= 2^32                     */
+    uint32_t step;        /* 0 .. inc                                     */
+} pddc_mfsk_modem;
+typedef struct pddc_mfsk_rx {
+    int modem;            /* 0 .. nmodems - 1                             */
+    uint32_t flags;       /* PDDC_MFSK_ON | _REVERSE | _RESTART           */
+} pddc_mfsk_rx;
+typedef struct pddc_mfsk_sym {
+    uint64_t start;       /* sample index m of the symbol's on-time sample */
+    uint8_t tone;         /* the strongest tone, 0 .. M - 1               */
+    uint8_t second;       /* the second strongest                         */
+    uint16_t flags;       /* 0 for now                                    */
+    float quality;        /* (b - r) / (b + r) of the two                 */
+} pddc_mfsk_sym;
+typedef struct pddc_mfsk_status {
+    uint32_t symbols;
+    uint32_t acc, skip, tone_last;
+    float q_last;
+} pddc_mfsk_status;
+typedef struct pddc_mfsk pddc_mfsk;
+int pddc_mfsk_create(pddc_mfsk **out, int device, int nrx, int window, int nmodems,
+                     const float *taps /* [nmodems][32][window] complex (re, im); copied */,
+                     const pddc_mfsk_modem *modems /* [nmodems] */, const pddc_mfsk_rx *rx /* [nrx] */);
+int pddc_mfsk_destroy(pddc_mfsk *f);
+int pddc_mfsk_reset(pddc_mfsk *f);                    /* m and everything carried; synchronises the device */
+int pddc_mfsk_set_rx(pddc_mfsk *f, int rx, int modem, uint32_t flags);
+int pddc_mfsk_max_syms(const pddc_mfsk *f, size_t n, size_t *count);
+int pddc_mfsk_process(pddc_mfsk *f, const void *d_z, size_t n, size_t z_stride, void *d_syms, size_t sym_stride,
+                      void *d_counts, void *d_best, size_t best_stride, void *stream);
+/* status[nrx] after the batches submitted so far (it waits for them) */
+int pddc_mfsk_read(pddc_mfsk *f, pddc_mfsk_status *host /* [nrx] */, void *stream);
+/* samples per tile of the kernel's walk, from the batch's first (for tests that place batch cuts on its seams) */
+int pddc_mfsk_tile_outputs(void);
 
 /* ---- measurement hooks (bench.py) ----------------------------------------- */
 /* Times `iters` back-to-back launches of the pipeline's stage-0 kernel alone

@@ -173,6 +173,16 @@ class FaxModem(C.Structure):
                 ("need", C.c_uint32)]
 
 
+class MfskRx(C.Structure):
+    """pddc_mfsk_rx"""
+    _fields_ = [("modem", C.c_int), ("flags", C.c_uint32)]
+
+
+class MfskModem(C.Structure):
+    """pddc_mfsk_modem"""
+    _fields_ = [("ntones", C.c_uint32), ("inc", C.c_uint32), ("q", C.c_uint32), ("step", C.c_uint32)]
+
+
 class MorseKeyer(C.Structure):
     """pddc_morse_keyer"""
     _fields_ = [("two0", C.c_uint32), ("two_min", C.c_uint32), ("two_max", C.c_uint32), ("shift", C.c_uint32)]
@@ -561,6 +571,18 @@ def ddc_lib() -> C.CDLL:
     L.pddc_fax_tile_outputs.argtypes = []
     for name in ("pddc_fax_create", "pddc_fax_destroy", "pddc_fax_reset", "pddc_fax_set_rx", "pddc_fax_max_pixels", "pddc_fax_max_lines",
                  "pddc_fax_process", "pddc_fax_read", "pddc_fax_tile_outputs"):
+        getattr(L, name).restype = C.c_int
+    L.pddc_mfsk_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(MfskModem),
+                                   C.POINTER(MfskRx)]
+    L.pddc_mfsk_destroy.argtypes = [vp]
+    L.pddc_mfsk_reset.argtypes = [vp]
+    L.pddc_mfsk_set_rx.argtypes = [vp, C.c_int, C.c_int, C.c_uint32]
+    L.pddc_mfsk_max_syms.argtypes = [vp, sz, C.POINTER(sz)]
+    L.pddc_mfsk_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, vp, sz, vp]
+    L.pddc_mfsk_read.argtypes = [vp, vp, vp]
+    L.pddc_mfsk_tile_outputs.argtypes = []
+    for name in ("pddc_mfsk_create", "pddc_mfsk_destroy", "pddc_mfsk_reset", "pddc_mfsk_set_rx", "pddc_mfsk_max_syms", "pddc_mfsk_process",
+                 "pddc_mfsk_read", "pddc_mfsk_tile_outputs"):
         getattr(L, name).restype = C.c_int
     L.pddc_pipeline_time_stage0.argtypes = [vp, vp, sz, vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.pddc_pipeline_time_stage0_inline.argtypes = [vp, C.c_int]
@@ -1076,7 +1098,7 @@ def _clip(v) -> int:
 
 
 class _StreamObject:
-    """What WBlank, Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse, Psk, Sitor and Fax share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
+    """What WBlank, Spectrum, Channelizer, Tuner, Blanker, RxFilter, Carrier, Scope, Demod, Squelch, Adapt, Denoise, Eq, Audio, Mixer, Fsk, Morse, Psk, Sitor, Fax and Mfsk share: `_h`, the handle of a pddc_<_kind>_* object on `device`."""
     _kind = ""
 
     def _stream(self, stream):
@@ -2385,8 +2407,8 @@ class Mixer(_StreamObject):
 
 
 class _Decoder(_StreamObject):
-    """What Fsk, Morse, Psk, Sitor and Fax share: the capacity bound, the chars and counts outputs of process() and the status read
-    (Fax's records are its lines: `_bound` names the bound's function)."""
+    """What Fsk, Morse, Psk, Sitor, Fax and Mfsk share: the capacity bound, the chars and counts outputs of process() and the status read
+    (Fax's records are its lines, Mfsk's its symbols: `_bound` names the bound's function)."""
     _bound = "max_chars"
 
     def max_chars(self, n: int) -> int:
@@ -3271,6 +3293,274 @@ class Fax(_Decoder):
         """-> numpy structured array [nrx] (lines, pixels, images, active, acc, col, f_last) after the batches submitted so
         far (it waits for them)"""
         return self._read(fax_status_dtype(), stream)
+
+
+PDDC_MFSK_ON, PDDC_MFSK_REVERSE, PDDC_MFSK_RESTART = 0x1, 0x2, 0x4
+PDDC_MFSK_MAX_TONES = 32
+
+
+def mfsk_tile_outputs() -> int:
+    """pddc_mfsk_tile_outputs: samples per tile of the kernel's walk (tiles begin at the batch's first sample); host
+    arithmetic, no device"""
+    return int(ddc_lib().pddc_mfsk_tile_outputs())
+
+
+def mfsk_sym_dtype():
+    """pddc_mfsk_sym as a numpy structured dtype (16 bytes)"""
+    import numpy as np
+    return np.dtype([("start", np.uint64), ("tone", np.uint8), ("second", np.uint8), ("flags", np.uint16), ("quality", np.float32)])
+
+
+def mfsk_status_dtype():
+    """pddc_mfsk_status as a numpy structured dtype"""
+    import numpy as np
+    return np.dtype([("symbols", np.uint32), ("acc", np.uint32), ("skip", np.uint32), ("tone_last", np.uint32), ("q_last", np.float32)])
+
+
+def mfsk_modem(rate_hz: float, baud: float, tone0_hz: float, spacing_hz: float, ntones: int, W: int, q: int = None, step: int = None,
+               window: str = "rect"):
+    """A modem for Mfsk's bank: tone k = 0 .. ntones - 1 lies at f_k = tone0_hz + k spacing_hz (offsets from the receiver's
+    tuned frequency, either sign) and its matched filter is h_k[t] = w[t] exp(+2 pi i f_k t / rate_hz) over one symbol, L =
+    min(W, round(rate_hz / baud)) samples: w a boxcar ("rect": tones a baud apart are orthogonal) or a Hann window
+    ("hann": tones two bauds apart are, and far ones leak less), of unit sum and zero beyond L, computed in double and
+    rounded once.  The filter's output peaks where the window covers the symbol: L - 1 samples behind its first sample.
+    inc = round(2^32 baud / rate_hz), at most 2^29; q = round(a quarter symbol) in 1 .. 64 with 4 q inc <= 2^32; step
+    defaults to inc // 64, a 64th of a sample per strobe (inc is one sample of the clock): what it follows is a clock
+    error of 1 / (64 samples per symbol), so long symbols want a larger step.
+    -> (h complex64 [ntones, W], inc, q, step, tone0_hz, spacing_hz): Mfsk takes the first four, mfsk_encode all six"""
+    import numpy as np
+    W, M, rate, baud = int(W), int(ntones), float(rate_hz), float(baud)
+    if W <= 0 or not 2 <= M <= PDDC_MFSK_MAX_TONES or not rate > 0.0 or not baud > 0.0 or not rate >= 8.0 * baud:
+        raise PddcError(-1, "mfsk_modem: W positive, 2 .. 32 tones, and a symbol of 8 samples or more")
+    if window not in ("rect", "hann"):
+        raise PddcError(-1, "mfsk_modem: window is \"rect\" or \"hann\"")
+    sps = rate / baud
+    L = min(W, max(1, int(round(sps))))
+    t = np.arange(W, dtype=np.float64)
+    w = np.where(t < L, 1.0 if window == "rect" else 1.0 - np.cos(2.0 * np.pi * (t + 0.5) / L), 0.0)
+    w = w / w.sum()
+    f = float(tone0_hz) + float(spacing_hz) * np.arange(M, dtype=np.float64)
+    h = (w[None, :] * np.exp(2j * np.pi * (f / rate)[:, None] * t[None, :])).astype(np.complex64)
+    inc = min(max(int(round(4294967296.0 / sps)), 1), 1 << 29)
+    q = int(round(sps / 4.0)) if q is None else int(q)
+    q = min(max(q, 1), 64)
+    while q > 1 and 4 * q * inc > (1 << 32):
+        q -= 1
+    return h, inc, q, inc // 64 if step is None else int(step), float(tone0_hz), float(spacing_hz)
+
+
+def mfsk_encode(tones, modem, rate_hz: float, lead: float = 0.0, ppm: float = 0.0, n: int = None, amplitude: float = 1.0):
+    """The series a sender of `tones` (a sequence of tone numbers) gives a receiver on `modem` (mfsk_modem's six), for tests
+    and tools, host only: symbol k lasts T = 2^32 / inc (1 + ppm 1e-6) samples from sample lead + k T on and has the
+    frequency tone0_hz + tones[k] spacing_hz; the phase runs on from symbol to symbol (continuous-phase FSK), the
+    amplitude is constant over the symbols and zero outside them.  n: the length, default the symbols and one more.
+    -> complex64 [n]"""
+    import numpy as np
+    h, inc, _, _, tone0, spacing = modem
+    tones = np.asarray(tones, dtype=np.int64).reshape(-1)
+    if tones.size and (tones.min() < 0 or tones.max() >= np.asarray(h).shape[0]):
+        raise PddcError(-1, "mfsk_encode: a tone the modem does not have")
+    T = 4294967296.0 / float(inc) * (1.0 + float(ppm) * 1e-6)
+    if n is None:
+        n = int(np.ceil(float(lead) + (tones.size + 1) * T))
+    k = np.floor((np.arange(n, dtype=np.float64) - float(lead)) / T).astype(np.int64)
+    inside = (k >= 0) & (k < tones.size)
+    f = np.where(inside, tone0 + spacing * tones[np.clip(k, 0, max(tones.size - 1, 0))] if tones.size else 0.0, 0.0)
+    phase = np.concatenate([[0.0], np.cumsum(f[:-1])]) / float(rate_hz) if n else np.zeros(0)
+    return (float(amplitude) * inside * np.exp(2j * np.pi * (phase - np.floor(phase)))).astype(np.complex64)
+
+
+class Mfsk(_Decoder):
+    """pddc_mfsk: M-tone FSK (2G ALE, MFSK16 / 8, the tone layer of Olivia and Contestia) symbol decoding of every
+    receiver's complex series, such as Tuner, Blanker, RxFilter or Carrier write, on the device (include/perseus_ddc.h):
+    M complex matched filters of W taps, the strongest and the second strongest tone of every sample, and a symbol clock
+    that looks a quarter symbol to either side of the decision; the output is one record per symbol (start, tone,
+    second, quality), which ale_words and its like read on the host.
+    bank: up to 16 modems (h [M, W], inc, q, step, ...), as mfsk_modem gives them; sel: one (modem, flags) per receiver,
+    flags PDDC_MFSK_ON | PDDC_MFSK_REVERSE.  Feed it every batch in order on one stream; every output bit is the same
+    however the series is cut."""
+    _kind = "mfsk"
+    _bound = "max_syms"
+
+    def __init__(self, bank, sel, W: int, device: int = 0):
+        import numpy as np
+        bank = [tuple(b)[:4] for b in bank]
+        sel = [tuple(r) for r in sel]
+        self.W, self.nrx, self.nmodems, self.device = int(W), len(sel), len(bank), device
+        taps = np.zeros((max(self.nmodems, 1), PDDC_MFSK_MAX_TONES, max(self.W, 1)), np.complex64)
+        modems = (MfskModem * max(self.nmodems, 1))()
+        u32 = lambda v: max(0, min(int(v), (1 << 32) - 1))
+        for b, (h, inc, q, step) in enumerate(bank):
+            h = np.asarray(h, dtype=np.complex64)
+            if h.ndim != 2 or h.shape[1] != self.W or h.shape[0] > PDDC_MFSK_MAX_TONES:
+                raise PddcError(-1, f"mfsk: modem {b}: taps {h.shape} for a window of {self.W} and at most {PDDC_MFSK_MAX_TONES} tones")
+            taps[b, :h.shape[0]] = h
+            modems[b] = MfskModem(h.shape[0], u32(inc), u32(q), u32(step))
+        arr = (MfskRx * max(self.nrx, 1))()
+        for j, (modem, flags) in enumerate(sel):
+            arr[j] = MfskRx(_clip(modem), int(flags) & 0xFFFFFFFF)
+        h = C.c_void_p()
+        check(ddc_lib().pddc_mfsk_create(C.byref(h), device, self.nrx, _clip(W), self.nmodems,
+                                         taps.ctypes.data_as(C.POINTER(C.c_float)), modems, arr))
+        self._h = h
+
+    max_syms = _Decoder.max_chars
+
+    def process(self, z, syms=None, counts=None, best=None, want_best: bool = False, stream=None):
+        """One batch: a complex64 CUDA tensor [nrx, n] whose rows are contiguous (any row stride).  -> (syms, counts) or,
+        with want_best or best given, (syms, counts, best): syms int32 [nrx, capacity, 4], four words per pddc_mfsk_sym
+        (`.cpu().numpy().view(mfsk_sym_dtype())[..., 0]` gives the records), of which the first counts[j] (int32 [nrx])
+        of row j are written; best float32 [nrx, n], the strongest tone's power at every sample.  syms, counts and best,
+        if given, are tensors of these kinds (syms and best with any capacity that suffices); no output may overlap z."""
+        n, syms, counts, scap = self._batch(z, syms, counts)
+        bcap = 0
+        if best is not None or want_best:
+            import torch
+            best, bcap = self._out(best, n, torch.float32, "best must be a float32")
+        check(ddc_lib().pddc_mfsk_process(self._h, z.data_ptr() if n else None, n, int(z.stride(0)),
+                                          syms.data_ptr() if syms.numel() else None, scap, counts.data_ptr(),
+                                          best.data_ptr() if best is not None and best.numel() else None, bcap, self._stream(stream)))
+        return (syms, counts) if best is None else (syms, counts, best[:, :n])
+
+    def set_rx(self, rx: int, modem: int, flags: int):
+        """receiver rx from the next batch's first sample on: PDDC_MFSK_RESTART, OFF -> ON or another modem starts it
+        afresh (the counter stays)"""
+        check(ddc_lib().pddc_mfsk_set_rx(self._h, int(rx), _clip(modem), int(flags) & 0xFFFFFFFF))
+
+    def read(self, stream=None):
+        """-> numpy structured array [nrx] (symbols, acc, skip, tone_last, q_last) after the batches submitted so far (it waits
+        for them)"""
+        return self._read(mfsk_status_dtype(), stream)
+
+
+# ---- 2G ALE (MIL-STD-188-141A) on the host: words from Mfsk's symbol records -------------------------------------------
+# The Golay generator, the bit order within a symbol and a word, the interleaving and the inverted half below are this
+# project's own statement from memory, NOT verified against the standard's text: ale_encode and ale_words agree with each
+# other (the tests are round trips), and an on-air signal may need one of the conventions turned round.
+
+ALE_PREAMBLES = ("DATA", "THRU", "TO", "TWS", "FROM", "TIS", "CMD", "REP")
+ALE_BASIC38 = "ABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789@?"
+ALE_WORD_SYMBOLS = 49
+_ALE_GRAY = (0b000, 0b001, 0b011, 0b010, 0b110, 0b111, 0b101, 0b100)
+_ALE_GOLAY_POLY = 0xC75                                 # x^11 + x^10 + x^6 + x^5 + x^4 + x^2 + 1
+_ale_golay_table = None
+
+
+def ale_modem(rate_hz: float, W: int, q: int = None, step: int = None):
+    """mfsk_modem for 2G ALE: 8 tones 750 .. 2500 Hz, 250 Hz apart, 125 baud, Hann-windowed filters (the tones are two
+    bauds apart).  step defaults to inc // 2, half a sample per strobe: at 78 samples a symbol mfsk_modem's 64th of a
+    sample would not follow a sender 200 ppm off"""
+    h, inc, q, _, tone0, spacing = mfsk_modem(rate_hz, 125.0, 750.0, 250.0, 8, W, q=q, step=0, window="hann")
+    return h, inc, q, inc // 2 if step is None else int(step), tone0, spacing
+
+
+def ale_tribits(tones):
+    """The three bits of each tone, the first highest, by ALE's Gray map: tone 0 .. 7 -> 000, 001, 011, 010, 110, 111,
+    101, 100.  -> a list of 0 / 1, three per tone"""
+    out = []
+    for t in tones:
+        g = _ALE_GRAY[int(t) & 7]
+        out += [g >> 2 & 1, g >> 1 & 1, g & 1]
+    return out
+
+
+def ale_golay_check(data12: int) -> int:
+    """The 12 check bits of the extended Golay (24, 12) code for 12 data bits: the remainder of data x^11 by the
+    generator (11 bits), then an even parity bit over the 23"""
+    r = (int(data12) & 0xFFF) << 11
+    for i in range(22, 10, -1):
+        if r >> i & 1:
+            r ^= _ALE_GOLAY_POLY << (i - 11)
+    r &= 0x7FF
+    return r << 1 | (bin((int(data12) & 0xFFF) << 11 | r).count("1") & 1)
+
+
+def ale_golay_decode(word24: int):
+    """A received codeword (12 data bits, then 12 check bits) -> (data12, errors corrected) or None where more than
+    3 bits are wrong (the code's distance is 8: every pattern of up to 3 errors is corrected, none of 4 miscorrected)"""
+    global _ale_golay_table
+    if _ale_golay_table is None:
+        from itertools import combinations
+        table = {0: 0}
+        for w in (1, 2, 3):
+            for bits in combinations(range(24), w):
+                e = sum(1 << b for b in bits)
+                table[ale_golay_check(e >> 12) ^ (e & 0xFFF)] = e
+        _ale_golay_table = table
+    word24 = int(word24) & 0xFFFFFF
+    e = _ale_golay_table.get(ale_golay_check(word24 >> 12) ^ (word24 & 0xFFF))
+    return None if e is None else ((word24 ^ e) >> 12, bin(e).count("1"))
+
+
+def ale_encode(words):
+    """The tones of ALE words, 49 per word.  words: (preamble, three characters) pairs, the preamble a name of
+    ALE_PREAMBLES or its number, the characters of ALE_BASIC38 -- ("TO", "ABC").  A word is 24 bits, the preamble's
+    three and three 7-bit ASCII characters, the first bit highest; its halves A and B become Golay codewords, B's check
+    bits inverted; the 48 bits go out interleaved A1 B1 A2 B2 ... with a stuff bit 0 behind, three times over: 147 bits,
+    49 tones of three bits.  -> a list of tone numbers"""
+    bits = []
+    for pre, chars in words:
+        p = ALE_PREAMBLES.index(pre) if isinstance(pre, str) else int(pre)
+        if not 0 <= p < 8 or len(chars) != 3 or any(c not in ALE_BASIC38 for c in chars):
+            raise PddcError(-1, f"ale_encode: ({pre!r}, {chars!r}) is no ALE word")
+        w = p << 21 | ord(chars[0]) << 14 | ord(chars[1]) << 7 | ord(chars[2])
+        a, b = w >> 12, w & 0xFFF
+        ca, cb = a << 12 | ale_golay_check(a), b << 12 | (ale_golay_check(b) ^ 0xFFF)
+        one = []
+        for i in range(23, -1, -1):
+            one += [ca >> i & 1, cb >> i & 1]
+        bits += (one + [0]) * 3
+    inverse = {g: t for t, g in enumerate(_ALE_GRAY)}
+    return [inverse[bits[i] << 2 | bits[i + 1] << 1 | bits[i + 2]] for i in range(0, len(bits), 3)]
+
+
+def ale_words(records):
+    """The ALE words in a receiver's symbols: pddc_mfsk_sym records (a numpy array of mfsk_sym_dtype) or plain tone
+    numbers.  It slides over them; at every offset it takes 49 symbols = 147 bits, votes 2 of 3 over bits i, i + 49 and
+    i + 98, drops the stuff bit, de-interleaves, restores the inverted check bits of the second codeword and
+    Golay-decodes both halves with up to 3 errors each.  A word is accepted when both decode and its three characters
+    are of ALE_BASIC38.  -> a list of dicts {start: the first symbol's start (its index for plain tones), preamble,
+    chars, errors: the bits the two decoders corrected, split: of the 49 votes those that were not unanimous}.
+    That rule alone accepts about one wrong offset in a hundred -- there the three copies are those of two neighbouring
+    words, and what they vote into decodes as often as random bits do (2325 of 4096 syndromes, twice, and 38 of 128
+    characters, three times): such words have errors of 4 .. 6 and many split votes, and do not lie 49 symbols from the
+    next one.  A caller that wants none of them keeps the words with split = 0 or chains them by their starts."""
+    import numpy as np
+    rec = np.asarray(records)
+    named = rec.dtype.names is not None
+    tones = (rec["tone"] if named else rec).astype(np.int64).reshape(-1)
+    starts = rec["start"].reshape(-1) if named else np.arange(tones.size)
+    gray = np.array(_ALE_GRAY, np.int64)[tones & 7]
+    bits = np.stack([gray >> 2 & 1, gray >> 1 & 1, gray & 1], axis=1).reshape(-1)
+    weights = 1 << np.arange(23, -1, -1, dtype=np.int64)
+    out = []
+    for o in range(0, tones.size - ALE_WORD_SYMBOLS + 1):
+        b = bits[3 * o:3 * o + 147].reshape(3, 49)
+        votes = b.sum(axis=0)
+        v = (votes >= 2).astype(np.int64)[:48]
+        ca, cb = int(v[0::2] @ weights), int(v[1::2] @ weights) ^ 0xFFF
+        da, db = ale_golay_decode(ca), ale_golay_decode(cb)
+        if da is None or db is None:
+            continue
+        w = da[0] << 12 | db[0]
+        chars = "".join(chr(w >> s & 0x7F) for s in (14, 7, 0))
+        if all(c in ALE_BASIC38 for c in chars):
+            out.append({"start": int(starts[o]), "preamble": ALE_PREAMBLES[w >> 21], "chars": chars, "errors": da[1] + db[1],
+                        "split": int(((votes != 0) & (votes != 3)).sum())})
+    return out
+
+
+def ale_text(words) -> str:
+    """The addresses in ale_words' words: a DATA or REP word carries on the address of the word before it, any other
+    preamble begins one; the fill character @ is dropped.  -> "TO ABCDEF TIS XYZ" """
+    parts = []
+    for w in words:
+        chars = w["chars"].replace("@", "")
+        if w["preamble"] in ("DATA", "REP") and parts:
+            parts[-1] += chars
+        else:
+            parts.append(w["preamble"] + " " + chars)
+    return " ".join(parts)
 
 
 class PinnedBuffer:
